@@ -5,8 +5,18 @@ Metric (BASELINE.json): output Mpix/s of Lanczos-3 U8 3840x2160 -> 1920x1080 (co
 process per GPU, plus the HBM roofline fraction of the kernel.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c1|g1|g2|g3]
-                  [--frames B] [--shard image|band]
+                  [--frames B] [--shard image|band] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it generates the batches, warms up, times
+the K steps and prints the JSON line (`parity` is then "unchecked").  --full adds everything else
+described below: the parity check against the oracle, the same-batch reuse probe, the second batch
+size (`batch_alt`), the C3 / C4 `secondary` lines with their streaming probes, the CPU baseline and
+the reference-benchmark workload; the --no-* switches take single legs out of a --full run.
+--dump-outputs DIR writes what the last timed step computed (image mode: the output batch of rank
+0's last launch; band mode: the frames gathered on rank 0) as DIR/dst.npy, float32: the whole array
+up to DUMP_MAX_ELEMS elements, a fixed seeded sample of that many elements of it above.  The inputs
+are seeded, so two runs with the same arguments write the same file.
 
 --shard image (default): each rank resizes its own device-resident batch of B frames (weak
   scaling, no data-path collective).  A "step" = one libiqo_hip launch over the rank's batch.
@@ -22,11 +32,11 @@ Inputs are synthetic uniform-random U8 frames generated before timing.  Image mo
 several distinct device batches, one per step (--rotate; auto: >= 3 batches and >= 2.5 GB per cycle): relaunching
 the SAME batch lets the 256 MiB Infinity Cache serve part of the reads (C2: ~15 % faster), which no
 real pipeline sees; that figure is reported separately as reuse_probe.  Rank 0 prints ONE JSON
-line.  With the default config (C2) at N = 1 the line also carries `secondary`: C3 (64 frames) and
+line.  With --full and the default config (C2) at N = 1 the line also carries `secondary`: C3 (64 frames) and
 C4 (256 frames) timed the same way on their own rotated batches, with parity on frames 0, mid and
 last, and a plain streaming kernel of each config's read:write byte mix (libiqo_probe.so) on the
 same buffers -- the on-box ceiling each kernel's fraction can be read against.
-The CPU baseline (rank 0, N=1 only) times the reference's own CPU path -- its public
+The CPU baseline (--full; rank 0, N=1 only) times the reference's own CPU path -- its public
 classes with their CPUID dispatch (AVX512 on the node) and OpenMP, compiled from its sources into
 oracle/_ref -- plus its Generic impl, on the host CPUs this process may use, over a bounded
 sample of the same workload.
@@ -461,6 +471,33 @@ def secondary_config(name, frames, dev, stream, steps, verify, probe=None, make=
     return res
 
 
+DUMP_MAX_ELEMS = 8 << 20  # 32 MiB of float32 per dumped array
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> device tensor) as DIR/<name>.npy, float32.
+    An array of more than DUMP_MAX_ELEMS elements is written as that many of its elements, taken
+    at flat indices drawn once from DUMP_SEED (sorted, the same for every run of one shape)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_ELEMS, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        if a.size == n:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = {"shape": list(t.shape), "elements_written": int(a.size), "sampled": bool(a.size != n)}
+    return written
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` started without a launcher (no WORLD_SIZE in the environment): start N
     rank processes of this same command line, one per GPU, as torch.distributed.run would (RANK /
@@ -526,8 +563,21 @@ def main():
     ap.add_argument("--force-general", action="store_true")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                     help="plan option (iqo_hip_plan_set_option), repeatable; speed-only A/B knobs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity check against the oracle, "
+                         "the reuse probe, batch_alt, the C3 / C4 secondary lines and streaming probes, the CPU "
+                         "baseline and the reference-benchmark workload (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed as DIR/dst.npy (float32; a "
+                         "fixed seeded sample of a large output)")
     ap.add_argument("--spawn-probe", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, dump, print
+        args.no_verify = args.no_probe = args.no_secondary = args.no_cpu = True
+        args.alt_frames = 0
 
     if args.option:
         os.environ["IQO_HIP_TUNING"] = "1"  # the A/B option keys (include/iqo_hip.h iqo_hip_plan_set_option)
@@ -711,6 +761,13 @@ def main():
                      "scatter_ms": round(scatter_max * 1e3, 3), "gather_ms": round(t_g * 1e3, 3),
                      "scatter_path": sorted(be.paths.get("scatter", [])), "gather_path": sorted(be.paths.get("gather", []))}
 
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path holds after the last timed step
+        last_out = dst[(nstep[0] - 1) % rot] if args.shard == "image" else out
+        dumped = dump_outputs(args.dump_outputs, {"dst": last_out})
+        log("dumped outputs to %s: %s" % (args.dump_outputs, json.dumps(dumped)))
+
     parity = "unchecked"
     if rank == 0 and not args.no_verify:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -853,6 +910,8 @@ def main():
                                        "rank r on device r %% %d (gloo rehearsal)" % torch.cuda.device_count()}
         if band_info:
             res["band"] = band_info
+        if dumped:
+            res["dumped_outputs"] = dumped
         if alt:
             res["config"]["frames_per_gpu_alt"] = alt["frames"]
             res["batch_alt"] = alt

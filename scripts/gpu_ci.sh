@@ -6,7 +6,7 @@
 #   tests       pytest -m gpu, one process                      [PYTEST_K: -k expression]
 #   smoke       __graft_entry__.smoke()
 #   bench       short bench lines per config                    [CFGS, default "c2 c3 c4"; BENCH_EXTRA]
-#   fullbench   the driver's default `python bench.py`
+#   fullbench   `python bench.py --full` (every leg of the benchmark, CPU baseline included)
 #   benchlines  one 30-step bench line per config into gpurun_out/bench_lines.jsonl [CFGS, default all]
 #   prof        rocprofv3 --kernel-trace --stats per config     [PROF_CFGS]
 #   pmc         FETCH_SIZE / WRITE_SIZE passes per config        [PMC_CFGS]
@@ -41,18 +41,18 @@ smoke)
   ;;
 bench)
   for c in ${CFGS:-c2 c3 c4}; do
-    timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu ${BENCH_EXTRA} > "$OUT/bench_$c.log" 2>&1 || { echo "bench $c failed"; tail -20 "$OUT/bench_$c.log"; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu ${BENCH_EXTRA} > "$OUT/bench_$c.log" 2>&1 || { echo "bench $c failed"; tail -20 "$OUT/bench_$c.log"; exit 1; }
     tail -1 "$OUT/bench_$c.log"
   done
   ;;
 fullbench)
-  timeout -k 10 400 python bench.py > "$OUT/bench_full.log" 2>&1 || { echo "full bench failed"; tail -20 "$OUT/bench_full.log"; exit 1; }
+  timeout -k 10 400 python bench.py --full > "$OUT/bench_full.log" 2>&1 || { echo "full bench failed"; tail -20 "$OUT/bench_full.log"; exit 1; }
   tail -1 "$OUT/bench_full.log"
   ;;
 benchlines)
   : > "$OUT/bench_lines.jsonl"
   for c in ${CFGS:-$ALLCFGS}; do
-    timeout -k 10 300 python bench.py --config $c --steps 30 --warmup 3 --no-cpu --no-probe ${BENCH_EXTRA} > "$OUT/bl_$c.log" 2>&1 || { echo "bench $c failed"; tail -5 "$OUT/bl_$c.log"; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c --steps 30 --warmup 3 --no-cpu --no-probe ${BENCH_EXTRA} > "$OUT/bl_$c.log" 2>&1 || { echo "bench $c failed"; tail -5 "$OUT/bl_$c.log"; exit 1; }
     tail -1 "$OUT/bl_$c.log" >> "$OUT/bench_lines.jsonl"
   done
   python3 -c "
