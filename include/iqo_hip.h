@@ -63,8 +63,11 @@ enum {
     IQO_KERNEL_LINEAR_U23 = 10, /* exact 2:3 Linear upscale: clamped halo, no border code */
     IQO_KERNEL_LANCZOS_D31 = 11, /* exact 3:1 Lanczos-2/3 downscale: register window, symmetric taps, borders in-kernel */
     IQO_KERNEL_RYX = 12,         /* exact vertical ratio (9:4), tabled columns: register window + LDS work row */
-    IQO_KERNEL_RYG = 13          /* downscales by 1..2 (e.g. 1080 -> 768 rows), tabled rows and columns: shifting
+    IQO_KERNEL_RYG = 13,         /* downscales by 1..2 (e.g. 1080 -> 768 rows), tabled rows and columns: shifting
                                     register window + LDS work row */
+    IQO_KERNEL_PACKED_TILE = 14, /* packed pixels (2..4 channels), any layout: separable tiles, work rows de-interleaved
+                                    per channel, 4 pixels x all channels per thread */
+    IQO_KERNEL_PACKED_GENERAL = 15 /* packed pixels, any shape, any layout: IQO_KERNEL_GENERAL per channel (fallback) */
 };
 
 typedef struct iqo_hip_plan iqo_hip_plan;
@@ -92,6 +95,18 @@ int iqo_hip_plan_lanczos(unsigned degree, size_t srcW, size_t srcH, size_t dstW,
                          size_t pxScale, int device, iqo_hip_plan **out);
 int iqo_hip_plan_area(size_t srcW, size_t srcH, size_t dstW, size_t dstH, int device, iqo_hip_plan **out);
 int iqo_hip_plan_linear(size_t srcW, size_t srcH, size_t dstW, size_t dstH, int device, iqo_hip_plan **out);
+/* Interleaved U8 pixels, `channels` bytes per pixel (1..4; RGB, RGBA, the UV plane of NV12).  Every
+ * channel is resized independently; channel c of the output is byte-identical to the planar resize
+ * of channel c.  channels == 1 is exactly iqo_hip_plan_lanczos/area/linear.  Widths are in PIXELS,
+ * strides in BYTES (srcSt >= srcW*channels, dstSt >= dstW*channels), in every call that takes the
+ * plan: iqo_hip_resize_device, iqo_hip_resize, iqo_hip_resize_band, iqo_hip_band_src_rows,
+ * iqo_hip_plan_prepare / _query / _set_option / _destroy.  degree / pxScale: Lanczos only.
+ * IQO_HIP_EINVAL for channels outside 1..4.  Plans with channels > 1 run IQO_KERNEL_PACKED_TILE,
+ * or IQO_KERNEL_PACKED_GENERAL where the tile tables do not take the shape or "force_general" is
+ * set; no base or stride alignment is required. */
+int iqo_hip_plan_packed(int method, unsigned degree, int channels, size_t srcW, size_t srcH,
+                        size_t dstW, size_t dstH, size_t pxScale, int device, iqo_hip_plan **out);
+int iqo_hip_plan_channels(const iqo_hip_plan *plan);   /* 1 for every other constructor */
 void iqo_hip_plan_destroy(iqo_hip_plan *plan);
 
 int iqo_hip_plan_query(const iqo_hip_plan *plan, iqo_hip_plan_desc *desc);
@@ -163,6 +178,23 @@ int iqo_hip_resize_yuv420(iqo_hip_yuv_plan *plan, size_t srcStY, const uint8_t *
                           const uint8_t *srcU, const uint8_t *srcV, size_t dstStY, uint8_t *dstY, size_t dstStUV,
                           uint8_t *dstU, uint8_t *dstV);
 
+/* ---- NV12: a planar Y plane (srcW x srcH) and ONE interleaved UV plane (srcW/2 x srcH/2 pixels of
+ * 2 bytes), as the video decode blocks write it.  Y runs the planar plan with all its kernels at
+ * pxScale 1; UV runs a 2-channel packed plan at half size (Lanczos: pxScale 2, as the I420 chroma
+ * planes above), so U and V are byte-identical to the I420 planes' results.  Two launches on
+ * `stream`.  Strides in bytes (srcStUV >= 2 * (srcW/2)). */
+typedef struct iqo_hip_nv12_plan iqo_hip_nv12_plan;
+int iqo_hip_plan_nv12(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                      int device, iqo_hip_nv12_plan **out);
+void iqo_hip_nv12_plan_destroy(iqo_hip_nv12_plan *plan);
+/* Plane 0 = the luma plan, 1 = the packed UV plan (for iqo_hip_plan_set_option / _query). */
+iqo_hip_plan *iqo_hip_nv12_plane(iqo_hip_nv12_plan *plan, int plane);
+/* Device-resident batch, asynchronous on `stream`: frame f's planes start at srcY / srcUV +
+ * f*srcFrameSt (likewise dst). */
+int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                               size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, size_t dstStY,
+                               size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstUV, void *stream);
+
 /* ---- Multi-GPU data movement for row-band / image sharding.  The reference
  * splits a frame's output rows over OpenMP threads (src/IQOLanczosResizerImpl_AVX512.cpp:269-308);
  * across GPUs the same split needs each band's source window (halo rows) on its device and the
@@ -206,6 +238,11 @@ int iqo_host_band_src_rows(int method, unsigned degree, size_t srcW, size_t srcH
 /* Host-only: which kernel family a full-frame, 16-byte-aligned device call would use. */
 int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                         size_t pxScale);
+
+/* Host-only: the same for a packed plan of `channels` bytes per pixel (IQO_KERNEL_PACKED_TILE or
+ * IQO_KERNEL_PACKED_GENERAL; channels == 1: iqo_host_kernel_for).  < 0 for channels outside 1..4. */
+int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,
+                               size_t dstH, size_t pxScale);
 
 /* Drop-in classes (iqo::LanczosResizer, AreaResizer, LinearResizer): how many objects this process constructed on the
  * HIP backend, and on the CPU backend (no gfx950 device) plus the resize() calls of HIP objects that fell back to the

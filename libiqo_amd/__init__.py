@@ -12,15 +12,15 @@ call raises `IqoError`.
 import ctypes
 import os
 
-__all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420Resizer", "available", "lib",
-           "host_tables", "host_kernel_for", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
+__all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420Resizer", "Nv12Resizer", "available",
+           "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
            "ipc_close", "KERNELS", "COPY_PATHS", "LIB_PATH"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
 LIB_PATH = os.environ.get("LIBIQO_AMD_LIB") or os.path.join(PKG_DIR, "libiqo_hip.so")
 
-KERNELS = {0: "general", 1: "lanczos_stream", 2: "area_int", 3: "linear_up2", 4: "tile", 5: "walk", 6: "lanczos_up2", 7: "lanczos_d32", 8: "area_d32", 9: "lanczos_u23", 10: "linear_u23", 11: "lanczos_d31", 12: "ryx", 13: "ryg"}
+KERNELS = {0: "general", 1: "lanczos_stream", 2: "area_int", 3: "linear_up2", 4: "tile", 5: "walk", 6: "lanczos_up2", 7: "lanczos_d32", 8: "area_d32", 9: "lanczos_u23", 10: "linear_u23", 11: "lanczos_d31", 12: "ryx", 13: "ryg", 14: "packed_tile", 15: "packed_general"}
 _METHODS = {"lanczos": 0, "area": 1, "linear": 2}
 
 _c_sz = ctypes.c_size_t
@@ -61,6 +61,9 @@ def lib():
     L.iqo_hip_plan_lanczos.argtypes = [ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
     L.iqo_hip_plan_area.argtypes = [_c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
     L.iqo_hip_plan_linear.argtypes = [_c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
+    L.iqo_hip_plan_packed.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz,
+                                      ctypes.c_int, pp]
+    L.iqo_hip_plan_channels.argtypes = [_vp]
     L.iqo_hip_plan_destroy.argtypes = [_vp]
     L.iqo_hip_plan_destroy.restype = None
     L.iqo_hip_plan_query.argtypes = [_vp, ctypes.POINTER(PlanDesc)]
@@ -87,6 +90,14 @@ def lib():
     L.iqo_hip_resize_yuv420_device.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _vp, _c_sz, _c_sz, _c_sz,
                                                _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_resize_yuv420.argtypes = [_vp, _c_sz, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, _vp, _vp]
+    L.iqo_host_packed_kernel_for.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz]
+    L.iqo_hip_plan_nv12.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
+    L.iqo_hip_nv12_plan_destroy.argtypes = [_vp]
+    L.iqo_hip_nv12_plan_destroy.restype = None
+    L.iqo_hip_nv12_plane.argtypes = [_vp, ctypes.c_int]
+    L.iqo_hip_nv12_plane.restype = _vp
+    L.iqo_hip_resize_nv12_device.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _c_sz, _c_sz, _vp, _vp,
+                                             _vp]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -163,6 +174,14 @@ def host_kernel_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1):
     return KERNELS[lib().iqo_host_kernel_for(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale)]
 
 
+def host_packed_kernel_for(method, degree, channels, srcW, srcH, dstW, dstH, pxScale=1):
+    """Kernel family of a packed plan with `channels` bytes per pixel -- host only, no GPU."""
+    k = lib().iqo_host_packed_kernel_for(_METHODS[method], degree, channels, srcW, srcH, dstW, dstH, pxScale)
+    if k < 0:
+        raise IqoError("invalid packed plan request")
+    return KERNELS[k]
+
+
 def _ptr(obj):
     """Raw address of a numpy array, a torch tensor or an int."""
     if isinstance(obj, int):
@@ -185,11 +204,17 @@ def _stream_ptr(stream):
 class _Resizer:
     _method = None
 
-    def __init__(self, srcW, srcH, dstW, dstH, device=None):
+    def __init__(self, srcW, srcH, dstW, dstH, device=None, channels=1):
         self.srcW, self.srcH, self.dstW, self.dstH = int(srcW), int(srcH), int(dstW), int(dstH)
         self.device = 0 if device is None else int(device)
+        self.channels = int(channels)  # bytes per pixel, interleaved (widths stay in pixels, strides in bytes)
         self._plan = _vp()
-        self._make()
+        if self.channels == 1:
+            self._make()
+        else:
+            _check(lib().iqo_hip_plan_packed(self._method, getattr(self, "degree", 0), self.channels, self.srcW,
+                                             self.srcH, self.dstW, self.dstH, getattr(self, "pxScale", 1), self.device,
+                                             ctypes.byref(self._plan)), type(self).__name__)
 
     def _make(self):
         raise NotImplementedError
@@ -233,10 +258,14 @@ class _Resizer:
         _check(lib().iqo_hip_plan_query(self._plan, ctypes.byref(d)), "query")
         return {"method": d.method, "device": d.device, "tapsX": d.tapsX, "tapsY": d.tapsY,
                 "phasesX": d.phasesX, "phasesY": d.phasesY, "kernel": KERNELS.get(d.kernel, d.kernel),
-                "bands": d.bandsPerFrame, "tile_rows": d.tileRows}
+                "bands": d.bandsPerFrame, "tile_rows": d.tileRows,
+                "channels": int(lib().iqo_hip_plan_channels(self._plan))}
 
-    # -- torch convenience: src [F, srcH, srcW] (or [srcH, srcW]) uint8 on the plan's device
+    # -- torch convenience: src [F, srcH, srcW] (or [srcH, srcW]) uint8 on the plan's device;
+    #    packed plans: [F, srcH, srcW, C] (or [srcH, srcW, C])
     def resize_tensor(self, src, out=None, stream=None):
+        if self.channels > 1:
+            return self._resize_tensor_packed(src, out, stream)
         import torch
         squeeze = src.dim() == 2
         s = src.unsqueeze(0) if squeeze else src
@@ -256,12 +285,37 @@ class _Resizer:
         return out[0] if squeeze else out
 
 
-class LanczosResizer(_Resizer):
-    """iqo::LanczosResizer(degree, srcW, srcH, dstW, dstH, pxScale=1) -- LanczosResizer.hpp:26-33."""
+    def _resize_tensor_packed(self, src, out, stream):
+        import torch
+        C = self.channels
+        squeeze = src.dim() == 3
+        s = src.unsqueeze(0) if squeeze else src
+        if s.dtype != torch.uint8 or not s.is_cuda or s.dim() != 4 or tuple(s.shape[1:]) != (self.srcH, self.srcW, C):
+            raise IqoError("expected uint8 device tensor [F, %d, %d, %d]" % (self.srcH, self.srcW, C))
+        s = s.contiguous()
+        shape = (s.shape[0], self.dstH, self.dstW, C)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=s.device)
+        o = out.unsqueeze(0) if out.dim() == 3 else out
+        if (o.dtype != torch.uint8 or o.device != s.device or tuple(o.shape) != shape or o.stride(3) != 1
+                or o.stride(2) != C or o.stride(1) < self.dstW * C
+                or (o.shape[0] > 1 and o.stride(0) < self.dstH * o.stride(1))):
+            raise IqoError("out must be a uint8 tensor [%d, %d, %d, %d] on %s with interleaved channels and "
+                           "non-overlapping rows and frames" % (shape + (s.device,)))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        self.resize_device(s.shape[0], s.stride(1), s.stride(0), s, o.stride(1), o.stride(0), o, stream)
+        return out[0] if squeeze else out
 
-    def __init__(self, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None):
+
+class LanczosResizer(_Resizer):
+    """iqo::LanczosResizer(degree, srcW, srcH, dstW, dstH, pxScale=1) -- LanczosResizer.hpp:26-33.
+    channels > 1: interleaved pixels (iqo_hip_plan_packed)."""
+    _method = 0
+
+    def __init__(self, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None, channels=1):
         self.degree, self.pxScale = int(degree), int(pxScale)
-        super().__init__(srcW, srcH, dstW, dstH, device)
+        super().__init__(srcW, srcH, dstW, dstH, device, channels)
 
     def _make(self):
         _check(lib().iqo_hip_plan_lanczos(self.degree, self.srcW, self.srcH, self.dstW, self.dstH, self.pxScale,
@@ -270,6 +324,7 @@ class LanczosResizer(_Resizer):
 
 class AreaResizer(_Resizer):
     """iqo::AreaResizer(srcW, srcH, dstW, dstH) -- AreaResizer.hpp:24-29."""
+    _method = 1
 
     def _make(self):
         _check(lib().iqo_hip_plan_area(self.srcW, self.srcH, self.dstW, self.dstH, self.device,
@@ -278,19 +333,20 @@ class AreaResizer(_Resizer):
 
 class LinearResizer(_Resizer):
     """iqo::LinearResizer(srcW, srcH, dstW, dstH) -- LinearResizer.hpp:24-29."""
+    _method = 2
 
     def _make(self):
         _check(lib().iqo_hip_plan_linear(self.srcW, self.srcH, self.dstW, self.dstH, self.device,
                                          ctypes.byref(self._plan)), "LinearResizer")
 
 
-def make_resizer(method, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None):
+def make_resizer(method, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None, channels=1):
     if method == "lanczos":
-        return LanczosResizer(degree, srcW, srcH, dstW, dstH, pxScale, device)
+        return LanczosResizer(degree, srcW, srcH, dstW, dstH, pxScale, device, channels)
     if method == "area":
-        return AreaResizer(srcW, srcH, dstW, dstH, device)
+        return AreaResizer(srcW, srcH, dstW, dstH, device, channels)
     if method == "linear":
-        return LinearResizer(srcW, srcH, dstW, dstH, device)
+        return LinearResizer(srcW, srcH, dstW, dstH, device, channels)
     raise ValueError(method)
 
 
@@ -351,3 +407,65 @@ class Yuv420Resizer:
         fused = self.resize_device(n, sw, sw // 2, src.stride(0), b, b + sw * sh, b + sw * sh + cs,
                                    dw, dw // 2, out.stride(0), o, o + dw * dh, o + dw * dh + cd, stream)
         return out, fused
+
+
+class Nv12Resizer:
+    """NV12 resizer: a planar Y plane at full size and one interleaved UV plane at half size, with
+    the same method (Lanczos chroma: pxScale 2).  U and V come out as Yuv420Resizer's planes do."""
+
+    def __init__(self, method, degree, srcW, srcH, dstW, dstH, device=None):
+        self.method, self.degree = method, int(degree)
+        self.srcW, self.srcH, self.dstW, self.dstH = int(srcW), int(srcH), int(dstW), int(dstH)
+        self.device = 0 if device is None else int(device)
+        self._plan = _vp()
+        _check(lib().iqo_hip_plan_nv12(_METHODS[method], self.degree, self.srcW, self.srcH, self.dstW, self.dstH,
+                                       self.device, ctypes.byref(self._plan)), "Nv12Resizer")
+
+    def __del__(self):
+        p = getattr(self, "_plan", None)
+        if p and _lib is not None:
+            _lib.iqo_hip_nv12_plan_destroy(p)
+            self._plan = _vp()
+
+    def set_option(self, key, value, plane=None):
+        for pl in ((0, 1) if plane is None else (plane,)):
+            _check(lib().iqo_hip_plan_set_option(lib().iqo_hip_nv12_plane(self._plan, pl), key.encode(), int(value)),
+                   "set_option")
+
+    def describe(self):
+        """Kernel names of the (Y, UV) plans."""
+        out = []
+        for pl in (0, 1):
+            d = PlanDesc()
+            _check(lib().iqo_hip_plan_query(lib().iqo_hip_nv12_plane(self._plan, pl), ctypes.byref(d)), "query")
+            out.append(KERNELS.get(d.kernel, d.kernel))
+        return tuple(out)
+
+    def resize_device(self, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcUV, dstStY, dstStUV, dstFrameSt, dstY,
+                      dstUV, stream=None):
+        """Device-resident batch (async on `stream`); strides in bytes."""
+        _check(lib().iqo_hip_resize_nv12_device(self._plan, nFrames, srcStY, srcStUV, srcFrameSt, _ptr(srcY),
+                                                _ptr(srcUV), dstStY, dstStUV, dstFrameSt, _ptr(dstY), _ptr(dstUV),
+                                                _stream_ptr(stream)), "resize_nv12_device")
+
+    def resize_frames(self, src, out=None, stream=None):
+        """src: uint8 CUDA tensor [frames, srcH*srcW + 2*(srcW/2)*(srcH/2)], each frame laid out NV12 (Y, then
+        the interleaved UV plane, tightly packed); returns / fills out in the same layout at the output size."""
+        import torch
+        sw, sh, dw, dh = self.srcW, self.srcH, self.dstW, self.dstH
+        cs, cd = 2 * (sw // 2) * (sh // 2), 2 * (dw // 2) * (dh // 2)
+        if (src.dtype != torch.uint8 or not src.is_cuda or src.dim() != 2 or src.shape[1] != sw * sh + cs
+                or not src.is_contiguous()):
+            raise IqoError("src must be a contiguous uint8 device tensor [frames, %d]" % (sw * sh + cs))
+        n = src.shape[0]
+        if out is None:
+            out = torch.empty((n, dw * dh + cd), dtype=torch.uint8, device=src.device)
+        if (out.dtype != torch.uint8 or out.device != src.device or tuple(out.shape) != (n, dw * dh + cd)
+                or not out.is_contiguous()):
+            raise IqoError("out must be a contiguous uint8 tensor [%d, %d] on %s" % (n, dw * dh + cd, src.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(src.device)
+        b, o = src.data_ptr(), out.data_ptr()
+        self.resize_device(n, sw, 2 * (sw // 2), src.stride(0), b, b + sw * sh, dw, 2 * (dw // 2), out.stride(0),
+                           o, o + dw * dh, stream)
+        return out

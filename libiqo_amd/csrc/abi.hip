@@ -33,6 +33,11 @@ struct iqo_hip_plan {
     int keyMethod = 0;
     unsigned keyDegree = 0;
     size_t keyDims[5] = {0, 0, 0, 0, 0};
+    // bytes per pixel: 1 = planar (every kernel family), 2 .. 4 = packed interleaved channels
+    // (iqo_hip_plan_packed: packed_tile_kernel / packed_general_kernel only).  Part of the cache key.
+    int channels = 1;
+    iqo_amd::PackedTables pk;
+    int4 *dPSpans = nullptr;
     // Device tables (general / tile / walker / ratio-Y kernels) are staged into one host blob at
     // plan creation and uploaded by ONE allocation and copy the first time a launch needs them:
     // the specialised kernels take their coefficients as kernel arguments, so a plan that only
@@ -652,6 +657,21 @@ int upload_tile(iqo_hip_plan *h)
     return IQO_HIP_OK;
 }
 
+// Packed plans: the packed tiling over the tile tables upload_tile staged (its column coefficients
+// are laid out over the planar tiles' padded width, which covers the narrower packed tiles').
+int upload_packed(iqo_hip_plan *h)
+{
+    if (h->channels == 1)
+        return IQO_HIP_OK;
+    iqo_amd::build_packed_tables(h->p, h->tt, h->channels, &h->pk);
+    if (!h->pk.ok)
+        return IQO_HIP_OK;
+    std::vector<int4> spans(h->pk.spans.size());
+    for (size_t i = 0; i < spans.size(); ++i)
+        spans[i] = make_int4(h->pk.spans[i].lo8, h->pk.spans[i].groups, h->pk.spans[i].border, 0);
+    return upload(h, &h->dPSpans, spans.data(), spans.size());
+}
+
 // Every option iqo_hip_plan_set_option can change, back to its default.
 void reset_options(iqo_hip_plan *h)
 {
@@ -690,12 +710,12 @@ constexpr size_t kPlanCache = 16;
 std::mutex g_planCacheMu;
 std::vector<iqo_hip_plan *> g_planCache;
 
-iqo_hip_plan *plan_cache_take(int m, unsigned degree, const size_t (&dims)[5], int device)
+iqo_hip_plan *plan_cache_take(int m, unsigned degree, int channels, const size_t (&dims)[5], int device)
 {
     std::lock_guard<std::mutex> g(g_planCacheMu);
     for (size_t i = g_planCache.size(); i-- > 0;) {
         iqo_hip_plan *h = g_planCache[i];
-        if (h->keyMethod == m && h->keyDegree == degree && h->device == device &&
+        if (h->keyMethod == m && h->keyDegree == degree && h->channels == channels && h->device == device &&
             std::equal(dims, dims + 5, h->keyDims)) {
             g_planCache.erase(g_planCache.begin() + static_cast<std::ptrdiff_t>(i));
             return h;
@@ -723,13 +743,15 @@ void plan_cache_put(iqo_hip_plan *h)
 }
 
 int make_plan(iqo_amd::Method m, unsigned degree, size_t sw, size_t sh, size_t dw, size_t dh, size_t px,
-              int device, iqo_hip_plan **out)
+              int device, iqo_hip_plan **out, int channels = 1)
 {
     if (!out)
         return IQO_HIP_EINVAL;
     *out = nullptr;
+    if (channels < 1 || channels > 4)
+        return IQO_HIP_EINVAL;
     const size_t dims[5] = {sw, sh, dw, dh, px};
-    if (iqo_hip_plan *c = plan_cache_take(static_cast<int>(m), degree, dims, device)) {
+    if (iqo_hip_plan *c = plan_cache_take(static_cast<int>(m), degree, channels, dims, device)) {
         *out = c;
         return IQO_HIP_OK;
     }
@@ -749,6 +771,7 @@ int make_plan(iqo_amd::Method m, unsigned degree, size_t sw, size_t sh, size_t d
     h->device = device;
     h->keyMethod = static_cast<int>(m);
     h->keyDegree = degree;
+    h->channels = channels;
     std::copy(dims, dims + 5, h->keyDims);
     DeviceGuard guard(device);
     if (!guard.ok()) {
@@ -769,7 +792,8 @@ int make_plan(iqo_amd::Method m, unsigned degree, size_t sw, size_t sh, size_t d
     if ((rc = upload(h, &h->dX, xr.data(), xr.size())) || (rc = upload(h, &h->dY, yr.data(), yr.size())) ||
         (rc = upload(h, &h->dTabX, h->p.x.table.data(), h->p.x.table.size())) ||
         (rc = upload(h, &h->dTabY, h->p.y.table.data(), h->p.y.table.size())) ||
-        (rc = upload(h, &h->dChunks, chunks.data(), chunks.size())) || (rc = upload_tile(h))) {
+        (rc = upload(h, &h->dChunks, chunks.data(), chunks.size())) || (rc = upload_tile(h)) ||
+        (rc = upload_packed(h))) {
         free_plan(h);
         return rc;
     }
@@ -905,6 +929,21 @@ iqo_amd::TileDev tile_dev(const iqo_hip_plan *h)
     d.colA = h->dTColA;
     d.nQp = h->tileNQp;
     d.spans = h->dTSpans;
+    return d;
+}
+
+// packed_tile_kernel: the tile tables with the packed tiling (plan.hpp PackedTables)
+iqo_amd::TileDev packed_tile_dev(const iqo_hip_plan *h)
+{
+    iqo_amd::TileDev d = tile_dev(h);
+    const iqo_amd::PackedTables &k = h->pk;
+    d.CT = k.CT;
+    d.TH = k.TH;
+    d.pitchDw = k.pitchDw;
+    d.log2nQ = k.log2nQ;
+    d.srcRows = k.srcRows;
+    d.spitch = k.spitch;
+    d.spans = h->dPSpans;
     return d;
 }
 
@@ -1320,6 +1359,8 @@ bool walk_beats_ryg(const iqo_hip_plan *h)
 // The kernel family a full-frame call with aligned pointers and strides runs.
 int plan_kernel(const iqo_hip_plan *h)
 {
+    if (h->channels > 1)  // packed plans: none of the planar kernels
+        return h->pk.ok && !h->forceGeneral ? IQO_KERNEL_PACKED_TILE : IQO_KERNEL_PACKED_GENERAL;
     int k = h->forceGeneral ? IQO_KERNEL_GENERAL : h->p.kernel;
     if (k == IQO_KERNEL_GENERAL && !h->forceGeneral && h->tt.ok && h->useTile)
         k = IQO_KERNEL_TILE;
@@ -1352,6 +1393,8 @@ int plan_kernel(const iqo_hip_plan *h)
 int kernel_for_layout(const iqo_hip_plan *h, const void *src, size_t srcSt, size_t srcFrameSt, const void *dst,
                       size_t dstSt, size_t dstFrameSt)
 {
+    if (h->channels > 1)  // packed plans: both kernels take any alignment
+        return plan_kernel(h);
     const Plan &p = h->p;
     int kernel = h->forceGeneral ? IQO_KERNEL_GENERAL : p.kernel;
     if (kernel == IQO_KERNEL_LANCZOS_STREAM && !(aligned(src, 16, srcSt, srcFrameSt) && aligned(dst, 16 / p.flz.KX, dstSt, dstFrameSt)))
@@ -1424,7 +1467,8 @@ int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t src
              size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstFrameSt, uint8_t *dst, hipStream_t s)
 {
     const Plan &p = h->p;
-    if (!src || !dst || srcSt < static_cast<size_t>(p.srcW) || dstSt < static_cast<size_t>(p.dstW))
+    const size_t C = static_cast<size_t>(h->channels);
+    if (!src || !dst || srcSt < static_cast<size_t>(p.srcW) * C || dstSt < static_cast<size_t>(p.dstW) * C)
         return IQO_HIP_EINVAL;
     const size_t dstH = static_cast<size_t>(p.dstH);
     if (r0 > dstH || rows > dstH - r0 || srcRow0 >= static_cast<size_t>(p.srcH))
@@ -1443,7 +1487,8 @@ int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t src
 
     const int kernel = kernel_for_layout(h, src, srcSt, srcFrameSt, dst, dstSt, dstFrameSt);
     if (kernel == IQO_KERNEL_TILE || kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_RYX ||
-        kernel == IQO_KERNEL_RYG || kernel == IQO_KERNEL_GENERAL) {
+        kernel == IQO_KERNEL_RYG || kernel == IQO_KERNEL_GENERAL || kernel == IQO_KERNEL_PACKED_TILE ||
+        kernel == IQO_KERNEL_PACKED_GENERAL) {
         const int rc = ensure_tables(h);
         if (rc)
             return rc;
@@ -1505,6 +1550,10 @@ int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t src
             e = iqo_amd::launch_u23(u23_dev(h), io, rb, re, h->bands, s);
         else if (kernel == IQO_KERNEL_LINEAR_U23)
             e = iqo_amd::launch_l23(l23_dev(h), io, rb, re, h->bands, s);
+        else if (kernel == IQO_KERNEL_PACKED_TILE)
+            e = iqo_amd::launch_packed_tile(packed_tile_dev(h), h->channels, io, rb, re, s);
+        else if (kernel == IQO_KERNEL_PACKED_GENERAL)
+            e = iqo_amd::launch_packed_general(general_dev(h), h->channels, io, rb, re, s);
         else
             e = iqo_amd::launch_general(general_dev(h), io, rb, re, s);
         // the launchers reject a parameter set they have no instantiation for before launching
@@ -1551,6 +1600,21 @@ int iqo_hip_plan_linear(size_t srcW, size_t srcH, size_t dstW, size_t dstH, int 
     return make_plan(iqo_amd::kLinear, 0, srcW, srcH, dstW, dstH, 1, device, out);
 }
 
+int iqo_hip_plan_packed(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                        size_t pxScale, int device, iqo_hip_plan **out)
+{
+    if (method < IQO_METHOD_LANCZOS || method > IQO_METHOD_LINEAR || channels < 1 || channels > 4) {
+        if (out)
+            *out = nullptr;
+        return IQO_HIP_EINVAL;
+    }
+    const bool lz = method == IQO_METHOD_LANCZOS;  // degree / pxScale: Lanczos only (as the planar constructors)
+    return make_plan(static_cast<iqo_amd::Method>(method), lz ? degree : 0, srcW, srcH, dstW, dstH, lz ? pxScale : 1,
+                     device, out, channels);
+}
+
+int iqo_hip_plan_channels(const iqo_hip_plan *plan) { return plan ? plan->channels : IQO_HIP_EINVAL; }
+
 void iqo_hip_plan_destroy(iqo_hip_plan *plan)
 {
     if (!plan)
@@ -1574,7 +1638,7 @@ int iqo_hip_plan_query(const iqo_hip_plan *h, iqo_hip_plan_desc *d)
     d->phasesY = h->p.y.phases;
     d->kernel = plan_kernel(h);
     d->bandsPerFrame = h->bands;
-    d->tileRows = h->tt.ok ? h->tt.TH : 0;
+    d->tileRows = h->channels > 1 ? (h->pk.ok ? h->pk.TH : 0) : h->tt.ok ? h->tt.TH : 0;
     return IQO_HIP_OK;
 }
 
@@ -1850,7 +1914,8 @@ int host_pipeline(HostStage *st, HostPlane *planes, int nPlanes)
     for (int c = 0; c < nc; ++c) {
         HostPlane &P = planes[ch[c].plane];
         const Plan &p = P.h->p;
-        const size_t W = static_cast<size_t>(p.srcW), w = static_cast<size_t>(p.dstW);
+        const size_t C = static_cast<size_t>(P.h->channels);  // rows of width * channels bytes
+        const size_t W = static_cast<size_t>(p.srcW) * C, w = static_cast<size_t>(p.dstW) * C;
         int s0, s1;
         iqo_amd::band_src_rows(p, ch[c].r0, ch[c].r1, &s0, &s1);
         const bool lastOfPlane = c == nc - 1 || ch[c + 1].plane != ch[c].plane;
@@ -1902,7 +1967,8 @@ int host_pipeline(HostStage *st, HostPlane *planes, int nPlanes)
         if (!P.pinDst)
             copy_rows_par(P.dst + static_cast<size_t>(ch[c].r0) * P.dstSt, P.dstSt,
                           st->hDst + P.dOff + static_cast<size_t>(ch[c].r0) * P.dPitch, P.dPitch,
-                          static_cast<size_t>(P.h->p.dstW), static_cast<size_t>(ch[c].r1 - ch[c].r0));
+                          static_cast<size_t>(P.h->p.dstW) * static_cast<size_t>(P.h->channels),
+                          static_cast<size_t>(ch[c].r1 - ch[c].r0));
     }
     return IQO_HIP_OK;
 }
@@ -1920,7 +1986,7 @@ int host_direct(HostStage *st, HostPlane *planes, int nPlanes)
     for (int q = 0; q < nPlanes; ++q) {
         const HostPlane &P = planes[q];
         const Plan &p = P.h->p;
-        const size_t W = static_cast<size_t>(p.srcW), H = static_cast<size_t>(p.srcH);
+        const size_t W = static_cast<size_t>(p.srcW) * static_cast<size_t>(P.h->channels), H = static_cast<size_t>(p.srcH);
         const hipError_t e = (P.srcSt == W && P.sPitch == W)
                                  ? hipMemcpyAsync(st->dSrc + P.sOff, P.src, W * H, hipMemcpyHostToDevice, st->sK)
                                  : hipMemcpy2DAsync(st->dSrc + P.sOff, P.sPitch, P.src, P.srcSt, W, H,
@@ -1940,7 +2006,7 @@ int host_direct(HostStage *st, HostPlane *planes, int nPlanes)
     for (int q = 0; q < nPlanes; ++q) {
         const HostPlane &P = planes[q];
         const Plan &p = P.h->p;
-        const size_t w = static_cast<size_t>(p.dstW), hh = static_cast<size_t>(p.dstH);
+        const size_t w = static_cast<size_t>(p.dstW) * static_cast<size_t>(P.h->channels), hh = static_cast<size_t>(p.dstH);
         const hipError_t e = (P.dstSt == w && P.dPitch == w)
                                  ? hipMemcpyAsync(P.dst, st->dDst + P.dOff, w * hh, hipMemcpyDeviceToHost, st->sK)
                                  : hipMemcpy2DAsync(P.dst, P.dstSt, st->dDst + P.dOff, P.dPitch, w, hh,
@@ -1954,7 +2020,8 @@ int host_direct(HostStage *st, HostPlane *planes, int nPlanes)
 static int host_resize(iqo_hip_plan *h, HostStage *st, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst)
 {
     const Plan &p = h->p;
-    const size_t W = static_cast<size_t>(p.srcW), w = static_cast<size_t>(p.dstW);
+    const size_t C = static_cast<size_t>(h->channels);  // staged rows: width * channels bytes
+    const size_t W = static_cast<size_t>(p.srcW) * C, w = static_cast<size_t>(p.dstW) * C;
     const size_t sPitch = (W + 15) & ~size_t(15);
     const size_t dPitch = (w + 15) & ~size_t(15);
     const size_t sBytes = sPitch * p.srcH, dBytes = dPitch * p.dstH;
@@ -2007,7 +2074,8 @@ int iqo_hip_resize(iqo_hip_plan *h, size_t srcSt, const uint8_t *src, size_t dst
     if (!h || !src || !dst)
         return IQO_HIP_EINVAL;
     const Plan &p = h->p;
-    if (srcSt < static_cast<size_t>(p.srcW) || dstSt < static_cast<size_t>(p.dstW))
+    const size_t C = static_cast<size_t>(h->channels);
+    if (srcSt < static_cast<size_t>(p.srcW) * C || dstSt < static_cast<size_t>(p.dstW) * C)
         return IQO_HIP_EINVAL;
     DeviceGuard guard(h->device);
     if (!guard.ok())
@@ -2143,6 +2211,67 @@ int iqo_hip_resize_yuv420_device(iqo_hip_yuv_plan *yp, size_t nFrames, size_t sr
     if (!rc)
         rc = run_band(hc, nFrames, 0, static_cast<size_t>(pc.dstH), 0, srcStUV, srcFrameSt, srcV, dstStUV, dstFrameSt,
                       dstV, s);
+    return rc;
+}
+
+// ---- NV12: a planar Y plane and one interleaved UV plane at half size.  Y keeps the planar plan and
+// all its kernels; UV is a 2-channel packed plan (Lanczos chroma: pxScale 2, as iqo_hip_plan_yuv420).
+
+struct iqo_hip_nv12_plan {
+    iqo_hip_plan *y = nullptr, *uv = nullptr;
+};
+
+int iqo_hip_plan_nv12(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, int device,
+                      iqo_hip_nv12_plan **out)
+{
+    if (!out)
+        return IQO_HIP_EINVAL;
+    *out = nullptr;
+    if (srcW < 2 || srcH < 2 || dstW < 2 || dstH < 2)
+        return IQO_HIP_EINVAL;
+    iqo_hip_nv12_plan *np = new (std::nothrow) iqo_hip_nv12_plan();
+    if (!np)
+        return IQO_HIP_ENOMEM;
+    int rc = iqo_hip_plan_packed(method, degree, 1, srcW, srcH, dstW, dstH, 1, device, &np->y);
+    if (!rc)
+        rc = iqo_hip_plan_packed(method, degree, 2, srcW / 2, srcH / 2, dstW / 2, dstH / 2, 2, device, &np->uv);
+    if (rc) {
+        iqo_hip_nv12_plan_destroy(np);
+        return rc;
+    }
+    *out = np;
+    return IQO_HIP_OK;
+}
+
+void iqo_hip_nv12_plan_destroy(iqo_hip_nv12_plan *np)
+{
+    if (!np)
+        return;
+    iqo_hip_plan_destroy(np->y);
+    iqo_hip_plan_destroy(np->uv);
+    delete np;
+}
+
+iqo_hip_plan *iqo_hip_nv12_plane(iqo_hip_nv12_plan *np, int plane)
+{
+    if (!np)
+        return nullptr;
+    return plane == 0 ? np->y : plane == 1 ? np->uv : nullptr;
+}
+
+int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *np, size_t nFrames, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                               const uint8_t *srcY, const uint8_t *srcUV, size_t dstStY, size_t dstStUV,
+                               size_t dstFrameSt, uint8_t *dstY, uint8_t *dstUV, void *stream)
+{
+    if (!np || !np->y || !np->uv)
+        return IQO_HIP_EINVAL;
+    // two launches on the same stream (run_band checks pointers and strides per plane)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = run_band(np->y, nFrames, 0, static_cast<size_t>(np->y->p.dstH), 0, srcStY, srcFrameSt, srcY, dstStY,
+                      dstFrameSt, dstY, s);
+    if (!rc)
+        rc = run_band(np->uv, nFrames, 0, static_cast<size_t>(np->uv->p.dstH), 0, srcStUV, srcFrameSt, srcUV, dstStUV,
+                      dstFrameSt, dstUV, s);
     return rc;
 }
 
@@ -2490,6 +2619,23 @@ int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, s
     iqo_amd::build_a32(h.p, &h.at);
     iqo_amd::build_u23(h.p, &h.vt);
     iqo_amd::build_l23(h.p, &h.lt);
+    return plan_kernel(&h);
+}
+
+int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,
+                               size_t dstH, size_t pxScale)
+{
+    if (method < 0 || method > 2 || channels < 1 || channels > 4)
+        return IQO_HIP_EINVAL;
+    if (channels == 1)
+        return iqo_host_kernel_for(method, degree, srcW, srcH, dstW, dstH, pxScale);
+    iqo_hip_plan h;  // host half of a plan only: no device memory
+    std::string err;
+    if (!iqo_amd::build_plan(static_cast<iqo_amd::Method>(method), degree, srcW, srcH, dstW, dstH, pxScale, &h.p, &err))
+        return IQO_HIP_EINVAL;
+    h.channels = channels;
+    iqo_amd::build_tile_tables(h.p, &h.tt);
+    iqo_amd::build_packed_tables(h.p, h.tt, channels, &h.pk);
     return plan_kernel(&h);
 }
 

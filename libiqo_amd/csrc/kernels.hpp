@@ -46,6 +46,18 @@ struct TileDev {
 };
 hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s);
 
+
+// --- packed (interleaved) pixels, C = 2 .. 4 bytes per pixel, every channel resized on its own
+// (kernels_packed.hip).  Widths in GeneralDev / TileDev stay in PIXELS; Io strides are bytes.
+// packed_general_kernel: general_kernel per channel.
+hipError_t launch_packed_general(const GeneralDev &g, int channels, const Io &io, int rowBegin, int rowEnd,
+                                 hipStream_t s);
+// packed_tile_kernel: the planar tile tables (rows, rowTap, cols, colCoef, colA, nQp) with the
+// packed tiling of plan.hpp PackedTables in CT, TH, pitchDw (one channel segment), log2nQ, srcRows,
+// spitch and spans ({lo8 pixel, 8-pixel groups, any border column, 0} per column tile).
+hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd,
+                              hipStream_t s);
+
 // --- general-ratio wave walker: every wave walks a 256-column strip of one band of rows through
 // a private LDS ring of source rows widened to u16 (plan.hpp WalkTables; 4-byte aligned sources).
 struct WalkDev {

@@ -285,7 +285,7 @@ __device__ __forceinline__ uint32_t pack23_hi(uint32_t w, uint32_t a, uint32_t b
 
 // Waves of `kernel` (256-thread blocks) resident on the whole current device: occupancy x CUs.
 // Host-side query, cached per kernel.
-int resident_waves(const void *kernel, int block = 256, int ldsBytes = 0)
+[[maybe_unused]] int resident_waves(const void *kernel, int block = 256, int ldsBytes = 0)
 {
     static std::mutex mu;
     static std::unordered_map<const void *, int> cache;

@@ -899,6 +899,51 @@ bool tile_set_rows(const Plan &p, TileTables *t, int TH)
     return true;
 }
 
+size_t packed_lds_bytes(const Plan &p, const TileTables &t, const PackedTables &k, int TH)
+{
+    return static_cast<size_t>(TH) * (static_cast<size_t>(k.C) * k.pitchDw * 4 + 16 + t.nYp * 8) + 4u * k.CT +
+           static_cast<size_t>(tile_src_rows(p, t, TH)) * k.spitch;
+}
+
+void build_packed_tables(const Plan &p, const TileTables &t, int channels, PackedTables *k)
+{
+    *k = PackedTables();
+    if (!t.ok || channels < 2 || channels > 4)
+        return;
+    k->C = channels;
+    // the planar tile width divided by the channel count (3 rounds up to 4: CT / 4 is a power of 2)
+    k->CT = std::max(64, t.CT / (channels == 2 ? 2 : 4));
+    int l2 = 0;
+    while ((4 << l2) < k->CT)
+        ++l2;
+    k->log2nQ = l2;
+    const int nT = (p.dstW + k->CT - 1) / k->CT;
+    k->spans.resize(static_cast<size_t>(nT));
+    int maxG = 1;
+    for (int i = 0; i < nT; ++i) {
+        int lo = 1 << 30, hi = -(1 << 30), border = 0;
+        for (int x = i * k->CT; x < std::min(p.dstW, (i + 1) * k->CT); ++x) {
+            lo = std::min(lo, t.cols[static_cast<size_t>(x)].a);
+            hi = std::max(hi, t.cols[static_cast<size_t>(x)].a + 2 * t.NP);
+            border |= t.cols[static_cast<size_t>(x)].D != 0;
+        }
+        const int lo8 = lo & ~7;
+        const int g = (hi - lo8 + 7) / 8;
+        k->spans[static_cast<size_t>(i)] = PackedSpan{lo8, g, border};
+        maxG = std::max(maxG, g);
+    }
+    k->pitchDw = 4 * maxG;
+    k->spitch = 8 * channels * maxG;
+    int TH = 16;
+    while (TH > 2 && packed_lds_bytes(p, t, *k, TH) > 48 * 1024)
+        TH /= 2;
+    if (packed_lds_bytes(p, t, *k, TH) > 64 * 1024)
+        return;
+    k->TH = TH;
+    k->srcRows = tile_src_rows(p, t, TH);
+    k->ok = true;
+}
+
 void band_src_rows(const Plan &p, int r0, int r1, int *s0, int *s1)
 {
     int lo = p.srcH, hi = 0;

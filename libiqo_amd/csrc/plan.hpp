@@ -151,6 +151,29 @@ size_t tile_lds_bytes(const Plan &p, const TileTables &t, int TH);
 int tile_src_rows(const Plan &p, const TileTables &t, int TH);
 bool tile_set_rows(const Plan &p, TileTables *t, int TH);
 
+// Tile geometry of the packed (interleaved, C bytes per pixel) tile kernel (kernels_packed.hip
+// packed_tile_kernel).  The rows, row taps, columns and column coefficients are the planar tile
+// tables' (they do not depend on C); only the tiling differs: a tile is CT output PIXELS wide
+// (narrower than the planar tile by about C, so the C-fold staged source and work rows stay within
+// the LDS), its span counts groups of 8 source pixels, the staged source row holds 8 * C * groups
+// bytes and the work row one segment of pitchDw dwords per channel.
+struct PackedSpan {
+    int32_t lo8, groups, border;  // first work pixel (multiple of 8), 8-pixel groups, any Lanczos border column
+};
+struct PackedTables {
+    bool ok = false;
+    int C = 1;                    // bytes per pixel (2 .. 4)
+    int CT = 64;                  // output pixels per tile (a power of 2, >= 64)
+    int TH = 16;                  // output rows per tile
+    int log2nQ = 4;               // log2(CT / 4)
+    int pitchDw = 0;              // work-row pitch of ONE channel segment (dwords) = 4 * max groups
+    int spitch = 0;               // staged source row pitch (bytes) = 8 * C * max groups
+    int srcRows = 0;              // source rows staged per tile
+    std::vector<PackedSpan> spans;// ceil(dstW / CT)
+};
+void build_packed_tables(const Plan &p, const TileTables &t, int channels, PackedTables *k);
+size_t packed_lds_bytes(const Plan &p, const TileTables &t, const PackedTables &k, int TH);
+
 // Geometry of the general-ratio band walker (kernels.hip walk_kernel) over the tile tables:
 // column tiles of CTW output columns (at most 1024: one quad of 4 columns per thread), each with
 // its work-column span in 4-column units, and an LDS ring of R source rows.
