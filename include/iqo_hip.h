@@ -90,7 +90,14 @@ int iqo_hip_available(void);
  * memory are uploaded to `device` once, on the first launch that needs them.  Destroyed plans are
  * kept in a small process-wide cache (options reset to their defaults) and returned again for an
  * identical request, so constructing a resizer per call, as the reference benchmark does, does not
- * rebuild tables. */
+ * rebuild tables.
+ *
+ * Shapes without a pinned answer.  Linear upscales above 2x read outside the reference's rows:
+ * plans are built, the output is unpinned.  Lanczos shapes whose top border band exceeds the
+ * output, ceil((tapsY / 2 - 1) * dstH / srcH) > dstH (the vertical window is taller than the source,
+ * e.g. degree 8, 115x18 -> 16x6), make the reference write rows past dstH: every plan constructor
+ * below (lanczos, packed, yuv420, nv12) and every iqo_host_* query returns IQO_HIP_EINVAL for them.
+ * The same bound on the X axis only classifies columns and is accepted. */
 int iqo_hip_plan_lanczos(unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                          size_t pxScale, int device, iqo_hip_plan **out);
 int iqo_hip_plan_area(size_t srcW, size_t srcH, size_t dstW, size_t dstH, int device, iqo_hip_plan **out);

@@ -171,7 +171,10 @@ def host_band_src_rows(method, degree, srcW, srcH, dstW, dstH, pxScale, dstRow0,
 
 
 def host_kernel_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1):
-    return KERNELS[lib().iqo_host_kernel_for(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale)]
+    k = lib().iqo_host_kernel_for(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale)
+    if k < 0:
+        raise IqoError("invalid plan request")
+    return KERNELS[k]
 
 
 def host_packed_kernel_for(method, degree, channels, srcW, srcH, dstW, dstH, pxScale=1):

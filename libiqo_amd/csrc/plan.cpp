@@ -242,7 +242,10 @@ int clampi(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Lanczos Y map: simulate the three row loops with their SHARED iterator and table cursor
 // (:390-453); a later loop overwrites rows an earlier one wrote when mainEnd < mainBegin.
-void coords_lanczos_y(AxisPlan *a)
+// Returns false when the first loop alone runs past the image (mainBegin > dstLen: the window is
+// taller than the source by more than the output has rows).  The reference writes rows >= dstH
+// there, so the shape has no defined result and build_plan rejects it.
+bool coords_lanczos_y(AxisPlan *a)
 {
     const int64_t s = a->srcLen, d = a->dstLen, m = a->taps / 2;
     a->coord.assign(static_cast<size_t>(d), CoordInfo{0, 0, kMain, 0});
@@ -250,10 +253,12 @@ void coords_lanczos_y(AxisPlan *a)
         a->identity = true;
         for (int64_t y = 0; y < d; ++y)
             a->coord[y] = CoordInfo{static_cast<int32_t>(y), 0, kIdentity, 0};
-        return;
+        return true;
     }
     int64_t mb = ((m - 1) * d + s - 1) / s;
     int64_t me = std::max<int64_t>(0, (s - m) * d / s);
+    if (mb > d)
+        return false;
     a->mainBegin = static_cast<int>(mb);
     a->mainEnd = static_cast<int>(me);
     RationalStep it(d, s);
@@ -281,9 +286,13 @@ void coords_lanczos_y(AxisPlan *a)
         emit(y, kMain);
     for (int64_t y = me; y < d; ++y)
         emit(y, kBorderHi);
+    return true;
 }
 
 // Lanczos X map (resizeX / resizeXborder / resizeXmain, :518-612): each column is independent.
+// mainBegin may exceed dstLen here too, but only as a classification bound: the one loop below
+// runs x < dstLen and every column's origin and phase come from x alone, as in the reference's
+// resizeX, so no X shape is rejected.
 void coords_lanczos_x(AxisPlan *a)
 {
     const int64_t s = a->srcLen, d = a->dstLen, m = a->taps / 2;
@@ -715,7 +724,11 @@ bool build_plan(Method m, unsigned degree, size_t srcW, size_t srcH, size_t dstW
     switch (m) {
     case kLanczos:
         coords_lanczos_x(&p->x);
-        coords_lanczos_y(&p->y);
+        if (!coords_lanczos_y(&p->y)) {
+            if (err)
+                *err = "lanczos window taller than the source: the top border rows exceed dstH (no defined result)";
+            return false;
+        }
         pick_fast_lanczos(p);
         break;
     case kArea:

@@ -13,7 +13,11 @@
 //     that call (the public API has no error channel);
 //   * any other status (IQO_HIP_EINVAL / _EUNSUP: a plan / kernel / layout mismatch, i.e. a bug
 //     or an unsupported argument, not a missing device) -> a message on EVERY such call, then the
-//     CPU path.
+//     CPU path;
+//   * a shape no plan exists for (build_plan fails on both backends: a zero size, or a Lanczos
+//     shape whose top border rows exceed dstH, where the reference writes rows past the image)
+//     -> build_plan's message on stderr and an abort in the constructor: no table is built and
+//     cpu_generic.cpp never sees the shape.
 // IQO_REQUIRE_HIP=1 in the environment turns every fallback into an abort: tests/test_gpu_parity.py
 // sets it for the whole GPU test process and its children, so no GPU test can pass on the CPU
 // path.  IQO_DROPIN_REPORT=1 prints the backend counts at exit (for binaries that cannot call

@@ -498,6 +498,12 @@ static void lz_resize_x(const iqo_oracle *o, const int16_t *src, uint8_t *dst)
     ptrdiff_t mainEnd = (o->srcW - m) * o->dstW / o->srcW;
     if (mainEnd < 0)
         mainEnd = 0;
+    /* mainBegin > dstW (the window is wider than the source): the reference's first call writes
+     * columns >= dstW, into the next row or past the last one.  Every column's value comes from its
+     * own index alone and the last call rewrites [mainEnd, dstW), so stopping at dstW changes no
+     * column < dstW. */
+    if (mainBegin > o->dstW)
+        mainBegin = o->dstW;
     lz_resize_x_border(o, src, dst, 0, mainBegin);
     lz_resize_x_main(o, src, dst, mainBegin, mainEnd);
     lz_resize_x_border(o, src, dst, mainEnd, o->dstW);

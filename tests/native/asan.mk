@@ -5,7 +5,7 @@
 #                     CPU backend (cpu_generic.cpp) and the host plan (plan.cpp); the device side
 #                     of the C ABI is tests/native/asan_nodevice.cpp (no gfx950 device)
 #   host_tables_asan  tests/native/host_tables.cpp: every plan.cpp table builder, band windows and
-#                     the kernels' table reads emulated (ratio_emul.cpp, tile_emul.cpp)
+#                     the kernels' table reads emulated (ratio_emul.cpp, tile_emul.cpp, packed_emul.cpp)
 #   make -f tests/native/asan.mk [-j8]
 ROOT  := $(abspath $(dir $(lastword $(MAKEFILE_LIST)))/../..)
 OUT   ?= $(ROOT)/tests/native/_build/asan
@@ -30,5 +30,5 @@ $(OUT)/%.o: $(ROOT)/tests/native/%.cpp $(wildcard $(CSRC)/*.hpp) $(ROOT)/include
 $(OUT)/dropin_cpu_asan: $(OUT)/dropin_cpu.o $(OUT)/resizers.o $(OUT)/cpu_generic.o $(OUT)/plan.o $(OUT)/asan_nodevice.o
 	$(CXX) $(SAN) -o $@ $^
 
-$(OUT)/host_tables_asan: $(OUT)/host_tables.o $(OUT)/ratio_emul.o $(OUT)/tile_emul.o $(OUT)/plan.o
+$(OUT)/host_tables_asan: $(OUT)/host_tables.o $(OUT)/ratio_emul.o $(OUT)/tile_emul.o $(OUT)/packed_emul.o $(OUT)/plan.o
 	$(CXX) $(SAN) -o $@ $^

@@ -28,7 +28,8 @@ int exact_div(int n, int d)
 extern "C" {
 
 // src / dst: packed rows of srcSt / dstSt bytes.  Returns 0 on success, 1 if the shape has no packed
-// tile tables (packed_general_kernel), -1 on bad arguments.  geom (may be null): {CT, TH, NP, tiles in x}.
+// tile tables (packed_general_kernel), -1 on bad arguments.  geom (may be null): {CT, TH, NP, tiles in x,
+// first column tile is a border tile, last column tile is a border tile}.
 int packed_emul(int method, unsigned degree, int C, int srcW, int srcH, int dstW, int dstH, int pxScale,
                 const uint8_t *src, int srcSt, uint8_t *dst, int dstSt, int *geom)
 {
@@ -49,6 +50,8 @@ int packed_emul(int method, unsigned degree, int C, int srcW, int srcH, int dstW
         geom[1] = k.TH;
         geom[2] = t.NP;
         geom[3] = nTx;
+        geom[4] = k.spans.front().border;
+        geom[5] = k.spans.back().border;
     }
     if (packed_lds_bytes(p, t, k, k.TH) > 64 * 1024)
         return -1;

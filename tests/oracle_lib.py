@@ -6,6 +6,7 @@ oracle/Makefile (present only where /root/reference was available at build time)
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -178,9 +179,31 @@ def fnv1a64(arr2d):
     return int(oracle().iqo_fnv1a64(_ptr(a), a.shape[1], a.shape[0], a.shape[1]))
 
 
+# ----------------------------------------------------------------------------- shapes without an answer
+
+def lanczos_taps(degree, src_len, dst_len, px_scale=1):
+    """Taps of one Lanczos axis (calcNumCoefsForLanczos, IQOLanczosResizerImpl_Generic.cpp:32-96)."""
+    g = math.gcd(src_len, dst_len)
+    rs, rd = src_len // g, dst_len // g
+    if rs <= rd:
+        return 2 * degree
+    return 2 * int(math.ceil(float(max(1, degree // px_scale) * rs) / float(rd)))
+
+
+def lanczos_rows_defined(degree, srcH, dstH, pxScale=1):
+    """False where the reference's first row loop (dstY < mainBegin, :392-400) runs past dstH: the
+    reference, and the oracle that restates it, write rows that do not exist, so the shape has no
+    answer and the product rejects it.  Neither may be CALLED on such a shape."""
+    if srcH == dstH:
+        return True
+    m = lanczos_taps(degree, srcH, dstH, pxScale) // 2
+    return ((m - 1) * dstH + srcH - 1) // srcH <= dstH
+
+
 # ----------------------------------------------------------------------------- runners
 
 def run_oracle(method, degree, sw, sh, dw, dh, px, src, dst_st=None):
+    assert method != "lanczos" or lanczos_rows_defined(degree, sh, dh, px), "no defined answer: never run on this shape"
     src = np.ascontiguousarray(src)
     dst_st = dst_st or dw
     dst = np.zeros((dh, dst_st), dtype=np.uint8)
@@ -190,6 +213,7 @@ def run_oracle(method, degree, sw, sh, dw, dh, px, src, dst_st=None):
 
 
 def run_ref(method, degree, sw, sh, dw, dh, px, src, strict=False):
+    assert method != "lanczos" or lanczos_rows_defined(degree, sh, dh, px), "no defined answer: never run on this shape"
     src = np.ascontiguousarray(src)
     dst = np.zeros((dh, dw), dtype=np.uint8)
     rc = ref(strict).iqo_ref_run(METHODS[method], degree, sw, sh, dw, dh, px, src.shape[1], _ptr(src), dw, _ptr(dst))

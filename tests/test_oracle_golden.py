@@ -129,6 +129,8 @@ def test_oracle_matches_reference_random():
         dh = rng.randint(max(1, sh // 5), sh * 3) if m == "lanczos" else rng.randint(max(1, sh // 6), sh)
         if m == "area" and (sw % dw or sh % dh):
             continue  # non-integer area ratios read past the buffer in the reference
+        if m == "lanczos" and not ol.lanczos_rows_defined(d, sh, dh, 1):
+            continue  # the reference writes rows >= dstH: neither it nor the oracle is run on the shape
         if not _ref_clean(m, d, sw, sh, dw, dh):
             continue  # the reference itself traps (zero border denominator) on this shape
         src = ol.gen("noise", sw, sh, i)

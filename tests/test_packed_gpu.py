@@ -1,7 +1,9 @@
 """GPU parity of the packed (interleaved RGB / RGBA / UV / NV12) resize: channel c of every result
 equals the oracle (the reference's Generic resize, restated) run on channel c as a plane, bit for
 bit -- through packed_tile_kernel and packed_general_kernel, over shapes, layouts, bands, host
-pointers, NV12, the plan cache and the error paths.  Small shapes, 2 frames: a few seconds each."""
+pointers, NV12, the plan cache and the error paths; every packed_tile_kernel<C, NP, LZ> instantiation
+and every tile shape (packed_cases.INSTANTIATIONS / GEOMETRY, sections 11 - 13).  Small shapes, 2
+frames (3 with the constant-channel frame): well under a second each."""
 import gc
 import os
 import random
@@ -278,7 +280,8 @@ def test_packed_errors():
 
 def _fuzz_cases():
     """24 seeded shapes, sides 4..96, all three methods, C per case.  Linear upscales beyond 2x (the
-    reference reads outside its rows there: no pinned answer) are left out while generating."""
+    reference reads outside its rows there: no pinned answer) and Lanczos shapes the plan rejects
+    (ol.lanczos_rows_defined: the reference writes rows >= dstH) are left out while generating."""
     rng = random.Random(1409)
     out = []
     while len(out) < 24:
@@ -286,6 +289,8 @@ def _fuzz_cases():
         d = rng.randint(1, 5) if m == "lanczos" else 0
         sw, sh, dw, dh = (rng.randint(4, 96) for _ in range(4))
         if m == "linear" and (dw > 2 * sw or dh > 2 * sh):
+            continue
+        if m == "lanczos" and not ol.lanczos_rows_defined(d, sh, dh, 1):
             continue
         out.append((m, d, sw, sh, dw, dh, 1, rng.choice(CHANNELS)))
     return out
@@ -299,3 +304,175 @@ def test_packed_random_shapes_match_oracle(case):
     r = _make(shape, C)
     out = r.resize_tensor(torch.from_numpy(frames).to(DEV)).cpu().numpy()
     _check(out, exp, (case, r.describe()["kernel"]))
+
+
+# ---- 11. every packed_tile_kernel<C, NP, LZ> instantiation and every tile shape
+#
+# packed_cases.INSTANTIATIONS has one row per (C, NP, LZ), GEOMETRY the tile shapes (every CT and
+# TH with two tiles or more and a partial last one); tests/test_packed_host.py proves both censuses
+# and the rows' literals on the host.  Each row: frames_for's two frames plus a frame whose channels
+# are the constants (0, 255, 1, 254)[:C]; byte for byte against the oracle, no tolerance.
+
+def _cell(row):
+    shape, C, CT, TH, NP = row
+    return "C=%d NP=%d LZ=%s CT=%d TH=%d %s" % (C, NP, shape[0] == "lanczos", CT, TH, pc.sid(shape))
+
+
+def _check_cell(got, exp, row, what):
+    bad = np.argwhere(got != exp)
+    assert bad.size == 0, "%s: %s differs at %d bytes, first [frame, y, x, c] %s" % (_cell(row), what, len(bad),
+                                                                                    bad[:4].tolist())
+
+
+def _cell_io(row):
+    """Frames [3, sh, sw, C] (frames_for's two and the constant one) and their oracle results."""
+    shape, C = row[0], row[1]
+    const = pc.const_frame(shape, C)
+    frames = np.concatenate([pc.frames_for(shape, C), const[None]])
+    exp = np.concatenate([pc.expected_for(shape, C), pc.oracle_packed(shape, const)[None]])
+    return frames, exp
+
+
+def _run_cell(row, constants_kept=True):
+    shape, C, CT, TH, NP = row
+    frames, exp = _cell_io(row)
+    r = _make(shape, C)
+    desc = r.describe()
+    assert desc["kernel"] == "packed_tile" and desc["tile_rows"] == TH and desc["channels"] == C, (_cell(row), desc)
+    src = torch.from_numpy(frames).to(DEV)
+    out = r.resize_tensor(src)
+    got = out.cpu().numpy()
+    _check_cell(got, exp, row, "packed_tile vs the oracle")
+    if constants_kept:  # a wrong byte selector shows as cross-talk between the channels
+        want = np.broadcast_to(np.array(pc.CONST_CHANNELS[:C], np.uint8), got[2].shape)
+        _check_cell(got[2:], want[None], row, "constant channels")
+    r.set_option("force_general", 1)
+    assert r.describe()["kernel"] == "packed_general"
+    gen = r.resize_tensor(src)
+    _check_cell(gen.cpu().numpy(), got, row, "packed_general vs packed_tile")
+
+
+@pytest.mark.parametrize("row", pc.INSTANTIATIONS, ids=pc.cell_id)
+def test_packed_every_instantiation(row):
+    _run_cell(row)
+
+
+@pytest.mark.parametrize("row", pc.GEOMETRY, ids=pc.cell_id)
+def test_packed_tile_geometries(row):
+    _run_cell(row)
+
+
+@pytest.mark.parametrize("row", pc.LANCZOS_WIDE_UPSCALES, ids=pc.cell_id)
+def test_packed_wide_lanczos_upscales(row):
+    """CT = 512 at C = 2 and CT = 256 at C = 4 under Lanczos: upscales above 2x, where the reference
+    itself does not keep the constant frame (packed_cases.LANCZOS_WIDE_UPSCALES), so that frame is
+    compared with the oracle like the others."""
+    _run_cell(row, constants_kept=False)
+
+
+# ---- 12. layouts over the matrix: wide stores with a guarded row end, byte-shifted sources,
+#          byte-shifted destinations
+
+LAYOUT_ROWS = [pc.GEOMETRY[0], pc.GEOMETRY[1], pc.GEOMETRY[4], pc.GEOMETRY[5], pc.GEOMETRY[10], pc.GEOMETRY[11],
+               pc.GEOMETRY[12], pc.LANCZOS_WIDE_UPSCALES[1], pc.INSTANTIATIONS[31], pc.INSTANTIATIONS[63]]
+
+
+def test_layout_rows_cover_the_kernel_paths():
+    assert len(LAYOUT_ROWS) >= 8
+    assert {r[1] for r in LAYOUT_ROWS} == {2, 3, 4}
+    assert {r[0][0] == "lanczos" for r in LAYOUT_ROWS} == {True, False}
+    assert any(r[2] >= 256 for r in LAYOUT_ROWS) and any(r[3] == 2 for r in LAYOUT_ROWS)
+    assert all(r[0][4] % 4 for r in LAYOUT_ROWS)  # the last quad of a row is partial: single-byte stores
+
+
+def _up4(v):
+    return (v + 3) & ~3
+
+
+@pytest.mark.parametrize("row", LAYOUT_ROWS, ids=pc.cell_id)
+def test_packed_layout_sweep(row):
+    shape, C, CT, TH, NP = row
+    m, d, sw, sh, dw, dh, px = shape
+    n = 2
+    frames, exp = pc.frames_for(shape, C), pc.expected_for(shape, C)
+    r = _make(shape, C)
+    assert r.describe()["kernel"] == "packed_tile"
+    G = 64  # guard bytes before the base and after the last frame
+    wide_st = _up4(dw * C + 8)  # a multiple of 4 with >= 8 bytes of padding: a store past the row's end lands in it
+    # (name, source base offset, srcSt, destination base offset, dstSt)
+    layouts = [("wide stores, guarded row end", 0, sw * C, 0, wide_st)]
+    layouts += [("source shifted by %d" % k, k, _up4(sw * C) + 4, 0, wide_st) for k in (1, 2, 3)]
+    layouts += [("destination shifted by %d" % k, 0, sw * C, k, wide_st) for k in (1, 2, 3)]
+    for name, soff, sst, doff, dst_st in layouts:
+        assert sst % 4 == 0 or soff == 0
+        assert dst_st % 4 == 0 and dst_st >= dw * C + 8
+        sfst, dfst = sh * sst, dh * dst_st
+        sbuf = torch.zeros(soff + n * sfst + 64, dtype=torch.uint8, device=DEV)
+        assert sbuf.data_ptr() % 4 == 0
+        sview = sbuf[soff:soff + n * sfst].view(n, sh, sst)
+        sview[:, :, :sw * C] = torch.from_numpy(frames.reshape(n, sh, sw * C)).to(DEV)
+        dbuf = torch.full((G + doff + n * dfst + G,), SENTINEL, dtype=torch.uint8, device=DEV)
+        assert dbuf.data_ptr() % 4 == 0
+        r.resize_device(n, sst, sfst, sview.data_ptr(), dst_st, dfst, dbuf.data_ptr() + G + doff)
+        torch.cuda.synchronize()
+        full = dbuf.cpu().numpy()
+        body = full[G + doff:G + doff + n * dfst].reshape(n, dh, dst_st)
+        _check_cell(body[:, :, :dw * C].reshape(n, dh, dw, C), exp, row, name)
+        pad = np.argwhere(body[:, :, dw * C:] != SENTINEL)
+        assert pad.size == 0, "%s: %s wrote into the row padding at [frame, y, byte] %s" % (_cell(row), name,
+                                                                                          pad[:4].tolist())
+        assert (full[:G + doff] == SENTINEL).all(), "%s: %s wrote before the base" % (_cell(row), name)
+        assert (full[G + doff + n * dfst:] == SENTINEL).all(), "%s: %s wrote past the last frame" % (_cell(row), name)
+
+
+# ---- 13. bands at C = 2 and C = 4: one-row bands and band starts inside a tile
+
+BAND_ROWS = [pc.GEOMETRY[13], pc.GEOMETRY[14], pc.GEOMETRY[8], pc.GEOMETRY[9]]  # C = 2, 4 down; C = 2, 4 up
+
+
+def test_band_rows_cover_both_directions():
+    assert sorted((r[1], r[0][2] > r[0][4]) for r in BAND_ROWS) == [(2, False), (2, True), (4, False), (4, True)]
+    assert all(r[0][5] > r[3] for r in BAND_ROWS)  # two row tiles or more
+
+
+@pytest.mark.parametrize("row", BAND_ROWS, ids=pc.cell_id)
+def test_packed_uneven_row_bands(row):
+    shape, C, CT, TH, NP = row
+    m, d, sw, sh, dw, dh, px = shape
+    src = torch.from_numpy(pc.frames_for(shape, C)).to(DEV)
+    r = _make(shape, C)
+    assert r.describe()["kernel"] == "packed_tile" and r.describe()["tile_rows"] == TH
+    full = r.resize_tensor(src)
+    _check_cell(full.cpu().numpy(), pc.expected_for(shape, C), row, "unsharded vs the oracle")
+    cuts = [0, 1, TH - 1, TH + 1, dh // 2, dh - 2, dh]
+    assert cuts == sorted(set(cuts)), cuts
+    parts = []
+    for r0, r1 in zip(cuts[:-1], cuts[1:]):
+        s0, sn = r.band_src_rows(r0, r1 - r0)
+        window = src[:, s0:s0 + sn].contiguous()
+        band = torch.empty((2, r1 - r0, dw, C), dtype=torch.uint8, device=DEV)
+        r.resize_band(2, r0, r1 - r0, s0, sw * C, sn * sw * C, window, dw * C, (r1 - r0) * dw * C, band,
+                      torch.cuda.current_stream())
+        parts.append(band)
+    torch.cuda.synchronize()
+    _check_cell(torch.cat(parts, dim=1).cpu().numpy(), full.cpu().numpy(), row, "bands %s vs unsharded" % cuts)
+
+
+# ---- 14. NV12 upscale: the UV plane runs at C = 2 with pxScale 2, upscaling
+
+def test_nv12_upscale_planes_match_oracle():
+    test_nv12_planes_match_oracle(("lanczos", 3, 64, 48, 160, 120))
+
+
+# ---- 15. Lanczos shapes whose top border rows exceed dstH are rejected before any launch
+
+@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("shape", pc.REJECTED, ids=pc.sid)
+def test_rejected_lanczos_shapes_raise(shape, C):
+    m, d, sw, sh, dw, dh, px = shape
+    assert not ol.lanczos_rows_defined(d, sh, dh, px)
+    with pytest.raises(libiqo_amd.IqoError):
+        libiqo_amd.make_resizer(m, d, sw, sh, dw, dh, px, channels=C)
+    if px == 1:
+        with pytest.raises(libiqo_amd.IqoError):
+            libiqo_amd.Nv12Resizer(m, d, sw, sh, dw, dh)

@@ -45,7 +45,7 @@ def run_emul(lib, shape, C, img, dst_pad=0):
     m, d, sw, sh, dw, dh, px = shape
     img = np.ascontiguousarray(img)
     dst = np.full((dh, dw * C + dst_pad), 0xA5, np.uint8)
-    geom = (ctypes.c_int * 4)()
+    geom = (ctypes.c_int * 6)()
     rc = lib.packed_emul(METHODS[m], d, C, sw, sh, dw, dh, px, img.ctypes.data, sw * C, dst.ctypes.data,
                          dst.shape[1], geom)
     return rc, dst, list(geom)
@@ -138,3 +138,101 @@ def test_python_surface():
         assert inspect.signature(fn).parameters["channels"].default == 1
     for name in ("Nv12Resizer", "host_packed_kernel_for"):
         assert name in libiqo_amd.__all__
+
+
+# ---- the instantiation matrix and the tile shapes (packed_cases.INSTANTIATIONS / GEOMETRY)
+
+MATRIX = pc.INSTANTIATIONS + pc.GEOMETRY + pc.LANCZOS_WIDE_UPSCALES
+
+
+def test_instantiation_matrix_is_the_full_product():
+    """One row per packed_tile_kernel<C, NP, LZ>: 3 x 11 x 2 = 66, over the NP list plan.hpp holds."""
+    import re
+    text = open(os.path.join(ROOT, "libiqo_amd", "csrc", "plan.hpp")).read()
+    k = re.search(r"constexpr int kTileNP\[\]\s*=\s*\{([^}]*)\}", text)
+    assert k and tuple(int(v) for v in k.group(1).split(",")) == pc.TILE_NP
+    cells = [(C, NP, shape[0] == "lanczos") for shape, C, _, _, NP in pc.INSTANTIATIONS]
+    assert len(cells) == 66 and len(set(cells)) == 66
+    assert set(cells) == {(C, NP, LZ) for C in (2, 3, 4) for NP in pc.TILE_NP for LZ in (True, False)}
+    for shape, C, CT, TH, NP in pc.INSTANTIATIONS:
+        m, d, sw, sh, dw, dh, px = shape
+        assert sh <= 48 and dw <= 40 and dh <= 32 and sh != dh, shape
+    assert {s[0][0] for s in pc.INSTANTIATIONS if s[0][0] != "lanczos"} == {"area", "linear"}
+    assert sum(s[0][6] == 2 for s in pc.INSTANTIATIONS) >= 6  # negative border divisors
+
+
+def test_matrix_shapes_have_a_pinned_answer():
+    for shape, C, _, _, _ in MATRIX:
+        m, d, sw, sh, dw, dh, px = shape
+        assert m != "lanczos" or ol.lanczos_rows_defined(d, sh, dh, px), shape
+        assert m != "linear" or (dw <= 2 * sw and dh <= 2 * sh), shape
+    for m, d, sw, sh, dw, dh, px in pc.REJECTED:
+        assert not ol.lanczos_rows_defined(d, sh, dh, px)
+    assert {s[6] for s in pc.REJECTED} == {1, 2}
+
+
+def test_geometry_covers_every_tile_shape(emul):
+    """Every CT and every TH, each with two tiles or more and a partial last one."""
+    cts, ths, odd_bytes, both_borders = set(), set(), False, False
+    for shape, C, CT, TH, NP in pc.GEOMETRY:
+        m, d, sw, sh, dw, dh, px = shape
+        rc, _, geom = run_emul(emul, shape, C, pc.packed_noise(sw, sh, C, 3))
+        assert rc == 0 and geom[:3] == [CT, TH, NP], (shape, C, geom)
+        nTx = geom[3]
+        if dw > CT and dw % CT and dw % 4:
+            assert nTx >= 2
+            cts.add(CT)
+            both_borders |= bool(geom[4] and geom[5])
+        if dh > TH and dh % TH:
+            ths.add(TH)
+        odd_bytes |= (sw * C) % 8 != 0
+    assert cts == {64, 128, 256, 512} and ths == {2, 4, 8, 16}
+    assert odd_bytes and both_borders
+    # the wide Lanczos upscales: CT = 512 at C = 2, CT = 256 at C = 4, upscaling by more than 2
+    assert {(C, CT) for _, C, CT, _, _ in pc.LANCZOS_WIDE_UPSCALES} == {(2, 512), (4, 256)}
+    assert all(s[0][4] > 2 * s[0][2] and s[0][4] > s[2] and s[0][4] % 4 for s in pc.LANCZOS_WIDE_UPSCALES)
+
+
+@pytest.mark.parametrize("row", MATRIX, ids=pc.cell_id)
+def test_matrix_rows_match_their_literals_and_the_oracle(emul, row):
+    import libiqo_amd
+    shape, C, CT, TH, NP = row
+    m, d, sw, sh, dw, dh, px = shape
+    assert libiqo_amd.host_packed_kernel_for(m, d, C, sw, sh, dw, dh, px) == "packed_tile"
+    frames = list(pc.frames_for(shape, C)) + [pc.const_frame(shape, C)]
+    exp = list(pc.expected_for(shape, C)) + [pc.oracle_packed(shape, frames[2])]
+    if row not in pc.LANCZOS_WIDE_UPSCALES:  # (the GPU tests assert these constants of the kernel's output)
+        assert (exp[2] == np.array(pc.CONST_CHANNELS[:C], np.uint8)).all(), "the reference does not keep the constants"
+    for f, e in zip(frames, exp):
+        rc, out, geom = run_emul(emul, shape, C, f, dst_pad=5)
+        assert rc == 0 and geom[:3] == [CT, TH, NP], (pc.cell_id(row), rc, geom)
+        assert (out[:, dw * C:] == 0xA5).all()
+        bad = np.argwhere(out[:, :dw * C].reshape(dh, dw, C) != e)
+        assert bad.size == 0, (pc.cell_id(row), bad[:4].tolist())
+
+
+@pytest.mark.parametrize("shape", pc.REJECTED, ids=pc.sid)
+def test_rejected_lanczos_shapes_raise(emul, shape):
+    """The top border rows exceed dstH: no plan, from any constructor or host query (the calls fail
+    on the host, before any device is looked at)."""
+    import libiqo_amd
+    m, d, sw, sh, dw, dh, px = shape
+    with pytest.raises(libiqo_amd.IqoError):
+        libiqo_amd.host_kernel_for(m, d, sw, sh, dw, dh, px)
+    for C in (1, 2, 3, 4):
+        with pytest.raises(libiqo_amd.IqoError):
+            libiqo_amd.host_packed_kernel_for(m, d, C, sw, sh, dw, dh, px)
+    L = libiqo_amd.lib()
+    plan = ctypes.c_void_p()
+    assert L.iqo_hip_plan_lanczos(d, sw, sh, dw, dh, px, 0, ctypes.byref(plan)) == -1 and not plan  # IQO_HIP_EINVAL
+    for C in (1, 3):
+        assert L.iqo_hip_plan_packed(0, d, C, sw, sh, dw, dh, px, 0, ctypes.byref(plan)) == -1 and not plan
+    if px == 1:  # the Y plane of a 4:2:0 / NV12 frame of this size
+        assert L.iqo_hip_plan_yuv420(0, d, sw, sh, dw, dh, 0, ctypes.byref(plan)) == -1 and not plan
+        assert L.iqo_hip_plan_nv12(0, d, sw, sh, dw, dh, 0, ctypes.byref(plan)) == -1 and not plan
+    else:        # ... and the chroma planes (pxScale 2) of a frame twice this size
+        assert L.iqo_hip_plan_nv12(0, d, 2 * sw, 2 * sh, 2 * dw, 2 * dh, 0, ctypes.byref(plan)) == -1 and not plan
+    img = pc.packed_noise(sw, sh, 3, 1)
+    assert run_emul(emul, shape, 3, img)[0] == -1
+    # the same sizes with rows to spare are accepted
+    assert libiqo_amd.host_kernel_for(m, d, sw, 4 * sh, dw, 4 * dh, px)
