@@ -147,6 +147,44 @@ int iqo_hip_resize_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size
                           const uint8_t *dSrc, size_t dstSt, size_t dstFrameSt, uint8_t *dDst,
                           void *stream);
 
+/* Packed plans (channels 2..4) straight to a model's input: the batched resize above, stored as
+ * normalised PLANAR float tensors [frame][plane][row][column] instead of interleaved bytes.  With
+ * u8(f, y, x, c) the byte iqo_hip_resize_device writes for the same plan and source,
+ *
+ *   out(f, p, y, x) = cvt( fl32( fl32( (float)u8(f, y, x, order[p]) * scale[p] ) + bias[p] ) )
+ *
+ * two separately rounded fp32 operations (not a fused multiply-add); cvt is the identity for
+ * IQO_OUT_F32 and round-to-nearest-even to fp16 / bf16 otherwise (overflow gives +-inf).  This is
+ * numpy's u8.astype(float32) * float32(s) + float32(b), then .astype(float16) (or torch's
+ * .to(bfloat16)), bit for bit.  (v/255 - mean)/std is scale = 1/(255 std), bias = -mean/std; order
+ * reorders channels (BGR -> RGB: {2, 1, 0}), repeats them or drops some (planes < channels).
+ *
+ * Element (f, p, y, x) is at dDst + f*dstFrameSt + p*dstPlaneSt + y*dstRowSt + x*elem, elem = 4 or 2
+ * bytes, every stride in BYTES.  dDst and the strides need no alignment beyond the element size
+ * (the kernels store 16 / 8 bytes per thread where the addresses allow and single elements
+ * otherwise).  Asynchronous on `stream`; the plan's tables are uploaded as for iqo_hip_resize_device
+ * (iqo_hip_plan_prepare beforehand for graph capture).  The option "force_general" applies.
+ *
+ * Plans with channels 2..4 only: a planar (1-channel) plan returns IQO_HIP_EUNSUP -- planar plans
+ * dispatch to sixteen kernel families, none of which has the float epilogue.
+ * IQO_HIP_EINVAL: a null plan, dSrc, dDst or norm; an unknown dtype; planes outside 1..4; an order[p]
+ * outside 0..channels-1; a non-finite scale[p] or bias[p] (p < planes; entries from `planes` on are
+ * ignored); dDst or a destination stride that is no multiple of elem; srcSt < srcW*channels;
+ * dstRowSt < dstW*elem; dstPlaneSt < dstH*dstRowSt; dstFrameSt < planes*dstPlaneSt when nFrames > 1;
+ * a source frame, or a float frame (from its first element to the end of its last plane's last row),
+ * that reaches 2^31 bytes; srcSt >= 2^24.  On any error nothing is launched and the destination is
+ * untouched. */
+enum { IQO_OUT_F32 = 1, IQO_OUT_F16 = 2, IQO_OUT_BF16 = 3 };
+typedef struct {
+    int dtype;                 /* IQO_OUT_* */
+    int planes;                /* 1..4 output planes */
+    int order[4];              /* order[p] in 0..channels-1: the source channel of plane p (repeats allowed) */
+    float scale[4], bias[4];   /* per output plane, finite */
+} iqo_hip_norm;
+int iqo_hip_resize_device_norm(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt,
+                               const uint8_t *dSrc, const iqo_hip_norm *norm, size_t dstRowSt,
+                               size_t dstPlaneSt, size_t dstFrameSt, void *dDst, void *stream);
+
 /* Source rows [*srcRow0, *srcRow0 + *srcRows) that output rows [dstRow0, dstRow0 + dstRows)
  * read (the halo of a row band).  Host-only, no device work. */
 int iqo_hip_band_src_rows(const iqo_hip_plan *plan, size_t dstRow0, size_t dstRows, size_t *srcRow0,

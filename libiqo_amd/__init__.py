@@ -14,7 +14,7 @@ import os
 
 __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420Resizer", "Nv12Resizer", "available",
            "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
-           "ipc_close", "KERNELS", "COPY_PATHS", "LIB_PATH"]
+           "ipc_close", "KERNELS", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -36,6 +36,15 @@ class PlanDesc(ctypes.Structure):
                 ("dstW", _c_sz), ("dstH", _c_sz), ("tapsX", ctypes.c_int), ("tapsY", ctypes.c_int),
                 ("phasesX", ctypes.c_int), ("phasesY", ctypes.c_int), ("kernel", ctypes.c_int),
                 ("bandsPerFrame", ctypes.c_int), ("tileRows", ctypes.c_int)]
+
+
+class Norm(ctypes.Structure):
+    """iqo_hip_norm: element type, output planes, their source channels and affine maps."""
+    _fields_ = [("dtype", ctypes.c_int), ("planes", ctypes.c_int), ("order", ctypes.c_int * 4),
+                ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4)]
+
+
+OUT_F32, OUT_F16, OUT_BF16 = 1, 2, 3  # IQO_OUT_*
 
 
 class IpcHandle(ctypes.Structure):
@@ -71,6 +80,8 @@ def lib():
     L.iqo_hip_plan_set_option.argtypes = [_vp, ctypes.c_char_p, ctypes.c_long]
     L.iqo_hip_resize.argtypes = [_vp, _c_sz, _vp, _c_sz, _vp]
     L.iqo_hip_resize_device.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_sz, _vp, _vp]
+    L.iqo_hip_resize_device_norm.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _vp, ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz,
+                                             _vp, _vp]
     L.iqo_hip_band_src_rows.argtypes = [_vp, _c_sz, _c_sz, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]
     L.iqo_hip_resize_band.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_sz, _vp, _vp]
     L.iqo_hip_strerror.restype = ctypes.c_char_p
@@ -309,6 +320,53 @@ class _Resizer:
             stream = torch.cuda.current_stream(s.device)
         self.resize_device(s.shape[0], s.stride(1), s.stride(0), s, o.stride(1), o.stride(0), o, stream)
         return out[0] if squeeze else out
+
+    # -- packed plans straight to a model's input: planar float planes of (byte * scale + bias)
+    def resize_normalized(self, src, scale, bias, dtype=None, order=None, out=None, stream=None):
+        """iqo_hip_resize_device_norm on torch tensors.  src: [F, srcH, srcW, C] (or [srcH, srcW, C]) uint8 on
+        the plan's device.  Returns [F, planes, dstH, dstW] (or [planes, dstH, dstW]) of `dtype` (float32,
+        float16 or bfloat16): plane p is float32(byte of channel order[p]) * scale[p] + bias[p], each
+        operation rounded to float32, then rounded to `dtype`.  planes = len(order), or C with the identity
+        order.  `out` may be a strided view with unit column stride and non-overlapping rows, planes and
+        frames; it is returned."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32
+        C = self.channels
+        if C < 2:
+            raise IqoError("resize_normalized needs a packed resizer (channels 2..4)")
+        codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+        if dtype not in codes:
+            raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        order = tuple(range(C)) if order is None else tuple(int(c) for c in order)
+        scale, bias = tuple(float(v) for v in scale), tuple(float(v) for v in bias)
+        planes = len(order)
+        if not 1 <= planes <= 4 or len(scale) != planes or len(bias) != planes:
+            raise IqoError("order, scale and bias must have the same length, 1..4 (one entry per output plane)")
+        squeeze = src.dim() == 3
+        s = src.unsqueeze(0) if squeeze else src
+        if s.dtype != torch.uint8 or not s.is_cuda or s.dim() != 4 or tuple(s.shape[1:]) != (self.srcH, self.srcW, C):
+            raise IqoError("expected uint8 device tensor [F, %d, %d, %d]" % (self.srcH, self.srcW, C))
+        s = s.contiguous()
+        shape = (s.shape[0], planes, self.dstH, self.dstW)
+        if out is None:
+            out = torch.empty(shape[1:] if squeeze else shape, dtype=dtype, device=s.device)
+        o = out.unsqueeze(0) if out.dim() == 3 else out
+        if (o.dtype != dtype or o.device != s.device or tuple(o.shape) != shape or o.stride(3) != 1
+                or o.stride(2) < self.dstW or o.stride(1) < self.dstH * o.stride(2)
+                or (o.shape[0] > 1 and o.stride(0) < planes * o.stride(1))):
+            raise IqoError("out must be a %s tensor [%d, %d, %d, %d] on %s with unit column stride and "
+                           "non-overlapping rows, planes and frames" % ((dtype,) + shape + (s.device,)))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        n = Norm(codes[dtype], planes)
+        for i in range(planes):
+            n.order[i], n.scale[i], n.bias[i] = order[i], scale[i], bias[i]
+        e = o.element_size()
+        _check(lib().iqo_hip_resize_device_norm(self._plan, s.shape[0], s.stride(1), s.stride(0), _ptr(s),
+                                                ctypes.byref(n), o.stride(2) * e, o.stride(1) * e, o.stride(0) * e,
+                                                _ptr(o), _stream_ptr(stream)), "resize_normalized")
+        return out
 
 
 class LanczosResizer(_Resizer):

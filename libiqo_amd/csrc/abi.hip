@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1569,6 +1570,76 @@ int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t src
     return IQO_HIP_OK;
 }
 
+// iqo_hip_resize_device_norm: every check runs on the host before the first launch, so a rejected
+// call leaves the destination untouched.
+int run_norm(iqo_hip_plan *h, size_t nFrames, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
+             const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt, size_t dstFrameSt, void *dst, hipStream_t s)
+{
+    if (!src || !dst || !norm)
+        return IQO_HIP_EINVAL;
+    if (h->channels < 2)  // planar plans: sixteen kernel families without the float epilogue
+        return IQO_HIP_EUNSUP;
+    const Plan &p = h->p;
+    const size_t C = static_cast<size_t>(h->channels);
+    if (norm->dtype != IQO_OUT_F32 && norm->dtype != IQO_OUT_F16 && norm->dtype != IQO_OUT_BF16)
+        return IQO_HIP_EINVAL;
+    if (norm->planes < 1 || norm->planes > 4)
+        return IQO_HIP_EINVAL;
+    for (int i = 0; i < norm->planes; ++i)
+        if (norm->order[i] < 0 || norm->order[i] >= h->channels || !std::isfinite(norm->scale[i]) ||
+            !std::isfinite(norm->bias[i]))
+            return IQO_HIP_EINVAL;
+    const size_t elem = norm->dtype == IQO_OUT_F32 ? 4 : 2;
+    const size_t dstW = static_cast<size_t>(p.dstW), dstH = static_cast<size_t>(p.dstH);
+    const size_t planes = static_cast<size_t>(norm->planes);
+    if (reinterpret_cast<uintptr_t>(dst) % elem || dstRowSt % elem || dstPlaneSt % elem || dstFrameSt % elem)
+        return IQO_HIP_EINVAL;
+    // (divisions: no product of caller-supplied strides can wrap)
+    if (srcSt < static_cast<size_t>(p.srcW) * C || dstRowSt < dstW * elem || dstPlaneSt / dstH < dstRowSt ||
+        (nFrames > 1 && dstFrameSt / planes < dstPlaneSt))
+        return IQO_HIP_EINVAL;
+    // the kernels address one float frame with 32-bit byte offsets (launch_packed_tile's limits)
+    const size_t kLim = size_t(1) << 31;
+    if (dstRowSt >= kLim || dstPlaneSt >= kLim ||
+        (planes - 1) * dstPlaneSt + (dstH - 1) * dstRowSt + dstW * elem >= kLim ||
+        static_cast<size_t>(p.srcH - 1) * srcSt + static_cast<size_t>(p.srcW) * C >= kLim || srcSt >= (size_t(1) << 24))
+        return IQO_HIP_EINVAL;
+    if (nFrames == 0)
+        return IQO_HIP_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    const int rc = ensure_tables(h);
+    if (rc)
+        return rc;
+    const int kernel = plan_kernel(h);
+    iqo_amd::NormDev n;
+    n.dtype = norm->dtype;
+    n.planes = norm->planes;
+    n.planeSt = static_cast<int>(dstPlaneSt);
+    for (int i = 0; i < 4; ++i) {
+        const bool used = i < norm->planes;
+        n.order[i] = used ? norm->order[i] : 0;
+        n.scale[i] = used ? norm->scale[i] : 0.f;
+        n.bias[i] = used ? norm->bias[i] : 0.f;
+    }
+    int s0, s1;  // the source rows a full frame reads, as run_band
+    iqo_amd::band_src_rows(p, 0, p.dstH, &s0, &s1);
+    const size_t chunk = 65535;  // frames per launch (grid y of the general kernel)
+    for (size_t f0 = 0; f0 < nFrames; f0 += chunk) {
+        const iqo_amd::Io io = make_io(std::min(chunk, nFrames - f0), src + f0 * srcFrameSt, srcSt, srcFrameSt, 0, s1,
+                                       static_cast<uint8_t *>(dst) + f0 * dstFrameSt, dstRowSt, dstFrameSt, 0);
+        const hipError_t e = kernel == IQO_KERNEL_PACKED_TILE
+                                 ? iqo_amd::launch_packed_tile_norm(packed_tile_dev(h), h->channels, io, n, 0, p.dstH, s)
+                                 : iqo_amd::launch_packed_general_norm(general_dev(h), h->channels, io, n, 0, p.dstH, s);
+        if (e == hipErrorInvalidValue)
+            return IQO_HIP_EINVAL;
+        if (e != hipSuccess)
+            return IQO_HIP_EHIP;
+    }
+    return IQO_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1845,6 +1916,16 @@ int iqo_hip_resize_device(iqo_hip_plan *h, size_t nFrames, size_t srcSt, size_t 
         return IQO_HIP_EINVAL;
     return run_band(h, nFrames, 0, static_cast<size_t>(h->p.dstH), 0, srcSt, srcFrameSt, dSrc, dstSt, dstFrameSt,
                     dDst, static_cast<hipStream_t>(stream));
+}
+
+int iqo_hip_resize_device_norm(iqo_hip_plan *h, size_t nFrames, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrc,
+                               const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt, size_t dstFrameSt,
+                               void *dDst, void *stream)
+{
+    if (!h)
+        return IQO_HIP_EINVAL;
+    return run_norm(h, nFrames, srcSt, srcFrameSt, dSrc, norm, dstRowSt, dstPlaneSt, dstFrameSt, dDst,
+                    static_cast<hipStream_t>(stream));
 }
 
 int iqo_hip_band_src_rows(const iqo_hip_plan *h, size_t dstRow0, size_t dstRows, size_t *srcRow0, size_t *srcRows)

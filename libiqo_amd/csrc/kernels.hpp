@@ -58,6 +58,23 @@ hipError_t launch_packed_general(const GeneralDev &g, int channels, const Io &io
 hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd,
                               hipStream_t s);
 
+// --- normalised planar float output of the two packed kernels (their NORM instantiations): plane p
+// of the output is cvt(fl32(fl32((float)u8(order[p]) * scale[p]) + bias[p])) of the byte the U8 path
+// would store, two separately rounded fp32 operations.  Io::dst is the float buffer, Io::dstSt its
+// row stride and Io::dstFrameSt its frame stride, in bytes; plane p starts planeSt * p bytes into the
+// frame.  Every stride and the base are multiples of the element size (checked by the caller).
+struct NormDev {
+    int dtype;                   // 1 fp32, 2 fp16, 3 bf16 (iqo_hip.h IQO_OUT_*)
+    int planes;                  // 1 .. 4
+    int planeSt;                 // bytes, < 2^31
+    int order[4];                // source channel of plane p
+    float scale[4], bias[4];
+};
+hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const Io &io, const NormDev &n, int rowBegin,
+                                      int rowEnd, hipStream_t s);
+hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io, const NormDev &n, int rowBegin,
+                                   int rowEnd, hipStream_t s);
+
 // --- general-ratio wave walker: every wave walks a 256-column strip of one band of rows through
 // a private LDS ring of source rows widened to u16 (plan.hpp WalkTables; 4-byte aligned sources).
 struct WalkDev {

@@ -6,6 +6,10 @@
 //   packed_general_kernel   any shape, any alignment: general_kernel (kernels.hip) per channel
 //   packed_tile_kernel      the hot path: tile_kernel's two passes through LDS over the same
 //                           host tables, with the work rows de-interleaved per channel
+//
+// Both also come with a float epilogue (NORM): instead of the interleaved bytes they store planar
+// fp32 / fp16 / bf16 planes of (byte * scale + bias), channels picked and ordered by the caller
+// (kernels.hpp NormDev).  The bytes are the U8 path's; only the end of the horizontal pass differs.
 #include "kernels_dev.hpp"
 
 namespace iqo_amd {
@@ -115,14 +119,59 @@ __device__ int x_value(const GeneralDev &g, const int *w, int lo, int hi, int4 x
     return u16clamp((sum + (1 << 22)) >> 23);
 }
 
-__global__ __launch_bounds__(256) void packed_general_kernel(PackedGeneralArgs a)
+// ---- float epilogue (NORM)
+
+struct PackedGeneralNormArgs : PackedGeneralArgs {
+    NormDev n;
+};
+
+// fl32(fl32(v * s) + b), two roundings: the empty asm takes the product out of the compiler's
+// sight, so no contraction setting can fuse the pair into an FMA.
+__device__ __forceinline__ float norm_affine(uint32_t v, float s, float b)
 {
-    extern __shared__ __attribute__((aligned(16))) int wrow[];
+    float m = static_cast<float>(v) * s;
+    asm("" : "+v"(m));
+    return m + b;
+}
+
+// round-to-nearest-even conversions (overflow to +-inf), as bit patterns
+__device__ __forceinline__ uint32_t f16_bits(float f)
+{
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));
+}
+__device__ __forceinline__ uint32_t bf16_bits(float f)
+{
+    return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f));
+}
+
+// entry p (wave-uniform, 0 .. 3) of a kernel-argument array: selects, never an indexed copy
+template <typename T>
+__device__ __forceinline__ T pick4(const T (&v)[4], int p)
+{
+    return p == 0 ? v[0] : p == 1 ? v[1] : p == 2 ? v[2] : v[3];
+}
+
+// One workgroup per (output row, frame, channel); NORM: per (output row, frame, output plane),
+// whose channel is order[plane].
+template <bool NORM, typename Args>
+__device__ __forceinline__ void packed_general_body(const Args &a, int *wrow)
+{
     const int y = a.rowBegin + static_cast<int>(blockIdx.x);
-    const int c = static_cast<int>(blockIdx.z);  // the workgroup's channel
+    int c = static_cast<int>(blockIdx.z);  // the workgroup's channel
+    int64_t dstOff = c;
+    float scale = 0.f, bias = 0.f;
+    int dtype = 0;
+    if constexpr (NORM) {
+        const int p = c;
+        c = pick4(a.n.order, p);
+        scale = pick4(a.n.scale, p);
+        bias = pick4(a.n.bias, p);
+        dtype = a.n.dtype;
+        dstOff = static_cast<int64_t>(p) * a.n.planeSt;
+    }
     const uint8_t *srcC = a.io.src + static_cast<int64_t>(blockIdx.y) * a.io.srcFrameSt + c;
     uint8_t *dstRow = a.io.dst + static_cast<int64_t>(blockIdx.y) * a.io.dstFrameSt +
-                      static_cast<int64_t>(y - a.io.dstRow0) * a.io.dstSt + c;
+                      static_cast<int64_t>(y - a.io.dstRow0) * a.io.dstSt + dstOff;
     const int4 yi = a.g.yInfo[y];
     for (int k = 0; k < a.g.nChunks; ++k) {
         const int4 ch = a.g.chunks[k];
@@ -130,10 +179,33 @@ __global__ __launch_bounds__(256) void packed_general_kernel(PackedGeneralArgs a
             wrow[col - ch.z] = y_value(a, srcC, yi, col);
         lds_barrier();
         const int x = ch.x + static_cast<int>(threadIdx.x);
-        if (x < ch.y)
-            dstRow[x * a.C] = static_cast<uint8_t>(x_value(a.g, wrow, ch.z, ch.w, a.g.xInfo[x]));
+        if (x < ch.y) {
+            const int v = x_value(a.g, wrow, ch.z, ch.w, a.g.xInfo[x]);
+            if constexpr (NORM) {
+                const float f = norm_affine(static_cast<uint32_t>(v), scale, bias);
+                uint8_t *o = dstRow + x * (dtype == 1 ? 4 : 2);
+                if (dtype == 1)
+                    *reinterpret_cast<float *>(o) = f;
+                else
+                    *reinterpret_cast<uint16_t *>(o) = static_cast<uint16_t>(dtype == 2 ? f16_bits(f) : bf16_bits(f));
+            } else {
+                dstRow[x * a.C] = static_cast<uint8_t>(v);
+            }
+        }
         lds_barrier();
     }
+}
+
+__global__ __launch_bounds__(256) void packed_general_kernel(PackedGeneralArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) int wrow[];
+    packed_general_body<false>(a, wrow);
+}
+
+__global__ __launch_bounds__(256) void packed_general_norm_kernel(PackedGeneralNormArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) int wrow_n[];
+    packed_general_body<true>(a, wrow_n);
 }
 
 // ================================================================ packed tile kernel
@@ -173,8 +245,17 @@ __device__ __forceinline__ constexpr uint32_t pair_sel(int m, int c)
     return static_cast<uint32_t>(b0 - 4 * k) | (static_cast<uint32_t>(b0 + C - 4 * k) << 16) | 0x0c000c00u;
 }
 
-template <int C, int NP, bool LZ>
-__global__ __launch_bounds__(256) void packed_tile_kernel(PackedTileArgs a)
+struct PackedTileNormArgs : PackedTileArgs {  // dstBytes: the float frame's byte range
+    NormDev n;
+};
+
+// NORM = false is the U8 kernel, argument layout included.  NORM = true ends the horizontal pass
+// with the float epilogue: the thread's 4 pixels of every channel are in registers, so output plane
+// p is 4 consecutive elements, one 16-byte (fp32) or 8-byte (fp16 / bf16) store.  order, scale, bias,
+// the plane stride and the element type are kernel arguments (wave-uniform: SGPRs, a uniform branch
+// around the conversion); every channel is still computed, order / planes only pick what is stored.
+template <int C, int NP, bool LZ, bool NORM>
+__global__ __launch_bounds__(256) void packed_tile_kernel(std::conditional_t<NORM, PackedTileNormArgs, PackedTileArgs> a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t ptile_lds[];
     const TileDev &t = a.t;
@@ -393,6 +474,67 @@ __global__ __launch_bounds__(256) void packed_tile_kernel(PackedTileArgs a)
                 }
             }
         }
+        if constexpr (NORM) {
+            // float epilogue: per output plane the 4 bytes of channel order[p] (uniform selects),
+            // the affine map, one vector store (single elements at the row's right end, or where the
+            // frame, row or plane start is not 4-byte aligned: 2-byte elements only)
+            const NormDev &n = a.n;
+            const bool full = x0 + 4 <= t.dstW;
+            const bool vec = full && dstA4 && !(n.planeSt & 3);
+            const int rowOff = (y0 + j - a.io.dstRow0) * dstSt;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (p >= n.planes)
+                    break;
+                const int oc = n.order[p];
+                float f[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    uint32_t v = bt[k * C];
+#pragma unroll
+                    for (int c = 1; c < C; ++c)
+                        v = oc == c ? bt[k * C + c] : v;
+                    f[k] = norm_affine(v, n.scale[p], n.bias[p]);
+                }
+                if (n.dtype == 1) {
+                    const int off = p * n.planeSt + rowOff + x0 * 4;
+                    if (vec) {
+                        __builtin_amdgcn_raw_buffer_store_b128(
+                            u32x4{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
+                                  __float_as_uint(f[3])},
+                            dstR, off, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (x0 + k < t.dstW)
+                                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(f[k]), dstR, off + 4 * k, 0, 0);
+                    }
+                } else {
+                    uint32_t h[4];
+                    if (n.dtype == 2) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            h[k] = f16_bits(f[k]);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            h[k] = bf16_bits(f[k]);
+                    }
+                    const int off = p * n.planeSt + rowOff + x0 * 2;
+                    if (vec) {
+                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)}, dstR, off,
+                                                              0, 0);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (x0 + k < t.dstW)
+                                __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(h[k]), dstR, off + 2 * k, 0,
+                                                                      0);
+                    }
+                }
+            }
+            continue;
+        }
         // packed after every LDS read of the row is issued (opaque() is a volatile asm, which the
         // reads do not move across), one per dword as in tile_kernel: it keeps the combiner from
         // packing two clamps with v_ashr_pk_u8_i32 and OR-ing into its undefined half (kernels_dev.hpp)
@@ -418,12 +560,12 @@ __global__ __launch_bounds__(256) void packed_tile_kernel(PackedTileArgs a)
     }
 }
 
-template <int C, bool LZ>
+template <int C, bool LZ, bool NORM>
 const void *packed_tile_np(int NP)
 {
 #define IQO_PTILE(NP_)                                                                               \
     case NP_:                                                                                        \
-        return reinterpret_cast<const void *>(packed_tile_kernel<C, NP_, LZ>);
+        return reinterpret_cast<const void *>(packed_tile_kernel<C, NP_, LZ, NORM>);
     switch (NP) {
         IQO_PTILE(1)
         IQO_PTILE(2)
@@ -442,10 +584,27 @@ const void *packed_tile_np(int NP)
 #undef IQO_PTILE
 }
 
-template <int C>
+template <int C, bool NORM>
 const void *packed_tile_fn(bool lanczos, int NP)
 {
-    return lanczos ? packed_tile_np<C, true>(NP) : packed_tile_np<C, false>(NP);
+    return lanczos ? packed_tile_np<C, true, NORM>(NP) : packed_tile_np<C, false, NORM>(NP);
+}
+
+template <bool NORM>
+const void *packed_tile_any(int channels, bool lanczos, int NP)
+{
+    return channels == 2 ? packed_tile_fn<2, NORM>(lanczos, NP)
+                         : channels == 3 ? packed_tile_fn<3, NORM>(lanczos, NP) : packed_tile_fn<4, NORM>(lanczos, NP);
+}
+
+bool norm_ok(const NormDev &n, int channels)
+{
+    if (n.dtype < 1 || n.dtype > 3 || n.planes < 1 || n.planes > 4 || n.planeSt < 0)
+        return false;
+    for (int p = 0; p < n.planes; ++p)
+        if (n.order[p] < 0 || n.order[p] >= channels)
+            return false;
+    return true;
 }
 
 } // namespace
@@ -466,16 +625,38 @@ hipError_t launch_packed_general(const GeneralDev &g, int channels, const Io &io
     return hipGetLastError();
 }
 
-hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
+hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const Io &io, const NormDev &n, int rowBegin,
+                                      int rowEnd, hipStream_t s)
 {
-    if (channels < 2 || channels > 4)
+    if (channels < 2 || channels > 4 || !norm_ok(n, channels))
+        return hipErrorInvalidValue;
+    if (rowEnd <= rowBegin || io.frames <= 0)
+        return hipSuccess;
+    PackedGeneralNormArgs a;
+    static_cast<PackedGeneralArgs &>(a) = PackedGeneralArgs{g, io, rowBegin, channels};
+    a.n = n;
+    dim3 grid(static_cast<unsigned>(rowEnd - rowBegin), static_cast<unsigned>(io.frames), static_cast<unsigned>(n.planes));
+    size_t lds = static_cast<size_t>(g.ldsInts) * sizeof(int);
+    hipLaunchKernelGGL(packed_general_norm_kernel, grid, dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+namespace {
+
+// norm == nullptr: the U8 kernel; else its NORM instantiation on the float frame io.dst
+hipError_t launch_ptile(const TileDev &t, int channels, const Io &io, const NormDev *norm, int rowBegin, int rowEnd,
+                        hipStream_t s)
+{
+    if (channels < 2 || channels > 4 || (norm && !norm_ok(*norm, channels)))
         return hipErrorInvalidValue;
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
     const int rows = rowEnd - rowBegin;
     const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + static_cast<int64_t>(t.srcW) * channels;
-    // stores are relative to dstRow0
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + static_cast<int64_t>(t.dstW) * channels;
+    // stores are relative to dstRow0; a float frame: the last plane's last row
+    const int64_t rowB = norm ? static_cast<int64_t>(t.dstW) * (norm->dtype == 1 ? 4 : 2) : static_cast<int64_t>(t.dstW) * channels;
+    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + rowB +
+                       (norm ? static_cast<int64_t>(norm->planes - 1) * norm->planeSt : 0);
     if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31) || io.srcSt >= (int64_t(1) << 24) ||
         io.dstSt >= (int64_t(1) << 31) || t.srcH >= (1 << 24))
         return hipErrorInvalidValue;
@@ -491,12 +672,30 @@ hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int 
                        4u * static_cast<size_t>(t.CT) + static_cast<size_t>(t.srcRows) * t.spitch;
     if (lds > 64 * 1024)
         return hipErrorInvalidValue;
-    const void *kern = channels == 2 ? packed_tile_fn<2>(t.lanczos, t.NP)
-                                     : channels == 3 ? packed_tile_fn<3>(t.lanczos, t.NP) : packed_tile_fn<4>(t.lanczos, t.NP);
+    const void *kern = norm ? packed_tile_any<true>(channels, t.lanczos, t.NP) : packed_tile_any<false>(channels, t.lanczos, t.NP);
     if (!kern)
         return hipErrorInvalidValue;
+    PackedTileNormArgs an;
     void *args[] = {&a};
+    if (norm) {
+        static_cast<PackedTileArgs &>(an) = a;
+        an.n = *norm;
+        args[0] = &an;
+    }
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>(nTiles)), dim3(256), args, lds, s);
+}
+
+} // namespace
+
+hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
+{
+    return launch_ptile(t, channels, io, nullptr, rowBegin, rowEnd, s);
+}
+
+hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io, const NormDev &n, int rowBegin,
+                                   int rowEnd, hipStream_t s)
+{
+    return launch_ptile(t, channels, io, &n, rowBegin, rowEnd, s);
 }
 
 } // namespace iqo_amd
