@@ -289,6 +289,31 @@ int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, s
 int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,
                                size_t dstH, size_t pxScale);
 
+/* Fused I420 instantiations: the kernel iqo_hip_resize_yuv420_device runs when it resizes the three
+ * planes in one launch.  IQO_YUV420_NONE: plane by plane. */
+enum {
+    IQO_YUV420_NONE = 0,
+    IQO_YUV420_LZ_SYMB10 = 1,  /* Lanczos-3 2:1, Y block-shared symmetric streamer (exactly 4 waves per row) */
+    IQO_YUV420_LZ_SYM10 = 2,   /* Lanczos-3 2:1, Y per-wave symmetric streamer */
+    IQO_YUV420_LZ_SYMB8 = 3,   /* Lanczos-2 2:1, block-shared */
+    IQO_YUV420_LZ_SYM8 = 4,    /* Lanczos-2 2:1, per-wave */
+    IQO_YUV420_AREA44 = 5,     /* Area 4:1 x 4:1 */
+    IQO_YUV420_AREA22 = 6,     /* Area 2:1 x 2:1 */
+    IQO_YUV420_AREA2Y = 7,     /* Area 2:1 columns, any integer row ratio */
+    IQO_YUV420_AREA4Y = 8,
+    IQO_YUV420_AREA8Y = 9,
+    IQO_YUV420_AREA33 = 10,    /* Area 3:1 x 3:1 */
+    IQO_YUV420_AREA3Y = 11,
+    IQO_YUV420_AREA6Y = 12,
+    IQO_YUV420_LIN_D2 = 13,    /* Linear 2:1 */
+    IQO_YUV420_LIN_UP2 = 14    /* Linear 2x */
+};
+
+/* Host-only: the IQO_YUV420_* instantiation an I420 call of this shape runs with default options and a
+ * 16-byte-aligned layout (Y at the given size, U and V at half size; Lanczos chroma: pxScale 2, as
+ * iqo_hip_plan_yuv420).  < 0 for a request iqo_hip_plan_yuv420 rejects. */
+int iqo_host_yuv420_fused(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH);
+
 /* Drop-in classes (iqo::LanczosResizer, AreaResizer, LinearResizer): how many objects this process constructed on the
  * HIP backend, and on the CPU backend (no gfx950 device) plus the resize() calls of HIP objects that fell back to the
  * CPU (a device failure, or a call the HIP path rejected).  IQO_REQUIRE_HIP=1 makes any CPU use abort;

@@ -13,14 +13,18 @@ import ctypes
 import os
 
 __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420Resizer", "Nv12Resizer", "available",
-           "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
-           "ipc_close", "KERNELS", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16"]
+           "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_yuv420_fused", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
+           "ipc_close", "KERNELS", "YUV420_FUSED", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
 LIB_PATH = os.environ.get("LIBIQO_AMD_LIB") or os.path.join(PKG_DIR, "libiqo_hip.so")
 
 KERNELS = {0: "general", 1: "lanczos_stream", 2: "area_int", 3: "linear_up2", 4: "tile", 5: "walk", 6: "lanczos_up2", 7: "lanczos_d32", 8: "area_d32", 9: "lanczos_u23", 10: "linear_u23", 11: "lanczos_d31", 12: "ryx", 13: "ryg", 14: "packed_tile", 15: "packed_general"}
+# IQO_YUV420_*: the fused I420 instantiations (one launch for the three planes)
+YUV420_FUSED = {0: "none", 1: "lz_symb10", 2: "lz_sym10", 3: "lz_symb8", 4: "lz_sym8", 5: "area44", 6: "area22",
+                7: "area2y", 8: "area4y", 9: "area8y", 10: "area33", 11: "area3y", 12: "area6y", 13: "lin_d2",
+                14: "lin_up2"}
 _METHODS = {"lanczos": 0, "area": 1, "linear": 2}
 
 _c_sz = ctypes.c_size_t
@@ -102,6 +106,7 @@ def lib():
                                                _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_resize_yuv420.argtypes = [_vp, _c_sz, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, _vp, _vp]
     L.iqo_host_packed_kernel_for.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz]
+    L.iqo_host_yuv420_fused.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz]
     L.iqo_hip_plan_nv12.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
     L.iqo_hip_nv12_plan_destroy.argtypes = [_vp]
     L.iqo_hip_nv12_plan_destroy.restype = None
@@ -194,6 +199,15 @@ def host_packed_kernel_for(method, degree, channels, srcW, srcH, dstW, dstH, pxS
     if k < 0:
         raise IqoError("invalid packed plan request")
     return KERNELS[k]
+
+
+def host_yuv420_fused(method, degree, srcW, srcH, dstW, dstH):
+    """Fused instantiation (YUV420_FUSED label) an I420 call of this shape runs with default options and an
+    aligned layout, "none" when it goes plane by plane -- host only, no GPU."""
+    k = lib().iqo_host_yuv420_fused(_METHODS[method], degree, srcW, srcH, dstW, dstH)
+    if k < 0:
+        raise IqoError("invalid yuv420 plan request")
+    return YUV420_FUSED[k]
 
 
 def _ptr(obj):

@@ -2720,4 +2720,36 @@ int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t
     return plan_kernel(&h);
 }
 
+int iqo_host_yuv420_fused(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH)
+{
+    static_assert(int(IQO_YUV420_LZ_SYMB10) == int(iqo_amd::kYuvLzSymb10) &&
+                      int(IQO_YUV420_LZ_SYM8) == int(iqo_amd::kYuvLzSym8) &&
+                      int(IQO_YUV420_AREA44) == int(iqo_amd::kYuvArea44) &&
+                      int(IQO_YUV420_LIN_D2) == int(iqo_amd::kYuvLinD2) &&
+                      int(IQO_YUV420_LIN_UP2) == int(iqo_amd::kYuvLinUp2) &&
+                      int(IQO_YUV420_LIN_UP2) + 1 == int(iqo_amd::kYuvFusedCount),
+                  "iqo_hip.h IQO_YUV420_* are kernels.hpp Yuv420Fused");
+    // the requests iqo_hip_plan_yuv420 rejects, and the planes as it builds them
+    if (method < 0 || method > 2 || srcW < 2 || srcH < 2 || dstW < 2 || dstH < 2)
+        return IQO_HIP_EINVAL;
+    const iqo_amd::Method m = static_cast<iqo_amd::Method>(method);
+    iqo_hip_plan hy, hc;  // host halves of the two plans only: no device memory
+    std::string err;
+    if (!iqo_amd::build_plan(m, degree, srcW, srcH, dstW, dstH, 1, &hy.p, &err) ||
+        !iqo_amd::build_plan(m, degree, srcW / 2, srcH / 2, dstW / 2, dstH / 2, m == iqo_amd::kLanczos ? 2 : 1, &hc.p,
+                             &err))
+        return IQO_HIP_EINVAL;
+    // as iqo_hip_resize_yuv420_device with aligned planes: one of the three fusable families on both
+    const int k = hy.p.kernel;
+    if (k != hc.p.kernel)
+        return IQO_YUV420_NONE;
+    if (k == IQO_KERNEL_LANCZOS_STREAM)
+        return iqo_amd::yuv420_fused(lanczos_dev(&hy), lanczos_dev(&hc)).label;
+    if (k == IQO_KERNEL_AREA_INT)
+        return iqo_amd::yuv420_fused(area_dev(&hy), area_dev(&hc)).label;
+    if (k == IQO_KERNEL_LINEAR_UP2)
+        return iqo_amd::yuv420_fused(linear_dev(&hy), linear_dev(&hc)).label;
+    return IQO_YUV420_NONE;
+}
+
 } // extern "C"

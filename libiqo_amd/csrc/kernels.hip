@@ -2947,6 +2947,59 @@ hipError_t launch_fused3(const void *kern, const Prep<A> &y, const Prep<A> &u, c
     return hipLaunchKernel(kern, grid, dim3(static_cast<unsigned>(block)), args, static_cast<size_t>(lds), s);
 }
 
+namespace {
+
+// The Y plane as the fused launch prepares it: one (band, frame) grid for all three planes, so no
+// frame stacking and no XCD tail split (both change the grid)
+LanczosDev yuv420_y_grid(const LanczosDev &ly)
+{
+    LanczosDev l = ly;
+    l.stack = 0;
+    l.tail = -1;
+    return l;
+}
+
+// One tightly packed frame without pointers, for the selection: what it reads of a Prep (kind,
+// block, pd, chunks, np) depends on neither the layout, the batch nor the band count, and
+// an explicit band count keeps prep_lanczos / prep_linear from asking the device for occupancy.
+Io yuv420_pick_io(int srcW, int srcH, int dstW)
+{
+    Io io{};
+    io.srcSt = srcW;
+    io.srcRowEnd = srcH;
+    io.dstSt = dstW;
+    io.frames = 1;
+    return io;
+}
+
+} // namespace
+
+Yuv420Pick yuv420_fused(const LanczosDev &ly, const LanczosDev &lc)
+{
+    Yuv420Pick none, pick;
+    Prep<LanczosArgs> py, pu;
+    if (prep_lanczos(yuv420_y_grid(ly), yuv420_pick_io(ly.srcW, ly.srcH, ly.dstW), 0, ly.dstH, 1, &py) != hipSuccess ||
+        prep_lanczos(lc, yuv420_pick_io(lc.srcW, lc.srcH, lc.dstW), 0, lc.dstH, 1, &pu) != hipSuccess)
+        return none;
+    // chroma: the ring instantiation at the default depth; Y: a symmetric streamer at K = 4 whose
+    // blocks are 256 threads (block-shared only with exactly 4 waves per row)
+    if (pu.kind != 0 || lc.NY != 4 || pu.pd != 3 || py.kind == 0 || py.pd < 3)
+        return none;
+    const bool one = (ly.cy[0] & 0xffffu) == 1u;
+    // (4 waves per row: >= 1488 outputs, so the Y body always takes the line edge scheme)
+    const bool shared = py.kind == 1 && py.block == 256 && py.a.chunks <= 4 && symb_line(py.a.l.dstW, py.a.np);
+    if (ly.NY == 10 && one) {
+        pick.label = shared ? kYuvLzSymb10 : kYuvLzSym10;
+        pick.kern = shared ? reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymbY<10, 12, -5, true, true>, RingChroma>)
+                           : reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymY<10, 12, -5, true>, RingChroma>);
+    } else if (ly.NY == 8) {
+        pick.label = shared ? kYuvLzSymb8 : kYuvLzSym8;
+        pick.kern = shared ? reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymbY<8, 8, -3, false, true>, RingChroma>)
+                           : reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymY<8, 8, -3, false>, RingChroma>);
+    }
+    return pick;
+}
+
 hipError_t launch_yuv420_lanczos(const LanczosDev &ly, const Io &ioY, const LanczosDev &lc, const Io &ioU,
                                  const Io &ioV, hipStream_t s)
 {
@@ -2956,29 +3009,18 @@ hipError_t launch_yuv420_lanczos(const LanczosDev &ly, const Io &ioY, const Lanc
         return hipErrorInvalidValue;
     Prep<LanczosArgs> py, pu, pv;
     hipError_t e;
-    LanczosDev lyGrid = ly;
-    lyGrid.stack = 0;  // the fused launch has one (band, frame) grid for all three planes
-    lyGrid.tail = -1;
+    const LanczosDev lyGrid = yuv420_y_grid(ly);
     if ((e = prep_lanczos(lyGrid, ioY, 0, ly.dstH, 0, &py)) != hipSuccess ||
         (e = prep_lanczos(lc, ioU, 0, lc.dstH, 0, &pu)) != hipSuccess ||
         (e = prep_lanczos(lc, ioV, 0, lc.dstH, 0, &pv)) != hipSuccess)
         return e;
-    // chroma: the ring instantiation at the default depth; Y: a symmetric streamer at K = 4 whose
-    // blocks are 256 threads (block-shared only with exactly 4 waves per row)
-    if (pu.kind != 0 || lc.NY != 4 || pu.pd != 3 || py.kind == 0 || py.pd < 3)
+    const Yuv420Pick pick = yuv420_fused(ly, lc);
+    if (!pick.kern)
         return hipErrorNotSupported;
-    const bool one = (ly.cy[0] & 0xffffu) == 1u;
-    // (4 waves per row: >= 1488 outputs, so the Y body always takes the line edge scheme)
-    const bool shared = py.kind == 1 && py.block == 256 && py.a.chunks <= 4 && symb_line(py.a.l.dstW, py.a.np);
-    const void *kern = nullptr;
-    if (ly.NY == 10 && one)
-        kern = shared ? reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymbY<10, 12, -5, true, true>, RingChroma>)
-                      : reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymY<10, 12, -5, true>, RingChroma>);
-    else if (ly.NY == 8)
-        kern = shared ? reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymbY<8, 8, -3, false, true>, RingChroma>)
-                      : reinterpret_cast<const void *>(yuv420_lanczos_kernel<SymY<8, 8, -3, false>, RingChroma>);
-    else
-        return hipErrorNotSupported;
+    const void *kern = pick.kern;
+    const bool shared = pick.label == kYuvLzSymb10 || pick.label == kYuvLzSymb8;
+    if (shared && (py.kind != 1 || py.block != 256))
+        return hipErrorInvalidValue;  // (cannot happen: the selection prepared the same description)
     if (!shared && py.kind == 1) {
         // re-prepare Y as the per-wave symmetric streamer (256-thread blocks of 4 waves)
         LanczosDev l2 = lyGrid;
@@ -2990,19 +3032,14 @@ hipError_t launch_yuv420_lanczos(const LanczosDev &ly, const Io &ioY, const Lanc
     return launch_fused3(kern, py, pu, pv, 256, shared ? py.lds : 0, s);
 }
 
-hipError_t launch_yuv420_area(const AreaDev &gy, const Io &ioY, const AreaDev &gc, const Io &ioU, const Io &ioV,
-                              hipStream_t s)
+Yuv420Pick yuv420_fused(const AreaDev &gy, const AreaDev &gc)
 {
-    if (ioY.frames <= 0)
-        return hipSuccess;
-    if (ioY.frames != ioU.frames || ioU.frames != ioV.frames)
-        return hipErrorInvalidValue;
-    Prep<AreaArgs> py, pu, pv;
-    (void)prep_area(gy, ioY, 0, gy.dstH, &py);
-    (void)prep_area(gc, ioU, 0, gc.dstH, &pu);
-    (void)prep_area(gc, ioV, 0, gc.dstH, &pv);
-    if (py.kind != pu.kind || (py.kind >= 2 && py.kind != 5 && py.kind != 8 && gy.KY != gc.KY))
-        return hipErrorNotSupported;
+    Yuv420Pick pick;
+    // the same instantiation on both plane kinds, and for the kinds with a run-time row count
+    // (2:y, 4:y, 8:y, 3:y, 6:y) the same count
+    const int ky = area_kind(gy), kc = area_kind(gc);
+    if (ky != kc || (ky >= 2 && ky != 5 && ky != 8 && gy.KY != gc.KY))
+        return pick;
     static const void *const kerns[kAreaKinds] = {
         reinterpret_cast<const void *>(yuv420_plane_kernel<AreaPlane<4, 4>, AreaArgs>),
         reinterpret_cast<const void *>(yuv420_plane_kernel<AreaPlane<2, 2>, AreaArgs>),
@@ -3013,7 +3050,41 @@ hipError_t launch_yuv420_area(const AreaDev &gy, const Io &ioY, const AreaDev &g
         reinterpret_cast<const void *>(yuv420_plane_kernel<AreaPlane<3, 0>, AreaArgs>),
         reinterpret_cast<const void *>(yuv420_plane_kernel<AreaPlane<6, 0>, AreaArgs>),
         reinterpret_cast<const void *>(yuv420_plane_kernel<LinearD2Plane, AreaArgs>)};
-    return launch_fused3(kerns[py.kind], py, pu, pv, 256, 0, s);
+    pick.label = static_cast<Yuv420Fused>(kYuvArea44 + ky);
+    pick.kern = kerns[ky];
+    return pick;
+}
+
+hipError_t launch_yuv420_area(const AreaDev &gy, const Io &ioY, const AreaDev &gc, const Io &ioU, const Io &ioV,
+                              hipStream_t s)
+{
+    if (ioY.frames <= 0)
+        return hipSuccess;
+    if (ioY.frames != ioU.frames || ioU.frames != ioV.frames)
+        return hipErrorInvalidValue;
+    const Yuv420Pick pick = yuv420_fused(gy, gc);
+    if (!pick.kern)
+        return hipErrorNotSupported;
+    Prep<AreaArgs> py, pu, pv;
+    (void)prep_area(gy, ioY, 0, gy.dstH, &py);
+    (void)prep_area(gc, ioU, 0, gc.dstH, &pu);
+    (void)prep_area(gc, ioV, 0, gc.dstH, &pv);
+    return launch_fused3(pick.kern, py, pu, pv, 256, 0, s);
+}
+
+Yuv420Pick yuv420_fused(const LinearDev &gy, const LinearDev &gc)
+{
+    Yuv420Pick none, pick;
+    Prep<LinearArgs> py, pu;
+    if (prep_linear(gy, yuv420_pick_io(gy.srcW, gy.srcH, gy.dstW), 0, gy.dstH, 1, &py) != hipSuccess ||
+        prep_linear(gc, yuv420_pick_io(gc.srcW, gc.srcH, gc.dstW), 0, gc.dstH, 1, &pu) != hipSuccess)
+        return none;
+    // the 2x body with nontemporal stores and 2 rows in flight
+    if (py.kind != 1 || pu.kind != 1 || py.pd != 2 || pu.pd != 2 || gy.F != 2 || gc.F != 2)
+        return none;
+    pick.label = kYuvLinUp2;
+    pick.kern = reinterpret_cast<const void *>(yuv420_plane_kernel<LinearPlane, LinearArgs>);
+    return pick;
 }
 
 hipError_t launch_yuv420_linear(const LinearDev &gy, const Io &ioY, const LinearDev &gc, const Io &ioU,
@@ -3029,10 +3100,10 @@ hipError_t launch_yuv420_linear(const LinearDev &gy, const Io &ioY, const Linear
         (e = prep_linear(gc, ioU, 0, gc.dstH, 0, &pu)) != hipSuccess ||
         (e = prep_linear(gc, ioV, 0, gc.dstH, 0, &pv)) != hipSuccess)
         return e;
-    if (py.kind != 1 || pu.kind != 1 || py.pd != 2 || pu.pd != 2 || gy.F != 2 || gc.F != 2)
+    const Yuv420Pick pick = yuv420_fused(gy, gc);
+    if (!pick.kern)
         return hipErrorNotSupported;
-    return launch_fused3(reinterpret_cast<const void *>(yuv420_plane_kernel<LinearPlane, LinearArgs>), py, pu, pv,
-                         256, 0, s);
+    return launch_fused3(pick.kern, py, pu, pv, 256, 0, s);
 }
 
 } // namespace iqo_amd

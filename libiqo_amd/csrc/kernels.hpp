@@ -309,6 +309,27 @@ hipError_t launch_linear_up2(const LinearDev &l, const Io &io, int rowBegin, int
 // --- YUV 4:2:0: the Y, U and V planes of a batch in ONE launch (grid.z = plane) when both plane
 // kinds have a fused instantiation; hipErrorNotSupported otherwise (launch plane by plane).
 // Frame f of each plane: Io as above; all three Io must hold the same frame count.
+//
+// Which fused instantiation a (Y, chroma) pair of plane descriptions takes: a pure host function
+// (no device query, no launch), one overload per kernel family.  The launchers below run exactly
+// the kernel it returns, and iqo_host_yuv420_fused reports its label.
+enum Yuv420Fused {
+    kYuvNone = 0,                          // no fused instantiation: plane by plane
+    kYuvLzSymb10, kYuvLzSym10,             // Lanczos-3 2:1 Y (10 row taps): block-shared / per-wave symmetric
+    kYuvLzSymb8, kYuvLzSym8,               // Lanczos-2 2:1 Y (8 row taps)
+    kYuvArea44, kYuvArea22, kYuvArea2y, kYuvArea4y, kYuvArea8y, kYuvArea33, kYuvArea3y, kYuvArea6y,
+    kYuvLinD2,                             // Area kinds 0 .. 8 (area_int_kernel<KX, KY or any>; Linear 2:1)
+    kYuvLinUp2,                            // Linear 2x
+    kYuvFusedCount
+};
+struct Yuv420Pick {
+    Yuv420Fused label = kYuvNone;
+    const void *kern = nullptr;            // null exactly when label == kYuvNone
+};
+Yuv420Pick yuv420_fused(const LanczosDev &y, const LanczosDev &c);
+Yuv420Pick yuv420_fused(const AreaDev &y, const AreaDev &c);
+Yuv420Pick yuv420_fused(const LinearDev &y, const LinearDev &c);
+
 hipError_t launch_yuv420_lanczos(const LanczosDev &y, const Io &ioY, const LanczosDev &c, const Io &ioU,
                                  const Io &ioV, hipStream_t s);
 hipError_t launch_yuv420_area(const AreaDev &y, const Io &ioY, const AreaDev &c, const Io &ioU, const Io &ioV,
