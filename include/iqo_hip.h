@@ -284,6 +284,12 @@ int iqo_host_band_src_rows(int method, unsigned degree, size_t srcW, size_t srcH
 int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                         size_t pxScale);
 
+/* as iqo_host_kernel_for, for a source / destination whose base, row stride and frame stride
+ * are multiples of srcAlign / dstAlign bytes (powers of two, 1..16) and of nothing larger;
+ * IQO_HIP_EINVAL for any other alignment value */
+int iqo_host_kernel_for_layout(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW,
+                               size_t dstH, size_t pxScale, size_t srcAlign, size_t dstAlign);
+
 /* Host-only: the same for a packed plan of `channels` bytes per pixel (IQO_KERNEL_PACKED_TILE or
  * IQO_KERNEL_PACKED_GENERAL; channels == 1: iqo_host_kernel_for).  < 0 for channels outside 1..4. */
 int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,

@@ -95,6 +95,7 @@ def lib():
                                   ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                   ctypes.POINTER(ctypes.c_int32), _c_sz]
     L.iqo_host_kernel_for.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz]
+    L.iqo_host_kernel_for_layout.argtypes = L.iqo_host_kernel_for.argtypes + [_c_sz, _c_sz]
     L.iqo_host_band_src_rows.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz,
                                          ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]
     L.iqo_hip_plan_yuv420.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
@@ -186,8 +187,12 @@ def host_band_src_rows(method, degree, srcW, srcH, dstW, dstH, pxScale, dstRow0,
     return a.value, b.value
 
 
-def host_kernel_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1):
-    k = lib().iqo_host_kernel_for(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale)
+def host_kernel_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1, src_align=16, dst_align=16):
+    """Kernel family of a full-frame device call whose source / destination base and strides are
+    multiples of src_align / dst_align bytes (powers of two, 1..16) and of nothing larger -- host
+    only, no GPU."""
+    k = lib().iqo_host_kernel_for_layout(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale, src_align,
+                                         dst_align)
     if k < 0:
         raise IqoError("invalid plan request")
     return KERNELS[k]

@@ -9,10 +9,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <condition_variable>
 #include <mutex>
 #include <new>
@@ -27,7 +29,13 @@ using iqo_amd::AxisPlan;
 using iqo_amd::CoordInfo;
 using iqo_amd::Plan;
 
+struct iqo_hip_plan;
+namespace {
+void reset_options(iqo_hip_plan *h);
+}
+
 struct iqo_hip_plan {
+    iqo_hip_plan() { reset_options(this); }  // the option members below: defaults from kOptions
     Plan p;
     int device = 0;
     // plan-cache key (make_plan): identical requests reuse a destroyed plan's tables
@@ -52,31 +60,19 @@ struct iqo_hip_plan {
     int4 *dX = nullptr, *dY = nullptr, *dChunks = nullptr;
     int *dTabX = nullptr, *dTabY = nullptr;
     int nChunks = 0, ldsInts = 0;
-    bool forceGeneral = false;
-    int bands = 0;
-    int debugFlags = 0;
+    // Options (iqo_hip_plan_set_option): what each one does, its accepted values and its default are
+    // its row of kOptions below; reset_options sets every one of them.
+    int forceGeneral, bands, hostStage, tail, rounds, ryxSplit, ryxAdj, ryxCpt, ryxUc, rygCpt, stack, prefetch,
+        streamVariant, lanes, ratioPrefetch, chunkFrames;
+    int useTile, useWalk, useUp2, useD32, useD31, useA32, useU23, useL23, useRyx, useRyg, useRyu, useRyuRun;
+    int debugFlags;  // variant builds only (timing experiments); 0 otherwise
 #ifdef IQO_VARIANT_DEBUG
-    uint64_t traceAddr = 0;  // variant builds: workgroup timeline buffer of the block-shared streamer
+    uint64_t traceAddr;  // variant builds: workgroup timeline buffer of the block-shared streamer
 #endif
-    int prefetch = 3;  // streamer prefetch: ring streamer depth 1..3 / symmetric LDS ring K = 3..5
-    int streamVariant = 0;  // 0: block-shared symmetric streamer where eligible, 1: accumulator-ring
-                            // streamer, 2: per-wave symmetric streamer (all bit-identical)
-    int rounds = 0;         // block-shared streamer: target rounds for the auto band count (0 = 6, -1 = makespan model)
-    int tail = 0;           // block-shared streamer: short bands for each XCD's last frame (0 auto, -1 off, n bands)
-    int stack = 1;          // block-shared streamer: narrow frames side by side in one workgroup (speed only)
-    int ryxAdj = 1;         // ratio-Y kernel: adjacent column pairs per thread where they fit (speed only)
-    int ryxCpt = 1;         // ratio-Y kernel: 4 output columns per thread at the Lanczos 4:9 upscales (speed only)
-    int ryxSplit = 1;       // ratio-Y kernel column parts (speed only; option ryx_split)
-    int rygCpt = 0;         // general-row kernel on rows of > 1024 outputs: output columns per thread (0 = auto)
-    int ryxUc = 1;          // ratio-Y kernel: uniform column coefficients as scalars where every column has the same
-    int lanes = 0;          // symmetric streamer producing lanes per wave (0 = auto)
-    int ratioPrefetch = 0;  // exact-ratio kernels: row groups loaded ahead (0 = kernel default)
-    int chunkFrames = 0;    // frames per launch (0 = up to 65535)
     // separable tile kernel (shapes without a specialised kernel; plan option "tile" = 0 turns
     // it off, leaving general_kernel)
     iqo_amd::TileTables tt;
     int tileTH0 = 0, tileSrcRows0 = 0;  // the auto tile height (option "tile_rows" changes it; reset_options restores it)
-    bool useTile = true;
     int4 *dTRows = nullptr, *dTSpans = nullptr;
     int2 *dTCols = nullptr;
     uint2 *dTRowTap = nullptr;
@@ -85,10 +81,8 @@ struct iqo_hip_plan {
     int tileNQp = 0;
     // general-ratio wave walker (plan.hpp WalkTables; option "walk" = 0 keeps tile_kernel)
     iqo_amd::WalkTables wt;
-    bool useWalk = true;
     // exact 2x Lanczos upscale kernel, every row and column in-kernel (option "up2" = 0: walker only)
     iqo_amd::Up2Tables ut;
-    bool useUp2 = true;
     // exact 3:2 Lanczos-3 downscale kernel on the main rows (option "d32" = 0: walker only)
     iqo_amd::D32Tables dt;
     iqo_amd::D31Tables t31;
@@ -96,28 +90,17 @@ struct iqo_hip_plan {
     uint32_t *dRyxRowCoef = nullptr, *dRyxColCoef = nullptr;
     int4 *dRyxCols = nullptr;
     int4 *dRyxRowRec = nullptr;  // general-row tables (ryx.general: the ryg kernel, kernels.hpp RygDev)
-    bool useRyg = true;
     // general upscale rows by window position (kernels.hip ryu_kernel): records, first window start
     int4 *dRyuPos = nullptr;
     int ryuBase = 0;
     bool hasRyu = false;  // the table exists (every window position holds 1 or 2 rows)
-    bool useRyu = true;   // option "ryu" = 0: ryg_kernel's NL = 1 mode instead (A/B)
     uint32_t *dRyuRun = nullptr;  // run-mode column table (plan.hpp colRun), when it exists
-    bool useRyuRun = true;        // option "ryu_run" = 0: per-column mode (A/B)
-    int hostStage = 0;  // host-pointer path, frames >= 4 MiB: 0 the runtime's own pageable copies, 1 our pinned
-                        // staging pipeline (host_pipeline), for A/B
-    bool useD32 = true;
-    bool useD31 = true;
-    bool useRyx = true;
     // exact 2:3 Linear upscale kernel (option "l23" = 0: walker only)
     iqo_amd::L23Tables lt;
-    bool useL23 = true;
     // exact 2:3 Lanczos-3 upscale kernel (option "u23" = 0: walker only)
     iqo_amd::U23Tables vt;
-    bool useU23 = true;
     // exact 3:2 Area downscale kernel (option "a32" = 0: walker only)
     iqo_amd::A32Tables at;
-    bool useA32 = true;
     int4 *dWSpans = nullptr;
     int4 *dWSegs = nullptr;
     uint32_t *dWRowTap = nullptr;
@@ -416,7 +399,7 @@ bool is_gfx950(int dev)
 }
 
 template <typename T>
-int upload(iqo_hip_plan *h, T **dptr, const T *src, size_t n)
+void upload(iqo_hip_plan *h, T **dptr, const T *src, size_t n)
 {
     // stage into the plan's blob (256-B aligned sections); ensure_tables uploads it on first use
     const size_t off = (h->blob.size() + 255) & ~static_cast<size_t>(255);
@@ -426,7 +409,6 @@ int upload(iqo_hip_plan *h, T **dptr, const T *src, size_t n)
         std::memcpy(h->blob.data() + off, src, n * sizeof(T));
     h->blobPtrs.emplace_back(reinterpret_cast<void **>(dptr), off);
     *dptr = nullptr;
-    return IQO_HIP_OK;
 }
 
 // One allocation + one copy of every staged table, then the table pointers point into it.
@@ -509,31 +491,20 @@ std::vector<int4> coord_records(const AxisPlan &a)
     return v;
 }
 
-// Upload the separable tile kernel's tables (TileRec / TileCol have the int4 / int2 layout).
 iqo_amd::RyxDev ryx_dev(const iqo_hip_plan *h);
 
-// Window-position records of a general upscale (plan.cpp build_ryu_positions, kernels.hip
-// ryu_kernel); none when a position holds more than 2 rows: ryg_kernel's NL = 1 mode runs the plan.
-int ryu_positions(iqo_hip_plan *h)
+// Every host table of a plan, in dependency order.  Host memory only: make_plan stages the result
+// for upload (stage_*), the iqo_host_* queries stop here.
+void build_host_tables(iqo_hip_plan *h)
 {
-    h->hasRyu = iqo_amd::build_ryu_positions(h->p.dstH, &h->ryx);
-    if (!h->hasRyu)
-        return IQO_HIP_OK;
-    static_assert(iqo_amd::kRyuPosPad >= 3, "ryu_kernel reads the records up to a band's last position + 2");
-    static_assert(iqo_amd::kRyuRec == 8, "ryu_kernel reads 8-int position records");
-    h->ryuBase = h->ryx.posBase;
-    int rc = upload(h, &h->dRyuPos, reinterpret_cast<const int4 *>(h->ryx.posRec.data()), h->ryx.posRec.size() / 4);
-    if (!rc && iqo_amd::build_ryu_runs(h->p.dstW, &h->ryx))
-        rc = upload(h, &h->dRyuRun, h->ryx.colRun.data(), h->ryx.colRun.size());
-    return rc;
-}
-
-// Tables of the exact-ratio kernels (most take their coefficients as kernel arguments; ryx has
-// device tables).  Built whether or not the tile tables exist: ryx also serves shapes whose taps
-// exceed the tile kernel's (Lanczos-8/9 2:1).
-int upload_exact(iqo_hip_plan *h)
-{
-    // exact-ratio kernels (no device tables: their coefficients are kernel arguments)
+    iqo_amd::build_tile_tables(h->p, &h->tt);
+    h->tileTH0 = h->tt.TH;
+    h->tileSrcRows0 = h->tt.srcRows;
+    if (h->tt.ok)
+        iqo_amd::build_walk_tables(h->p, h->tt, &h->wt);
+    // Tables of the exact-ratio kernels (most take their coefficients as kernel arguments; ryx has
+    // device tables).  Built whether or not the tile tables exist: ryx also serves shapes whose taps
+    // exceed the tile kernel's (Lanczos-8/9 2:1).
     iqo_amd::build_up2(h->p, h->wt, &h->ut);
     iqo_amd::build_d32(h->p, h->wt, &h->dt);
     iqo_amd::build_d31(h->p, &h->t31);
@@ -546,7 +517,48 @@ int upload_exact(iqo_hip_plan *h)
         iqo_amd::build_ryg(h->p, &h->ryx);  // general rows (no exact P:Q)
     if (h->ryx.ok && ryx_dev(h).parts == 0)
         h->ryx = iqo_amd::RyxTables();  // no column split fits the workgroup limits
-    if (h->ryx.ok && h->ryx.general) {
+    // Window-position records of a general upscale (plan.cpp build_ryu_positions, kernels.hip
+    // ryu_kernel); none when a position holds more than 2 rows: ryg_kernel's NL = 1 mode runs the
+    // plan.  With them the run-mode column table (runPairs > 0), where one exists.
+    if (h->ryx.ok && h->ryx.general && h->ryx.rowLoads == 1)
+        h->hasRyu = iqo_amd::build_ryu_positions(h->p.dstH, &h->ryx);
+    if (h->hasRyu) {
+        h->ryuBase = h->ryx.posBase;
+        iqo_amd::build_ryu_runs(h->p.dstW, &h->ryx);
+    }
+    iqo_amd::build_a32(h->p, &h->at);
+    iqo_amd::build_u23(h->p, &h->vt);
+    iqo_amd::build_l23(h->p, &h->lt);
+    // packed plans: the packed tiling over the tile tables
+    if (h->channels > 1)
+        iqo_amd::build_packed_tables(h->p, h->tt, h->channels, &h->pk);
+}
+
+void stage_walk(iqo_hip_plan *h)
+{
+    std::vector<int4> ws(h->wt.spans.size());
+    for (size_t i = 0; i < ws.size(); ++i)
+        ws[i] = make_int4(h->wt.spans[i].lo8, h->wt.spans[i].units, h->wt.spans[i].interior, 0);
+    std::vector<int4> sg(2 * h->wt.segs.size());
+    for (size_t i = 0; i < h->wt.segs.size(); ++i) {
+        const iqo_amd::WalkSeg &g = h->wt.segs[i];
+        sg[2 * i] = make_int4(g.first, g.slotOff, g.border, g.firstD);
+        sg[2 * i + 1] = make_int4(static_cast<int>(g.yM), g.yS, g.yNeg, 0);
+    }
+    std::vector<int4> wr(h->wt.rows.size());
+    for (size_t i = 0; i < wr.size(); ++i)
+        wr[i] = make_int4(h->wt.rows[i].lo, h->wt.rows[i].hi, h->wt.rows[i].hiSlot, h->wt.rows[i].deno);
+    upload(h, &h->dWSpans, ws.data(), ws.size());
+    upload(h, &h->dWRows, wr.data(), wr.size());
+    upload(h, &h->dWRowTap, h->wt.rowTap.data(), h->wt.rowTap.size());
+    upload(h, &h->dWSegs, sg.data(), sg.size());
+}
+
+// The ratio-Y / general-row kernels' tables (the other exact-ratio kernels have no device tables:
+// their coefficients are kernel arguments).
+void stage_ryx(iqo_hip_plan *h)
+{
+    if (h->ryx.general) {
         // ryg_kernel reads the records of rows up to y1 - 1 + kRygPD + 1 unclamped (its FIFO look-ahead
         // and the next row's record): build_ryg's padding must cover them
         static_assert(iqo_amd::kRygRecPad >= iqo_amd::kRygPD + 2, "ryg row records: padding below the look-ahead");
@@ -555,38 +567,27 @@ int upload_exact(iqo_hip_plan *h)
             const size_t ia = std::min(rr.size() - 1, i + iqo_amd::kRygPD - 1);  // (rows past the end repeat)
             rr[i] = make_int4(h->ryx.rowRec[2 * i], h->ryx.rowRec[2 * i + 1], h->ryx.rowRec[2 * ia], 0);
         }
-        const int rc2 = upload(h, &h->dRyxRowRec, rr.data(), rr.size());
-        if (rc2)
-            return rc2;
-        if (h->ryx.rowLoads == 1) {
-            const int rc3 = ryu_positions(h);
-            if (rc3)
-                return rc3;
-        }
+        upload(h, &h->dRyxRowRec, rr.data(), rr.size());
     }
-    if (h->ryx.ok) {
-        std::vector<int4> rc(h->ryx.cols.size() / 4);
-        for (size_t i = 0; i < rc.size(); ++i)
-            rc[i] = make_int4(h->ryx.cols[4 * i], h->ryx.cols[4 * i + 1], h->ryx.cols[4 * i + 2], 0);
-        int rc2 = upload(h, &h->dRyxRowCoef, h->ryx.rowCoef.data(), h->ryx.rowCoef.size());
-        if (!rc2)
-            rc2 = upload(h, &h->dRyxColCoef, h->ryx.colCoef.data(), h->ryx.colCoef.size());
-        if (!rc2)
-            rc2 = upload(h, &h->dRyxCols, rc.data(), rc.size());
-        if (rc2)
-            return rc2;
+    if (h->hasRyu) {
+        static_assert(iqo_amd::kRyuPosPad >= 3, "ryu_kernel reads the records up to a band's last position + 2");
+        static_assert(iqo_amd::kRyuRec == 8, "ryu_kernel reads 8-int position records");
+        upload(h, &h->dRyuPos, reinterpret_cast<const int4 *>(h->ryx.posRec.data()), h->ryx.posRec.size() / 4);
+        if (h->ryx.runPairs > 0)
+            upload(h, &h->dRyuRun, h->ryx.colRun.data(), h->ryx.colRun.size());
     }
-    iqo_amd::build_a32(h->p, &h->at);
-    iqo_amd::build_u23(h->p, &h->vt);
-    iqo_amd::build_l23(h->p, &h->lt);
-    return IQO_HIP_OK;
+    std::vector<int4> rc(h->ryx.cols.size() / 4);
+    for (size_t i = 0; i < rc.size(); ++i)
+        rc[i] = make_int4(h->ryx.cols[4 * i], h->ryx.cols[4 * i + 1], h->ryx.cols[4 * i + 2], 0);
+    upload(h, &h->dRyxRowCoef, h->ryx.rowCoef.data(), h->ryx.rowCoef.size());
+    upload(h, &h->dRyxColCoef, h->ryx.colCoef.data(), h->ryx.colCoef.size());
+    upload(h, &h->dRyxCols, rc.data(), rc.size());
 }
 
-int upload_tile(iqo_hip_plan *h)
+// The separable tile kernel's tables (TileRec / TileCol have the int4 / int2 layout).
+void stage_tile(iqo_hip_plan *h)
 {
     const iqo_amd::TileTables &t = h->tt;
-    if (!t.ok)
-        return upload_exact(h);
     std::vector<int4> rows(t.rows.size()), spans(t.spans.size());
     std::vector<int2> cols(t.cols.size());
     for (size_t i = 0; i < rows.size(); ++i)
@@ -614,33 +615,6 @@ int upload_tile(iqo_hip_plan *h)
                 coefT[(static_cast<size_t>(p) * 4 + k) * nQp + Q] = in ? t.colCoef[static_cast<size_t>(x) * t.NP + p] : 0u;
         }
     h->tileNQp = nQp;
-    iqo_amd::build_walk_tables(h->p, t, &h->wt);
-    if (h->wt.ok) {
-        std::vector<int4> ws(h->wt.spans.size());
-        for (size_t i = 0; i < ws.size(); ++i)
-            ws[i] = make_int4(h->wt.spans[i].lo8, h->wt.spans[i].units, h->wt.spans[i].interior, 0);
-        std::vector<int4> sg(2 * h->wt.segs.size());
-        for (size_t i = 0; i < h->wt.segs.size(); ++i) {
-            const iqo_amd::WalkSeg &g = h->wt.segs[i];
-            sg[2 * i] = make_int4(g.first, g.slotOff, g.border, g.firstD);
-            sg[2 * i + 1] = make_int4(static_cast<int>(g.yM), g.yS, g.yNeg, 0);
-        }
-        std::vector<int4> wr(h->wt.rows.size());
-        for (size_t i = 0; i < wr.size(); ++i)
-            wr[i] = make_int4(h->wt.rows[i].lo, h->wt.rows[i].hi, h->wt.rows[i].hiSlot, h->wt.rows[i].deno);
-        const std::vector<uint32_t> &wt = h->wt.rowTap;
-        int rc = upload(h, &h->dWSpans, ws.data(), ws.size());
-        if (!rc)
-            rc = upload(h, &h->dWRows, wr.data(), wr.size());
-        if (!rc)
-            rc = upload(h, &h->dWRowTap, wt.data(), wt.size());
-        if (!rc)
-            rc = upload(h, &h->dWSegs, sg.data(), sg.size());
-        if (rc)
-            return rc;
-    }
-    if (int rc = upload_exact(h))
-        return rc;
     // per (row, tap): coefficient splat and the clamped source row it reads
     std::vector<uint2> rowTap(t.rowCoef.size());
     for (size_t y = 0; y < t.rows.size(); ++y)
@@ -649,54 +623,101 @@ int upload_tile(iqo_hip_plan *h)
             const int row = std::min(std::max(r.start + i, r.lo), r.hi);
             rowTap[y * t.nYp + i] = make_uint2(t.rowCoef[y * t.nYp + i], static_cast<uint32_t>(row));
         }
-    int rc;
-    if ((rc = upload(h, &h->dTRows, rows.data(), rows.size())) || (rc = upload(h, &h->dTCols, cols.data(), cols.size())) ||
-        (rc = upload(h, &h->dTSpans, spans.data(), spans.size())) ||
-        (rc = upload(h, &h->dTRowTap, rowTap.data(), rowTap.size())) ||
-        (rc = upload(h, &h->dTColCoef, coefT.data(), coefT.size())) || (rc = upload(h, &h->dTColA, colA.data(), colA.size())))
-        return rc;
-    return IQO_HIP_OK;
+    upload(h, &h->dTRows, rows.data(), rows.size());
+    upload(h, &h->dTCols, cols.data(), cols.size());
+    upload(h, &h->dTSpans, spans.data(), spans.size());
+    upload(h, &h->dTRowTap, rowTap.data(), rowTap.size());
+    upload(h, &h->dTColCoef, coefT.data(), coefT.size());
+    upload(h, &h->dTColA, colA.data(), colA.size());
 }
 
-// Packed plans: the packed tiling over the tile tables upload_tile staged (its column coefficients
+// Packed plans: the packed tiling over the tile tables stage_tile staged (its column coefficients
 // are laid out over the planar tiles' padded width, which covers the narrower packed tiles').
-int upload_packed(iqo_hip_plan *h)
+void stage_packed(iqo_hip_plan *h)
 {
-    if (h->channels == 1)
-        return IQO_HIP_OK;
-    iqo_amd::build_packed_tables(h->p, h->tt, h->channels, &h->pk);
-    if (!h->pk.ok)
-        return IQO_HIP_OK;
     std::vector<int4> spans(h->pk.spans.size());
     for (size_t i = 0; i < spans.size(); ++i)
         spans[i] = make_int4(h->pk.spans[i].lo8, h->pk.spans[i].groups, h->pk.spans[i].border, 0);
-    return upload(h, &h->dPSpans, spans.data(), spans.size());
+    upload(h, &h->dPSpans, spans.data(), spans.size());
 }
+
+// The options of iqo_hip_plan_set_option, one row each: name, member, accepted values lo .. hi,
+// default, and whether a caller of the public ABI may set it (the others are the A/B keys: kernel
+// family switches and band / lane / prefetch / column-split schedules, every one speed-only,
+// accepted only with IQO_HIP_TUNING=1, include/iqo_hip.h).  The tile height and the variant builds'
+// two debug keys are no plain integers: they have handlers of their own in iqo_hip_plan_set_option.
+struct Option {
+    const char *name;
+    int iqo_hip_plan::*member;
+    long lo, hi;  // lo > hi (onoff): any value, stored as value != 0
+    int def;
+    bool pub;
+};
+using PlanT = iqo_hip_plan;
+constexpr long kMax = std::numeric_limits<long>::max();
+constexpr Option onoff(const char *name, int PlanT::*member, int def, bool pub) { return {name, member, 1, 0, def, pub}; }
+constexpr Option kOptions[] = {
+    onoff("force_general", &PlanT::forceGeneral, 0, true),  // general_kernel whatever the shape
+    {"bands", &PlanT::bands, 0, kMax, 0, true},                    // bands per frame of the banded kernels (0 = auto)
+    // host-pointer path of large frames (>= 4 MiB; speed only): 0 the runtime's pageable copies, 1 the
+    // pinned staging pipeline (host_pipeline), for A/B
+    {"host_stage", &PlanT::hostStage, 0, 1, 0, true},
+    // block-shared Lanczos streamer: short bands for each XCD's last frame (0 auto, -1 off, n bands; speed only)
+    {"tail", &PlanT::tail, -1, 4096, 0, false},
+    // block-shared Lanczos streamer: target rounds for the auto band count (0 = 6, -1 = makespan model; speed only)
+    {"rounds", &PlanT::rounds, -1, 64, 0, false},
+    // ratio-Y kernel column parts (speed only): 0 one 8-wave workgroup per row where it fits, 1 default,
+    // 2 / 3 parts of 2 / 1 waves, 4 the general rows' round-6 rule before one-wave parts
+    {"ryx_split", &PlanT::ryxSplit, 0, 4, 1, false},
+    // ratio-Y kernel adjacent column pairs per thread (speed only): 0 off, 1 where they fit
+    {"ryx_adj", &PlanT::ryxAdj, 0, 1, 1, false},
+    // ratio-Y upscales: 0 two output columns per thread, 1 four at the Lanczos 4:9 upscales (speed only)
+    {"ryx_cpt", &PlanT::ryxCpt, 0, 1, 1, false},
+    // ratio-Y kernel: uniform column coefficients as scalars where every column has the same; 0 per-lane
+    // column coefficients everywhere (speed only)
+    onoff("ryx_uc", &PlanT::ryxUc, 1, false),
+    // general-row kernel, rows of > 1024 outputs: output columns per thread (0 auto, 2, 3, 4 -- not 1,
+    // iqo_hip_plan_set_option; speed only)
+    {"ryg_cpt", &PlanT::rygCpt, 0, 4, 0, false},
+    // block-shared streamer, narrow frames side by side in one workgroup (speed only): 0 off, 1 where a
+    // frame fills <= 1/2 wave, 2 from 2 frames
+    {"stack", &PlanT::stack, 0, 2, 1, false},
+    // Lanczos streamer prefetch depth (rows): ring streamer depth 1..3 / symmetric LDS ring K = 3..5
+    {"prefetch", &PlanT::prefetch, 1, 4, 3, false},
+    // A/B: 0 block-shared symmetric streamer where eligible, 1 accumulator-ring streamer, 2 per-wave
+    // symmetric streamer (all bit-identical)
+    {"stream_variant", &PlanT::streamVariant, 0, 2, 0, false},
+    {"lanes", &PlanT::lanes, 0, 62, 0, false},  // Lanczos / Linear streamers: producing lanes per wave (0 = auto)
+    // exact-ratio kernels: row groups loaded ahead (0 = kernel default; speed only); a depth the plan's
+    // kernel does not instantiate fails the resize call with IQO_HIP_EINVAL
+    {"ratio_prefetch", &PlanT::ratioPrefetch, 0, 8, 0, false},
+    {"chunk_frames", &PlanT::chunkFrames, 0, kMax, 0, false},  // frames per launch (0 = up to 65535)
+    onoff("tile", &PlanT::useTile, 1, false),  // 0: shapes without a specialised kernel use general_kernel
+    onoff("walk", &PlanT::useWalk, 1, false),  // 0: general ratios use tile_kernel instead of the wave walker
+    onoff("up2", &PlanT::useUp2, 1, false),    // 0: exact 2x Lanczos upscales use the wave walker alone
+    onoff("d32", &PlanT::useD32, 1, false),    // 0: exact 3:2 Lanczos-3 downscales use the wave walker alone
+    onoff("d31", &PlanT::useD31, 1, false),    // 0: exact 3:1 Lanczos downscales use the general kernels
+    onoff("a32", &PlanT::useA32, 1, false),    // 0: exact 3:2 Area downscales use the wave walker alone
+    onoff("u23", &PlanT::useU23, 1, false),    // 0: exact 2:3 Lanczos-3 upscales use the wave walker alone
+    onoff("l23", &PlanT::useL23, 1, false),    // 0: exact 2:3 Linear upscales use the wave walker alone
+    onoff("ryx", &PlanT::useRyx, 1, false),    // 0: exact-vertical-ratio downscales use the general kernels
+    // 0: general-row downscales (1 .. 2 : 1) use the wave walker / tile kernel
+    onoff("ryg", &PlanT::useRyg, 1, false),
+    // 0: general upscale rows walk output rows (ryg_kernel's NL = 1 mode), not window positions (A/B)
+    onoff("ryu", &PlanT::useRyu, 1, false),
+    // 0: general upscale rows read each column's window separately (per-column mode, A/B)
+    onoff("ryu_run", &PlanT::useRyuRun, 1, false),
+};
 
 // Every option iqo_hip_plan_set_option can change, back to its default.
 void reset_options(iqo_hip_plan *h)
 {
-    h->forceGeneral = false;
-    h->bands = 0;
+    for (const Option &o : kOptions)
+        h->*o.member = o.def;
     h->debugFlags = 0;
-    h->prefetch = 3;
-    h->streamVariant = 0;
-    h->rounds = 0;
-    h->tail = 0;
-    h->stack = 1;
-    h->ryxSplit = 1;
-    h->rygCpt = 0;
-    h->ryxUc = 1;
-    h->ryxAdj = 1;
-    h->ryxCpt = 1;
-    h->lanes = 0;
-    h->ratioPrefetch = 0;
-    h->chunkFrames = 0;
-    h->useTile = h->useWalk = h->useUp2 = h->useD32 = h->useD31 = h->useRyx = h->useL23 = h->useU23 = h->useA32 = true;
-    h->useRyg = true;
-    h->useRyu = true;
-    h->useRyuRun = true;
-    h->hostStage = 0;
+#ifdef IQO_VARIANT_DEBUG
+    h->traceAddr = 0;
+#endif
     if (h->tt.ok) {  // option "tile_rows"
         h->tt.TH = h->tileTH0;
         h->tt.srcRows = h->tileSrcRows0;
@@ -786,28 +807,27 @@ int make_plan(iqo_amd::Method m, unsigned degree, size_t sw, size_t sh, size_t d
         return rc;
     }
     h->nChunks = static_cast<int>(chunks.size());
-    iqo_amd::build_tile_tables(h->p, &h->tt);
-    h->tileTH0 = h->tt.TH;
-    h->tileSrcRows0 = h->tt.srcRows;
+    build_host_tables(h);
+    // stage what has device tables, in the blob's section order
     std::vector<int4> xr = coord_records(h->p.x), yr = coord_records(h->p.y);
-    if ((rc = upload(h, &h->dX, xr.data(), xr.size())) || (rc = upload(h, &h->dY, yr.data(), yr.size())) ||
-        (rc = upload(h, &h->dTabX, h->p.x.table.data(), h->p.x.table.size())) ||
-        (rc = upload(h, &h->dTabY, h->p.y.table.data(), h->p.y.table.size())) ||
-        (rc = upload(h, &h->dChunks, chunks.data(), chunks.size())) || (rc = upload_tile(h)) ||
-        (rc = upload_packed(h))) {
-        free_plan(h);
-        return rc;
-    }
+    upload(h, &h->dX, xr.data(), xr.size());
+    upload(h, &h->dY, yr.data(), yr.size());
+    upload(h, &h->dTabX, h->p.x.table.data(), h->p.x.table.size());
+    upload(h, &h->dTabY, h->p.y.table.data(), h->p.y.table.size());
+    upload(h, &h->dChunks, chunks.data(), chunks.size());
+    if (h->wt.ok)
+        stage_walk(h);
+    if (h->ryx.ok)
+        stage_ryx(h);
+    if (h->tt.ok)
+        stage_tile(h);
+    if (h->pk.ok)
+        stage_packed(h);
     *out = h;
     return IQO_HIP_OK;
 }
 
 uint32_t pair16(int lo, int hi) { return (static_cast<uint32_t>(lo) & 0xffffu) | (static_cast<uint32_t>(hi) << 16); }
-
-bool aligned(const void *p, size_t a, size_t st, size_t fst)
-{
-    return (reinterpret_cast<uintptr_t>(p) % a) == 0 && (st % a) == 0 && (fst % a) == 0;
-}
 
 // Device-side views of a plan for each kernel family (kernel arguments, no device memory).
 iqo_amd::LanczosDev lanczos_dev(const iqo_hip_plan *h)
@@ -1357,94 +1377,111 @@ bool walk_beats_ryg(const iqo_hip_plan *h)
     return p.method != iqo_amd::kLanczos && (5 * p.srcH < 7 * p.dstH || p.y.phases <= 2);
 }
 
-// The kernel family a full-frame call with aligned pointers and strides runs.
-int plan_kernel(const iqo_hip_plan *h)
+// What a call's pointers and strides offer the kernels' vector accesses: base, row stride and frame
+// stride OR-ed into one word per side.  All three are multiples of a power of two a exactly when the
+// word's low bits a - 1 are zero.
+struct Layout {
+    uintptr_t src, dst;
+};
+constexpr Layout kAlignedLayout{0, 0};
+
+Layout layout_of(const void *src, size_t srcSt, size_t srcFrameSt, const void *dst, size_t dstSt, size_t dstFrameSt)
 {
-    if (h->channels > 1)  // packed plans: none of the planar kernels
+    return Layout{reinterpret_cast<uintptr_t>(src) | srcSt | srcFrameSt, reinterpret_cast<uintptr_t>(dst) | dstSt | dstFrameSt};
+}
+
+// The alignment in bytes that each kernel family's vector accesses need of the source and of the
+// destination (base, row stride and frame stride alike).
+struct Align {
+    unsigned src, dst;
+};
+
+Align kernel_align(const iqo_hip_plan *h, int kernel)
+{
+    switch (kernel) {
+    case IQO_KERNEL_LANCZOS_STREAM:  // 16-B loads, 16 / KX output bytes per thread
+        return {16, 16u / static_cast<unsigned>(h->p.flz.KX)};
+    case IQO_KERNEL_AREA_INT: {
+        // 16-B loads / 16 / KX output bytes per thread; 12-B loads / 12 / KX bytes when KX is 3 or 6
+        const unsigned KX = static_cast<unsigned>(h->p.far.KX), cols = 16 % KX == 0 ? 16 : 12;
+        return {cols == 16 ? 16u : 4u, cols / KX};
+    }
+    case IQO_KERNEL_LINEAR_UP2:
+        return {8, 16};
+    case IQO_KERNEL_WALK:  // the wave walker loads aligned dwords: 4-byte aligned source frames and rows
+        return {4, 1};
+    case IQO_KERNEL_LANCZOS_UP2:  // the 2x Lanczos kernel loads 8 B per lane and stores 16 B per lane
+        return {8, 16};
+    case IQO_KERNEL_LANCZOS_D32:  // the 3:2 Lanczos kernel loads 12 B per lane (4-byte aligned) and stores 8 B per lane
+        return {4, 8};
+    case IQO_KERNEL_LANCZOS_D31:  // the 3:1 Lanczos kernel loads 12 B per lane (4-byte aligned) and stores 4 B per lane
+        return {4, 4};
+    case IQO_KERNEL_AREA_D32:
+        return {4, 8};
+    case IQO_KERNEL_LANCZOS_U23:  // the 2:3 Lanczos kernel loads 8 B per lane and stores 12 B per lane
+    case IQO_KERNEL_LINEAR_U23:
+        return {8, 4};
+    default:
+        // general_kernel; tile_kernel: any alignment (the kernel adapts per frame); ryx (exact vertical
+        // ratio, tabled columns): dword loads (round 5: unaligned dword loads verified on gfx950,
+        // profiles/r05/unaligned_src.txt), 2-byte stores (1-byte stores when the destination is not
+        // 2-byte aligned, launch_ryx); ryg (general rows): dword loads, byte stores
+        return {1, 1};
+    }
+}
+
+bool layout_fits(const iqo_hip_plan *h, int kernel, Layout l)
+{
+    const Align a = kernel_align(h, kernel);
+    assert(a.src && !(a.src & (a.src - 1)) && a.dst && !(a.dst & (a.dst - 1)));  // powers of two (Layout)
+    return !(l.src & (a.src - 1)) && !(l.dst & (a.dst - 1));
+}
+
+// The kernel family a call with this layout runs: the first family of the cascade below that has
+// the plan's shape, is switched on, and finds the alignment its vector accesses need
+// (kernel_align).  A family refused for alignment leaves the plan with the walker / tile kernel for
+// the later steps, and in the end with the general kernel.
+int select_kernel(const iqo_hip_plan *h, Layout l)
+{
+    if (h->channels > 1)  // packed plans: none of the planar kernels; both packed kernels take any alignment
         return h->pk.ok && !h->forceGeneral ? IQO_KERNEL_PACKED_TILE : IQO_KERNEL_PACKED_GENERAL;
+    // the plan's streamer family (build_plan: LANCZOS_STREAM, AREA_INT, LINEAR_UP2), else the general kernel
     int k = h->forceGeneral ? IQO_KERNEL_GENERAL : h->p.kernel;
+    if (!layout_fits(h, k, l))
+        k = IQO_KERNEL_GENERAL;
     if (k == IQO_KERNEL_GENERAL && !h->forceGeneral && h->tt.ok && h->useTile)
         k = IQO_KERNEL_TILE;
-    if (k == IQO_KERNEL_TILE && h->wt.ok && h->useWalk)
+    if (k == IQO_KERNEL_TILE && h->wt.ok && h->useWalk && layout_fits(h, IQO_KERNEL_WALK, l))
         k = IQO_KERNEL_WALK;
-    if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && h->ut.ok && h->useUp2)
-        k = IQO_KERNEL_LANCZOS_UP2;
-    if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && h->dt.ok && h->useD32)
-        k = IQO_KERNEL_LANCZOS_D32;
-    if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && h->t31.ok && h->useD31)
-        k = IQO_KERNEL_LANCZOS_D31;
+    // an exact-ratio family takes over from the walker / tile kernel
+    auto take = [&](int family, bool have) {
+        if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && have && layout_fits(h, family, l))
+            k = family;
+    };
+    take(IQO_KERNEL_LANCZOS_UP2, h->ut.ok && h->useUp2);
+    take(IQO_KERNEL_LANCZOS_D32, h->dt.ok && h->useD32);
+    take(IQO_KERNEL_LANCZOS_D31, h->t31.ok && h->useD31);
     // (ryx also takes shapes whose taps exceed the tile kernel's tables: Lanczos-8/9 2:1)
     if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE || (k == IQO_KERNEL_GENERAL && !h->forceGeneral)) &&
         ryx_usable(h))
         k = IQO_KERNEL_RYX;
-    if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && h->at.ok && h->useA32)
-        k = IQO_KERNEL_AREA_D32;
-    if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && h->vt.ok && h->useU23)
-        k = IQO_KERNEL_LANCZOS_U23;
-    if ((k == IQO_KERNEL_WALK || k == IQO_KERNEL_TILE) && h->lt.ok && h->useL23)
-        k = IQO_KERNEL_LINEAR_U23;
+    take(IQO_KERNEL_AREA_D32, h->at.ok && h->useA32);
+    take(IQO_KERNEL_LANCZOS_U23, h->vt.ok && h->useU23);
+    take(IQO_KERNEL_LINEAR_U23, h->lt.ok && h->useL23);
     // general rows last: only what no exact-ratio kernel takes
     if ((k == IQO_KERNEL_TILE || (k == IQO_KERNEL_WALK && !walk_beats_ryg(h))) && ryg_usable(h))
         k = IQO_KERNEL_RYG;
     return k;
 }
 
-// The kernel family a call with these pointers and strides runs: the plan's fast kernel when the
-// layout has the alignment that kernel's vector accesses need, else the general kernel.
+// The kernel family a full-frame call with aligned pointers and strides runs.
+int plan_kernel(const iqo_hip_plan *h) { return select_kernel(h, kAlignedLayout); }
+
+// The kernel family a call with these pointers and strides runs.
 int kernel_for_layout(const iqo_hip_plan *h, const void *src, size_t srcSt, size_t srcFrameSt, const void *dst,
                       size_t dstSt, size_t dstFrameSt)
 {
-    if (h->channels > 1)  // packed plans: both kernels take any alignment
-        return plan_kernel(h);
-    const Plan &p = h->p;
-    int kernel = h->forceGeneral ? IQO_KERNEL_GENERAL : p.kernel;
-    if (kernel == IQO_KERNEL_LANCZOS_STREAM && !(aligned(src, 16, srcSt, srcFrameSt) && aligned(dst, 16 / p.flz.KX, dstSt, dstFrameSt)))
-        kernel = IQO_KERNEL_GENERAL;
-    if (kernel == IQO_KERNEL_AREA_INT) {
-        // 16-B loads / 16 / KX output bytes per thread; 12-B loads / 12 / KX bytes when KX is 3 or 6
-        const int cols = 16 % p.far.KX == 0 ? 16 : 12;
-        if (!(aligned(src, cols == 16 ? 16 : 4, srcSt, srcFrameSt) && aligned(dst, cols / p.far.KX, dstSt, dstFrameSt)))
-            kernel = IQO_KERNEL_GENERAL;
-    }
-    if (kernel == IQO_KERNEL_LINEAR_UP2 && !(aligned(src, 8, srcSt, srcFrameSt) && aligned(dst, 16, dstSt, dstFrameSt)))
-        kernel = IQO_KERNEL_GENERAL;
-    if (kernel == IQO_KERNEL_GENERAL && !h->forceGeneral && h->tt.ok && h->useTile)
-        kernel = IQO_KERNEL_TILE;  // any alignment (the kernel adapts per frame)
-    // the wave walker loads aligned dwords: 4-byte aligned source frames and rows
-    if (kernel == IQO_KERNEL_TILE && h->wt.ok && h->useWalk && aligned(src, 4, srcSt, srcFrameSt))
-        kernel = IQO_KERNEL_WALK;
-    // the 2x Lanczos kernel loads 8 B per lane and stores 16 B per lane
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE) && h->ut.ok && h->useUp2 &&
-        aligned(src, 8, srcSt, srcFrameSt) &&
-        aligned(dst, 16, dstSt, dstFrameSt))
-        kernel = IQO_KERNEL_LANCZOS_UP2;
-    // the 3:2 Lanczos kernel loads 12 B per lane (4-byte aligned) and stores 8 B per lane
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE) && h->dt.ok && h->useD32 &&
-        aligned(src, 4, srcSt, srcFrameSt) && aligned(dst, 8, dstSt, dstFrameSt))
-        kernel = IQO_KERNEL_LANCZOS_D32;
-    // the 3:1 Lanczos kernel loads 12 B per lane (4-byte aligned) and stores 4 B per lane
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE) && h->t31.ok && h->useD31 &&
-        aligned(src, 4, srcSt, srcFrameSt) && aligned(dst, 4, dstSt, dstFrameSt))
-        kernel = IQO_KERNEL_LANCZOS_D31;
-    // exact vertical ratio, tabled columns: dword loads; 2-byte stores (1-byte stores when the
-    // destination is not 2-byte aligned, launch_ryx)
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE || (kernel == IQO_KERNEL_GENERAL && !h->forceGeneral)) &&
-        ryx_usable(h))  // (round 5: unaligned dword loads verified on gfx950, profiles/r05/unaligned_src.txt)
-        kernel = IQO_KERNEL_RYX;
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE) && h->at.ok && h->useA32 &&
-        aligned(src, 4, srcSt, srcFrameSt) && aligned(dst, 8, dstSt, dstFrameSt))
-        kernel = IQO_KERNEL_AREA_D32;
-    // the 2:3 Lanczos kernel loads 8 B per lane and stores 12 B per lane
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE) && h->vt.ok && h->useU23 &&
-        aligned(src, 8, srcSt, srcFrameSt) && aligned(dst, 4, dstSt, dstFrameSt))
-        kernel = IQO_KERNEL_LANCZOS_U23;
-    if ((kernel == IQO_KERNEL_WALK || kernel == IQO_KERNEL_TILE) && h->lt.ok && h->useL23 &&
-        aligned(src, 8, srcSt, srcFrameSt) && aligned(dst, 4, dstSt, dstFrameSt))
-        kernel = IQO_KERNEL_LINEAR_U23;
-    // general rows last (dword loads, byte stores)
-    if ((kernel == IQO_KERNEL_TILE || (kernel == IQO_KERNEL_WALK && !walk_beats_ryg(h))) && ryg_usable(h))
-        kernel = IQO_KERNEL_RYG;
-    return kernel;
+    return select_kernel(h, layout_of(src, srcSt, srcFrameSt, dst, dstSt, dstFrameSt));
 }
 
 iqo_amd::Io make_io(size_t frames, const uint8_t *src, size_t srcSt, size_t srcFrameSt, size_t srcRow0, int srcRowEnd,
@@ -1723,10 +1760,9 @@ int iqo_hip_plan_prepare(iqo_hip_plan *h)
     return ensure_tables(h);
 }
 
-// The A/B keys (kernel family switches, band / lane / prefetch / column-split schedules; every one
-// speed-only) are accepted only with IQO_HIP_TUNING=1 in the environment -- tests, bench.py
-// --option and the tuning scripts set it; a caller of the public ABI sees force_general, bands and
-// host_stage only (include/iqo_hip.h).
+// The A/B keys (kOptions rows that are not public, and the three keys handled below) are accepted
+// only with IQO_HIP_TUNING=1 in the environment -- tests, bench.py --option and the tuning scripts
+// set it; a caller of the public ABI sees force_general, bands and host_stage only (include/iqo_hip.h).
 bool tuning_enabled()
 {
     const char *e = std::getenv("IQO_HIP_TUNING");
@@ -1737,24 +1773,20 @@ int iqo_hip_plan_set_option(iqo_hip_plan *h, const char *key, long value)
 {
     if (!h || !key)
         return IQO_HIP_EINVAL;
-    if (!std::strcmp(key, "force_general")) {
-        h->forceGeneral = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "bands")) {
-        if (value < 0)
-            return IQO_HIP_EINVAL;
-        h->bands = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "host_stage")) {  // host-pointer path of large frames (speed only): 0 the runtime's
-        if (value < 0 || value > 1)              // pageable copies, 1 the pinned staging pipeline
-            return IQO_HIP_EINVAL;
-        h->hostStage = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!tuning_enabled())
+    const Option *o = std::find_if(std::begin(kOptions), std::end(kOptions),
+                                   [&](const Option &r) { return !std::strcmp(key, r.name); });
+    const bool known = o != std::end(kOptions);
+    if (!(known && o->pub) && !tuning_enabled())
         return IQO_HIP_EINVAL;
+    if (known) {
+        const bool onoff = o->lo > o->hi;
+        if (!onoff && (value < o->lo || value > o->hi))
+            return IQO_HIP_EINVAL;
+        if (o->member == &iqo_hip_plan::rygCpt && value == 1)  // (0 auto, 2, 3, 4)
+            return IQO_HIP_EINVAL;
+        h->*o->member = onoff ? value != 0 : static_cast<int>(value);
+        return IQO_HIP_OK;
+    }
 #ifdef IQO_VARIANT_DEBUG
     if (!std::strcmp(key, "debug_flags")) {  // variant builds only: timing experiments, wrong results
         h->debugFlags = static_cast<int>(value);
@@ -1765,72 +1797,6 @@ int iqo_hip_plan_set_option(iqo_hip_plan *h, const char *key, long value)
         return IQO_HIP_OK;
     }
 #endif
-    if (!std::strcmp(key, "tail")) {  // block-shared Lanczos streamer: short tail bands (speed only)
-        if (value < -1 || value > 4096)
-            return IQO_HIP_EINVAL;
-        h->tail = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "rounds")) {  // block-shared Lanczos streamer: auto band count (speed only)
-        if (value < -1 || value > 64)
-            return IQO_HIP_EINVAL;
-        h->rounds = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryx_split")) {  // ratio-Y kernel column parts (speed only): 0 one 8-wave
-        if (value < 0 || value > 4)          // workgroup per row where it fits, 1 default, 2 / 3 parts of 2 / 1 waves,
-                                             // 4 the general rows' round-6 rule before one-wave parts
-            return IQO_HIP_EINVAL;
-        h->ryxSplit = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryx_adj")) {  // ratio-Y kernel adjacent column pairs (speed only): 0 off, 1 where they fit
-        if (value < 0 || value > 1)
-            return IQO_HIP_EINVAL;
-        h->ryxAdj = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryx_cpt")) {  // ratio-Y upscales: 0 two output columns per thread, 1 four
-                                          // at the Lanczos 4:9 upscales
-        if (value < 0 || value > 1)
-            return IQO_HIP_EINVAL;
-        h->ryxCpt = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryx_uc")) {  // ratio-Y kernel: 0 per-lane column coefficients everywhere (speed only)
-        h->ryxUc = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryg_cpt")) {  // general-row kernel, rows of > 1024 outputs: columns per thread
-        if (value != 0 && (value < 2 || value > 4))  // (0 auto, 2, 3, 4; speed only)
-            return IQO_HIP_EINVAL;
-        h->rygCpt = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "stack")) {  // narrow frames side by side in one workgroup (speed only):
-        if (value < 0 || value > 2)        // 0 off, 1 where a frame fills <= 1/2 wave, 2 from 2 frames
-            return IQO_HIP_EINVAL;
-        h->stack = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "prefetch")) {  // Lanczos streamer prefetch depth (rows)
-        if (value < 1 || value > 4)
-            return IQO_HIP_EINVAL;
-        h->prefetch = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "stream_variant")) {  // A/B: 0 symmetric block-shared (default), 1 ring,
-        if (value < 0 || value > 2)              // 2 symmetric per-wave
-            return IQO_HIP_EINVAL;
-        h->streamVariant = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "lanes")) {  // Lanczos / Linear streamers: producing lanes per wave (0 = auto)
-        if (value < 0 || value > 62)
-            return IQO_HIP_EINVAL;
-        h->lanes = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
     if (!std::strcmp(key, "tile_rows")) {  // output rows per tile of the tile kernel (0 = auto)
         iqo_amd::TileTables t = h->tt;
         if (!t.ok)
@@ -1842,68 +1808,6 @@ int iqo_hip_plan_set_option(iqo_hip_plan *h, const char *key, long value)
         }
         h->tt.TH = t.TH;
         h->tt.srcRows = t.srcRows;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "tile")) {  // 0: shapes without a specialised kernel use general_kernel
-        h->useTile = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "up2")) {  // 0: exact 2x Lanczos upscales use the wave walker alone
-        h->useUp2 = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "l23")) {  // 0: exact 2:3 Linear upscales use the wave walker alone
-        h->useL23 = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "u23")) {  // 0: exact 2:3 Lanczos-3 upscales use the wave walker alone
-        h->useU23 = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "a32")) {  // 0: exact 3:2 Area downscales use the wave walker alone
-        h->useA32 = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ratio_prefetch")) {  // exact-ratio kernels: row groups loaded ahead (speed only);
-                                                 // a depth the plan's kernel does not instantiate fails the
-                                                 // resize call with IQO_HIP_EINVAL
-        if (value < 0 || value > 8)
-            return IQO_HIP_EINVAL;
-        h->ratioPrefetch = static_cast<int>(value);
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryg")) {  // 0: general-row downscales (1 .. 2 : 1) use the wave walker / tile kernel
-        h->useRyg = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryu_run")) {  // 0: general upscale rows read each column's window separately
-        h->useRyuRun = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryu")) {  // 0: general upscale rows walk output rows (ryg_kernel NL = 1), not window positions
-        h->useRyu = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "ryx")) {  // 0: exact-vertical-ratio downscales use the general kernels
-        h->useRyx = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "d31")) {  // 0: exact 3:1 Lanczos downscales use the general kernels
-        h->useD31 = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "d32")) {  // 0: exact 3:2 Lanczos-3 downscales use the wave walker alone
-        h->useD32 = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "walk")) {  // 0: general ratios use tile_kernel instead of the wave walker
-        h->useWalk = value != 0;
-        return IQO_HIP_OK;
-    }
-    if (!std::strcmp(key, "chunk_frames")) {  // frames per launch (0 = auto)
-        if (value < 0)
-            return IQO_HIP_EINVAL;
-        h->chunkFrames = static_cast<int>(value);
         return IQO_HIP_OK;
     }
     return IQO_HIP_EINVAL;
@@ -2676,31 +2580,27 @@ int iqo_host_band_src_rows(int method, unsigned degree, size_t srcW, size_t srcH
     return IQO_HIP_OK;
 }
 
-int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale)
+int iqo_host_kernel_for_layout(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale,
+                               size_t srcAlign, size_t dstAlign)
 {
-    if (method < 0 || method > 2)
+    auto valid = [](size_t a) { return a >= 1 && a <= 16 && !(a & (a - 1)); };
+    if (method < 0 || method > 2 || !valid(srcAlign) || !valid(dstAlign))
         return IQO_HIP_EINVAL;
+    const Layout l{srcAlign, dstAlign};  // multiples of the alignment and of nothing larger
     iqo_hip_plan h;  // host half of a plan only: no device memory
     std::string err;
     if (!iqo_amd::build_plan(static_cast<iqo_amd::Method>(method), degree, srcW, srcH, dstW, dstH, pxScale, &h.p, &err))
         return IQO_HIP_EINVAL;
-    if (h.p.kernel != IQO_KERNEL_GENERAL)
+    // a streamer family with the alignment it needs is what select_kernel returns: no table build
+    if (h.p.kernel != IQO_KERNEL_GENERAL && layout_fits(&h, h.p.kernel, l))
         return h.p.kernel;
-    iqo_amd::build_tile_tables(h.p, &h.tt);
-    if (h.tt.ok)
-        iqo_amd::build_walk_tables(h.p, h.tt, &h.wt);
-    iqo_amd::build_up2(h.p, h.wt, &h.ut);
-    iqo_amd::build_d32(h.p, h.wt, &h.dt);
-    iqo_amd::build_d31(h.p, &h.t31);
-    iqo_amd::build_ryx(h.p, &h.ryx);
-    if (!h.ryx.ok)
-        iqo_amd::build_ryg(h.p, &h.ryx);
-    if (h.ryx.ok && ryx_dev(&h).parts == 0)
-        h.ryx = iqo_amd::RyxTables();
-    iqo_amd::build_a32(h.p, &h.at);
-    iqo_amd::build_u23(h.p, &h.vt);
-    iqo_amd::build_l23(h.p, &h.lt);
-    return plan_kernel(&h);
+    build_host_tables(&h);
+    return select_kernel(&h, l);
+}
+
+int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale)
+{
+    return iqo_host_kernel_for_layout(method, degree, srcW, srcH, dstW, dstH, pxScale, 16, 16);
 }
 
 int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,
@@ -2715,8 +2615,7 @@ int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t
     if (!iqo_amd::build_plan(static_cast<iqo_amd::Method>(method), degree, srcW, srcH, dstW, dstH, pxScale, &h.p, &err))
         return IQO_HIP_EINVAL;
     h.channels = channels;
-    iqo_amd::build_tile_tables(h.p, &h.tt);
-    iqo_amd::build_packed_tables(h.p, h.tt, channels, &h.pk);
+    build_host_tables(&h);
     return plan_kernel(&h);
 }
 

@@ -143,6 +143,46 @@ def test_fast_path_selection(cfg, kernel):
     assert libiqo_amd.host_kernel_for(*cfg) == kernel
 
 
+# (source, destination) alignment in bytes of the columns below
+_LAYOUTS = [(16, 16), (8, 16), (4, 16), (2, 16), (1, 16), (16, 8), (16, 4), (16, 2), (16, 1), (1, 1)]
+
+
+@pytest.mark.parametrize("cfg,kernels", [
+    (("lanczos", 3, 384, 216, 192, 108, 1), ["lanczos_stream"] + ["ryx"] * 4 + ["lanczos_stream"] + ["ryx"] * 4),
+    (("lanczos", 3, 384, 216, 192, 108, 2),
+     ["lanczos_stream", "walk", "walk", "tile", "tile", "lanczos_stream", "walk", "walk", "walk", "tile"]),
+    (("area", 0, 384, 216, 96, 54, 1), ["area_int"] + ["tile"] * 4 + ["area_int", "area_int"] + ["tile"] * 3),
+    (("area", 0, 384, 216, 128, 72, 1), ["area_int"] * 3 + ["tile", "tile", "area_int", "area_int"] + ["tile"] * 3),  # KX 3
+    (("area", 0, 384, 216, 64, 36, 1), ["area_int"] * 3 + ["tile", "tile"] + ["area_int"] * 3 + ["tile", "tile"]),   # KX 6
+    (("linear", 0, 192, 108, 384, 216, 1), ["linear_up2", "linear_up2", "walk", "tile", "tile"] + ["walk"] * 4 + ["tile"]),
+    (("linear", 0, 384, 216, 192, 108, 1), ["area_int"] + ["tile"] * 4 + ["area_int"] + ["tile"] * 4),
+    (("lanczos", 3, 192, 108, 384, 216, 1), ["lanczos_up2", "lanczos_up2"] + ["ryg"] * 8),
+    (("lanczos", 3, 384, 216, 256, 144, 1), ["lanczos_d32"] * 3 + ["ryg", "ryg", "lanczos_d32"] + ["ryg"] * 4),
+    (("lanczos", 3, 384, 216, 128, 72, 1), ["lanczos_d31"] * 3 + ["ryg", "ryg", "lanczos_d31", "lanczos_d31"] + ["ryg"] * 3),
+    (("area", 0, 384, 216, 256, 144, 1), ["area_d32"] * 3 + ["ryg", "ryg", "area_d32"] + ["walk"] * 3 + ["ryg"]),
+    (("lanczos", 3, 256, 144, 384, 216, 1), ["lanczos_u23"] * 2 + ["ryg"] * 3 + ["lanczos_u23"] * 2 + ["ryg"] * 3),
+    (("linear", 0, 256, 144, 384, 216, 1),
+     ["linear_u23", "linear_u23", "walk", "tile", "tile", "linear_u23", "linear_u23", "walk", "walk", "tile"]),
+    (("area", 0, 384, 216, 320, 180, 1), ["walk"] * 3 + ["ryg", "ryg"] + ["walk"] * 4 + ["ryg"]),
+    (("lanczos", 5, 200, 140, 300, 200, 1), ["walk"] * 3 + ["tile", "tile"] + ["walk"] * 4 + ["tile"]),
+    (("lanczos", 3, 384, 216, 96, 54, 1), ["ryx"] * 10),
+    (("lanczos", 3, 7, 100, 3, 50, 1), ["general"] * 10),
+])
+def test_layout_fallbacks(cfg, kernels):
+    """The kernel a shape falls back to when the call's source / destination base and strides have
+    less than the alignment its fast kernel needs (abi.hip select_kernel / kernel_align): one column
+    per (source, destination) alignment of _LAYOUTS."""
+    assert len(kernels) == len(_LAYOUTS)
+    got = [libiqo_amd.host_kernel_for(*cfg, src_align=s, dst_align=d) for s, d in _LAYOUTS]
+    assert got == kernels
+    assert libiqo_amd.host_kernel_for(*cfg) == libiqo_amd.host_kernel_for(*cfg, 16, 16)
+    for bad in (0, 3, 32):
+        with pytest.raises(libiqo_amd.IqoError):
+            libiqo_amd.host_kernel_for(*cfg, src_align=bad)
+        with pytest.raises(libiqo_amd.IqoError):
+            libiqo_amd.host_kernel_for(*cfg, dst_align=bad)
+
+
 @pytest.mark.parametrize("tool", ["iqo_resize_yuv420p", "iqo_benchmark"])
 def test_cli_tools_usage_without_gpu(tool, tmp_path):
     """The two command-line tools are built against the library and reject bad arguments with
