@@ -240,6 +240,78 @@ int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t s
                                size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, size_t dstStY,
                                size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstUV, void *stream);
 
+/* ---- NV12 / I420 straight to RGB: the resize above, then ONE integer YUV -> RGB definition, stored as
+ * packed RGB(A) bytes or as the normalised planar float tensors of iqo_hip_resize_device_norm -- what a
+ * model takes from a video decoder, without a float pass in between.
+ *
+ * Let Y(f, y, x), U(f, j, i), V(f, j, i) be exactly the bytes iqo_hip_resize_nv12_device /
+ * iqo_hip_resize_yuv420_device write for the same plan and source: Y at dstW x dstH, chroma at
+ * cw x ch = dstW/2 x dstH/2.  Chroma is replicated to the output grid (nearest): pixel (y, x) takes
+ * sample (min(y >> 1, ch - 1), min(x >> 1, cw - 1)); the min matters for odd dstW / dstH only.  With
+ * y' = Y - yOff, u = U - 128, v = V - 128 in int32 and >> an arithmetic (floor) shift,
+ *
+ *   R = clamp255((cY y' + cRV v         + 8192) >> 14)
+ *   G = clamp255((cY y' - cGU u - cGV v + 8192) >> 14)
+ *   B = clamp255((cY y' + cBU u         + 8192) >> 14)
+ *
+ *   standard               yOff     cY    cRV    cGU    cGV    cBU
+ *   IQO_CS_BT601_LIMITED     16  19077  26149   6419  13320  33050
+ *   IQO_CS_BT601_FULL         0  16384  22970   5638  11700  29032
+ *   IQO_CS_BT709_LIMITED     16  19077  29372   3494   8731  34610
+ *   IQO_CS_BT709_FULL         0  16384  25802   3069   7670  30402
+ *
+ * round(k 2^14) of the standards' real coefficients (libiqo_amd/csrc/colorspace.hpp holds the table for
+ * host and device code).  The full-range standards map grey (u = v = 0) to itself; the limited-range
+ * ones map 16 to 0 and 235 to 255.
+ *
+ * The calls take the source arguments of the resize entries, then where the result goes:
+ *   _rgb_   packed bytes, `channels` (3 or 4) per pixel, dstSt >= dstW*channels; byte c of a pixel is
+ *           order[c] of {0 R, 1 G, 2 B, 3 the constant 255} (RGB {0,1,2}, BGRA {2,1,0,3}, ...); entries
+ *           of order from `channels` on are ignored.
+ *   _norm_  iqo_hip_resize_device_norm's contract (iqo_hip_norm, strides, the two separately rounded
+ *           fp32 operations, the fp16 / bf16 rounding) on the R, G, B bytes as a 3-channel source:
+ *           order[p] in 0..2.
+ * Neither form needs the destination aligned beyond its element size.
+ *
+ * Two passes on `stream`: the planes are resized into `workspace` (device memory of at least
+ * iqo_hip_yuv_rgb_workspace_bytes(dstW, dstH, nFrames) bytes, any alignment, contents unspecified
+ * afterwards), then one kernel writes the destination.  No call allocates or synchronises: after
+ * iqo_hip_plan_prepare on both sub-plans they can be captured into a hipGraph.  The option
+ * "force_general" of the sub-plans applies to the first pass.  The I420 calls report in *fused (may be
+ * NULL) whether the first pass was one launch, as iqo_hip_resize_yuv420_device.
+ *
+ * IQO_HIP_EINVAL: a null plan, source, destination, workspace, order or norm; an unknown standard;
+ * channels outside 3..4; an order[c] outside 0..3 (c < channels); what iqo_hip_resize_device_norm rejects
+ * of a norm and its destination (dtype, planes, order[p] outside 0..2, non-finite scale or bias,
+ * alignment to the element size, strides below their contents, a destination frame that reaches 2^31
+ * bytes); dstSt < dstW*channels, dstFrameSt < dstH*dstSt when nFrames > 1; a source stride below its
+ * row, a source plane that reaches 2^31 bytes or a source stride >= 2^24; workspaceBytes below the
+ * query's value.  On any error nothing is launched and the destination is untouched. */
+enum { IQO_CS_BT601_LIMITED = 0, IQO_CS_BT601_FULL = 1, IQO_CS_BT709_LIMITED = 2, IQO_CS_BT709_FULL = 3 };
+/* Host-only.  The layout of the workspace is internal. */
+size_t iqo_hip_yuv_rgb_workspace_bytes(size_t dstW, size_t dstH, size_t nFrames);
+int iqo_hip_resize_nv12_rgb_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                   size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, int standard,
+                                   int channels, const int *order /* [4] */, size_t dstSt, size_t dstFrameSt,
+                                   uint8_t *dst, void *workspace, size_t workspaceBytes, void *stream);
+int iqo_hip_resize_nv12_norm_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                    size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, int standard,
+                                    const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt, size_t dstFrameSt,
+                                    void *dDst, void *workspace, size_t workspaceBytes, void *stream);
+int iqo_hip_resize_yuv420_rgb_device(iqo_hip_yuv_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                     size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV,
+                                     int standard, int channels, const int *order /* [4] */, size_t dstSt,
+                                     size_t dstFrameSt, uint8_t *dst, void *workspace, size_t workspaceBytes,
+                                     void *stream, int *fused);
+int iqo_hip_resize_yuv420_norm_device(iqo_hip_yuv_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                      size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV,
+                                      int standard, const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt,
+                                      size_t dstFrameSt, void *dDst, void *workspace, size_t workspaceBytes,
+                                      void *stream, int *fused);
+/* Host-only, no GPU: the formula above on n (Y, U, V) triples in plain C++ from the same table;
+ * rgb receives 3 n bytes (R, G, B per triple).  IQO_HIP_EINVAL for an unknown standard or a null pointer. */
+int iqo_host_yuv_to_rgb(int standard, size_t n, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *rgb);
+
 /* ---- Multi-GPU data movement for row-band / image sharding.  The reference
  * splits a frame's output rows over OpenMP threads (src/IQOLanczosResizerImpl_AVX512.cpp:269-308);
  * across GPUs the same split needs each band's source window (halo rows) on its device and the

@@ -14,7 +14,9 @@ import os
 
 __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420Resizer", "Nv12Resizer", "available",
            "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_yuv420_fused", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
-           "ipc_close", "KERNELS", "YUV420_FUSED", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16"]
+           "ipc_close", "KERNELS", "YUV420_FUSED", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16",
+           "CS_BT601_LIMITED", "CS_BT601_FULL", "CS_BT709_LIMITED", "CS_BT709_FULL", "COLOR_STANDARDS", "RGB_ORDERS",
+           "host_yuv_to_rgb", "yuv_rgb_workspace_bytes"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -49,6 +51,11 @@ class Norm(ctypes.Structure):
 
 
 OUT_F32, OUT_F16, OUT_BF16 = 1, 2, 3  # IQO_OUT_*
+CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3  # IQO_CS_*
+COLOR_STANDARDS = {"bt601": CS_BT601_LIMITED, "bt601-full": CS_BT601_FULL, "bt709": CS_BT709_LIMITED,
+                   "bt709-full": CS_BT709_FULL}
+# packed byte orders of resize_rgb: the source of each byte of a pixel (0 R, 1 G, 2 B, 3 the constant 255)
+RGB_ORDERS = {"rgb": (0, 1, 2), "bgr": (2, 1, 0), "rgba": (0, 1, 2, 3), "bgra": (2, 1, 0, 3)}
 
 
 class IpcHandle(ctypes.Structure):
@@ -115,6 +122,17 @@ def lib():
     L.iqo_hip_nv12_plane.restype = _vp
     L.iqo_hip_resize_nv12_device.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _c_sz, _c_sz, _vp, _vp,
                                              _vp]
+    src_nv12 = [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp]        # plan, nFrames, srcStY, srcStUV, srcFrameSt, Y, UV
+    src_i420 = src_nv12 + [_vp]                                   # ... Y, U, V
+    to_rgb = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _c_sz, _c_sz, _vp, _vp, _c_sz, _vp]
+    to_norm = [ctypes.c_int, ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp]
+    L.iqo_hip_yuv_rgb_workspace_bytes.argtypes = [_c_sz, _c_sz, _c_sz]
+    L.iqo_hip_yuv_rgb_workspace_bytes.restype = _c_sz
+    L.iqo_hip_resize_nv12_rgb_device.argtypes = src_nv12 + to_rgb
+    L.iqo_hip_resize_nv12_norm_device.argtypes = src_nv12 + to_norm
+    L.iqo_hip_resize_yuv420_rgb_device.argtypes = src_i420 + to_rgb + [ctypes.POINTER(ctypes.c_int)]
+    L.iqo_hip_resize_yuv420_norm_device.argtypes = src_i420 + to_norm + [ctypes.POINTER(ctypes.c_int)]
+    L.iqo_host_yuv_to_rgb.argtypes = [ctypes.c_int, _c_sz, _vp, _vp, _vp, _vp]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -213,6 +231,33 @@ def host_yuv420_fused(method, degree, srcW, srcH, dstW, dstH):
     if k < 0:
         raise IqoError("invalid yuv420 plan request")
     return YUV420_FUSED[k]
+
+
+def _standard(standard):
+    """IQO_CS_* of a name in COLOR_STANDARDS or of the integer itself."""
+    if isinstance(standard, str):
+        if standard not in COLOR_STANDARDS:
+            raise IqoError("standard must be one of %s" % ", ".join(sorted(COLOR_STANDARDS)))
+        return COLOR_STANDARDS[standard]
+    return int(standard)
+
+
+def yuv_rgb_workspace_bytes(dstW, dstH, nFrames):
+    """Bytes of device workspace the resize_rgb / resize_normalized calls of the YUV resizers need -- host only."""
+    return int(lib().iqo_hip_yuv_rgb_workspace_bytes(dstW, dstH, nFrames))
+
+
+def host_yuv_to_rgb(standard, y, u, v):
+    """The library's integer YUV -> RGB formula (include/iqo_hip.h, IQO_CS_*) on numpy uint8 arrays of one
+    shape, in plain C++ on the host -- no GPU.  Returns uint8 [..., 3] (R, G, B)."""
+    import numpy as np
+    y, u, v = (np.ascontiguousarray(a, dtype=np.uint8) for a in (y, u, v))
+    if not (y.shape == u.shape == v.shape):
+        raise IqoError("y, u and v must have one shape")
+    rgb = np.empty(y.shape + (3,), np.uint8)
+    _check(lib().iqo_host_yuv_to_rgb(_standard(standard), y.size, _ptr(y), _ptr(u), _ptr(v), _ptr(rgb)),
+           "host_yuv_to_rgb")
+    return rgb
 
 
 def _ptr(obj):
@@ -430,7 +475,105 @@ def make_resizer(method, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None,
     raise ValueError(method)
 
 
-class Yuv420Resizer:
+class _YuvToRgb:
+    """resize_rgb / resize_normalized of the two YUV 4:2:0 resizers: the planes resized as resize_frames
+    does, then the integer YUV -> RGB matrix of include/iqo_hip.h (IQO_CS_*) with chroma replicated to the
+    output grid, in one more kernel.  The subclass supplies _frame_bytes() and _to_rgb() / _to_norm()."""
+
+    def _src_frames(self, src):
+        import torch
+        n = self._frame_bytes()
+        if (src.dtype != torch.uint8 or not src.is_cuda or src.dim() != 2 or src.shape[1] != n
+                or not src.is_contiguous()):
+            raise IqoError("src must be a contiguous uint8 device tensor [frames, %d]" % n)
+        return src
+
+    def _workspace(self, src, stream):
+        """The device workspace of a call on `stream`: one per stream, kept on the resizer and grown when a
+        batch needs more, so the two passes in flight on a stream never see their block handed to another
+        allocation (calls on one stream are ordered; calls on different streams get different blocks).  With
+        a raw stream handle the resizer must outlive the work it queued; a torch Stream is also recorded on
+        the block, which then outlives the resizer as long as that stream needs it."""
+        import torch
+        nbytes = yuv_rgb_workspace_bytes(self.dstW, self.dstH, src.shape[0])
+        cache = self.__dict__.setdefault("_ws", {})
+        key = (src.device, _stream_ptr(stream))
+        ws = cache.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = cache[key] = torch.empty((nbytes,), dtype=torch.uint8, device=src.device)
+        if hasattr(stream, "cuda_stream"):
+            ws.record_stream(stream)
+        return ws, ws.numel()
+
+    def resize_rgb(self, src, standard="bt709", order="rgb", out=None, stream=None):
+        """src: the tight frame layout of resize_frames.  Returns / fills out [F, dstH, dstW, C] uint8, C = 3
+        ("rgb", "bgr") or 4 ("rgba", "bgra"; alpha 255).  standard: a COLOR_STANDARDS name ("bt601", "bt601-full",
+        "bt709", "bt709-full") or an IQO_CS_* value.  `out` may be a strided view with interleaved channels and
+        non-overlapping rows and frames; it is returned."""
+        import torch
+        if order not in RGB_ORDERS:
+            raise IqoError("order must be one of %s" % ", ".join(sorted(RGB_ORDERS)))
+        cs = _standard(standard)
+        s = self._src_frames(src)
+        o4 = RGB_ORDERS[order]
+        C = len(o4)
+        shape = (s.shape[0], self.dstH, self.dstW, C)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=s.device)
+        o = out
+        if (o.dtype != torch.uint8 or o.device != s.device or tuple(o.shape) != shape or o.stride(3) != 1
+                or o.stride(2) != C or o.stride(1) < self.dstW * C
+                or (o.shape[0] > 1 and o.stride(0) < self.dstH * o.stride(1))):
+            raise IqoError("out must be a uint8 tensor [%d, %d, %d, %d] on %s with interleaved channels and "
+                           "non-overlapping rows and frames" % (shape + (s.device,)))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        ws, nbytes = self._workspace(s, stream)
+        self._to_rgb(s, cs, C, (ctypes.c_int * 4)(*(o4 + (0,) * (4 - C))), o.stride(1), o.stride(0), o, ws, nbytes,
+                     stream)
+        return out
+
+    def resize_normalized(self, src, scale, bias, standard="bt709", dtype=None, order=(0, 1, 2), out=None,
+                          stream=None):
+        """src: the tight frame layout of resize_frames.  Returns / fills out [F, planes, dstH, dstW] of `dtype`
+        (float32, float16 or bfloat16): plane p is float32(byte order[p] of (R, G, B)) * scale[p] + bias[p], each
+        operation rounded to float32, then rounded to `dtype` -- _Resizer.resize_normalized on the RGB bytes of
+        resize_rgb.  `out` may be a strided view with unit column stride and non-overlapping rows, planes and
+        frames; it is returned."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32
+        codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+        if dtype not in codes:
+            raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        cs = _standard(standard)
+        order = tuple(int(c) for c in order)
+        scale, bias = tuple(float(v) for v in scale), tuple(float(v) for v in bias)
+        planes = len(order)
+        if not 1 <= planes <= 4 or len(scale) != planes or len(bias) != planes:
+            raise IqoError("order, scale and bias must have the same length, 1..4 (one entry per output plane)")
+        s = self._src_frames(src)
+        shape = (s.shape[0], planes, self.dstH, self.dstW)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=s.device)
+        o = out
+        if (o.dtype != dtype or o.device != s.device or tuple(o.shape) != shape or o.stride(3) != 1
+                or o.stride(2) < self.dstW or o.stride(1) < self.dstH * o.stride(2)
+                or (o.shape[0] > 1 and o.stride(0) < planes * o.stride(1))):
+            raise IqoError("out must be a %s tensor [%d, %d, %d, %d] on %s with unit column stride and "
+                           "non-overlapping rows, planes and frames" % ((dtype,) + shape + (s.device,)))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        n = Norm(codes[dtype], planes)
+        for i in range(planes):
+            n.order[i], n.scale[i], n.bias[i] = order[i], scale[i], bias[i]
+        e = o.element_size()
+        ws, nbytes = self._workspace(s, stream)
+        self._to_norm(s, cs, n, o.stride(2) * e, o.stride(1) * e, o.stride(0) * e, o, ws, nbytes, stream)
+        return out
+
+
+class Yuv420Resizer(_YuvToRgb):
     """I420 three-plane resizer: the reference benchmark's workload (benchmark.cpp:131-229), Y at
     full size and U, V at half size with the same method (Lanczos chroma: pxScale 2)."""
 
@@ -488,8 +631,33 @@ class Yuv420Resizer:
                                    dw, dw // 2, out.stride(0), o, o + dw * dh, o + dw * dh + cd, stream)
         return out, fused
 
+    # -- _YuvToRgb: the I420 entries; last_fused tells whether the first pass of the last call was one launch
+    last_fused = False
 
-class Nv12Resizer:
+    def _frame_bytes(self):
+        return self.srcW * self.srcH + 2 * (self.srcW // 2) * (self.srcH // 2)
+
+    def _src_args(self, s):
+        sw, sh = self.srcW, self.srcH
+        b, cs = s.data_ptr(), (sw // 2) * (sh // 2)
+        return (self._plan, s.shape[0], sw, sw // 2, s.stride(0), b, b + sw * sh, b + sw * sh + cs)
+
+    def _to_rgb(self, s, cs, C, order, row_st, frame_st, o, ws, nbytes, stream):
+        fused = ctypes.c_int(0)
+        _check(lib().iqo_hip_resize_yuv420_rgb_device(*self._src_args(s), cs, C, order, row_st, frame_st, _ptr(o),
+                                                      _ptr(ws), nbytes, _stream_ptr(stream), ctypes.byref(fused)),
+               "resize_rgb")
+        self.last_fused = bool(fused.value)
+
+    def _to_norm(self, s, cs, norm, row_st, plane_st, frame_st, o, ws, nbytes, stream):
+        fused = ctypes.c_int(0)
+        _check(lib().iqo_hip_resize_yuv420_norm_device(*self._src_args(s), cs, ctypes.byref(norm), row_st, plane_st,
+                                                       frame_st, _ptr(o), _ptr(ws), nbytes, _stream_ptr(stream),
+                                                       ctypes.byref(fused)), "resize_normalized")
+        self.last_fused = bool(fused.value)
+
+
+class Nv12Resizer(_YuvToRgb):
     """NV12 resizer: a planar Y plane at full size and one interleaved UV plane at half size, with
     the same method (Lanczos chroma: pxScale 2).  U and V come out as Yuv420Resizer's planes do."""
 
@@ -549,3 +717,21 @@ class Nv12Resizer:
         self.resize_device(n, sw, 2 * (sw // 2), src.stride(0), b, b + sw * sh, dw, 2 * (dw // 2), out.stride(0),
                            o, o + dw * dh, stream)
         return out
+
+    # -- _YuvToRgb: the NV12 entries
+    def _frame_bytes(self):
+        return self.srcW * self.srcH + 2 * (self.srcW // 2) * (self.srcH // 2)
+
+    def _src_args(self, s):
+        sw, sh = self.srcW, self.srcH
+        b = s.data_ptr()
+        return (self._plan, s.shape[0], sw, 2 * (sw // 2), s.stride(0), b, b + sw * sh)
+
+    def _to_rgb(self, s, cs, C, order, row_st, frame_st, o, ws, nbytes, stream):
+        _check(lib().iqo_hip_resize_nv12_rgb_device(*self._src_args(s), cs, C, order, row_st, frame_st, _ptr(o),
+                                                    _ptr(ws), nbytes, _stream_ptr(stream)), "resize_rgb")
+
+    def _to_norm(self, s, cs, norm, row_st, plane_st, frame_st, o, ws, nbytes, stream):
+        _check(lib().iqo_hip_resize_nv12_norm_device(*self._src_args(s), cs, ctypes.byref(norm), row_st, plane_st,
+                                                     frame_st, _ptr(o), _ptr(ws), nbytes, _stream_ptr(stream)),
+               "resize_normalized")

@@ -2260,6 +2260,269 @@ int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *np, size_t nFrames, size_t src
     return rc;
 }
 
+// ---- NV12 / I420 straight to RGB bytes or normalised RGB tensors.  Two passes on the stream: the
+// resize entries above, unchanged, into the caller's workspace, then yuv_rgb_kernel
+// (kernels_color.hip) from the workspace to the destination.  Every check runs on the host before the
+// first launch, so a rejected call launches nothing and leaves the destination untouched.
+
+// Workspace of one frame: the Y plane, then U and V (I420) or the interleaved UV plane (NV12, rows of
+// 2 * cSt bytes) in the same bytes.  Rows are padded to what a thread of yuv_rgb_kernel loads (8 Y
+// bytes, 4 chroma pairs) and to 16 bytes, so that every plane kernel finds its widest stores aligned
+// and the fused I420 instantiations stay one launch.
+struct YuvRgbWs {
+    size_t ySt, cSt, frame;
+};
+
+static YuvRgbWs yuv_rgb_ws(size_t dstW, size_t dstH)
+{
+    const size_t w8 = (dstW + 7) / 8 * 8;
+    YuvRgbWs w;
+    w.ySt = (w8 + 15) & ~static_cast<size_t>(15);
+    w.cSt = (w8 / 2 + 15) & ~static_cast<size_t>(15);
+    w.frame = w.ySt * dstH + 2 * w.cSt * (dstH / 2);
+    return w;
+}
+
+size_t iqo_hip_yuv_rgb_workspace_bytes(size_t dstW, size_t dstH, size_t nFrames)
+{
+    const size_t kMaxSize = std::numeric_limits<size_t>::max(), kLim = size_t(1) << 31;
+    if (dstW >= kLim || dstH >= kLim)
+        return kMaxSize;  // (no plan has such a frame)
+    const size_t frame = yuv_rgb_ws(dstW, dstH).frame;
+    if (frame && nFrames > (kMaxSize - 15) / frame)
+        return kMaxSize;
+    return nFrames * frame + 15;  // + 15: the calls round the base up to 16 bytes
+}
+
+int iqo_host_yuv_to_rgb(int standard, size_t n, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *rgb)
+{
+    if (standard < 0 || standard >= iqo_amd::kYuvRgbStandards || !y || !u || !v || !rgb)
+        return IQO_HIP_EINVAL;
+    const iqo_amd::YuvRgbCoef &k = iqo_amd::kYuvRgb[standard];
+    for (size_t i = 0; i < n; ++i) {
+        int R, G, B;
+        iqo_amd::yuv_to_rgb(k, y[i], iqo_amd::yuv_chroma_terms(k, u[i], v[i]), R, G, B);
+        rgb[3 * i] = static_cast<uint8_t>(R);
+        rgb[3 * i + 1] = static_cast<uint8_t>(G);
+        rgb[3 * i + 2] = static_cast<uint8_t>(B);
+    }
+    return IQO_HIP_OK;
+}
+
+// Where the second pass writes: packed bytes (norm == nullptr; rowSt = the row stride) or planar floats.
+struct YuvRgbOut {
+    int channels;
+    const int *order;
+    const iqo_hip_norm *norm;
+    size_t rowSt, planeSt, frameSt;
+    void *dst;
+};
+
+// One source plane as the first pass reads it: `bpp` bytes per pixel
+static bool yuv_src_ok(const Plan &p, size_t bpp, size_t srcSt)
+{
+    const size_t rowB = static_cast<size_t>(p.srcW) * bpp;
+    return srcSt >= rowB && srcSt < (size_t(1) << 24) && static_cast<size_t>(p.srcH - 1) * srcSt + rowB < (size_t(1) << 31);
+}
+
+// Everything the second pass needs checked (as run_norm for the float form); fills *nd for it.
+static int yuv_rgb_check(const Plan &py, size_t nFrames, int standard, const YuvRgbOut &o, const void *workspace,
+                         size_t workspaceBytes, iqo_amd::NormDev *nd)
+{
+    if (!o.dst || !workspace || (!o.norm && !o.order))
+        return IQO_HIP_EINVAL;
+    if (standard < 0 || standard >= iqo_amd::kYuvRgbStandards)
+        return IQO_HIP_EINVAL;
+    const size_t dstW = static_cast<size_t>(py.dstW), dstH = static_cast<size_t>(py.dstH), kLim = size_t(1) << 31;
+    size_t elem = 1, planes = 1, rowB;
+    if (o.norm) {
+        const iqo_hip_norm &n = *o.norm;
+        if (n.dtype != IQO_OUT_F32 && n.dtype != IQO_OUT_F16 && n.dtype != IQO_OUT_BF16)
+            return IQO_HIP_EINVAL;
+        if (n.planes < 1 || n.planes > 4)
+            return IQO_HIP_EINVAL;
+        for (int i = 0; i < n.planes; ++i)
+            if (n.order[i] < 0 || n.order[i] > 2 || !std::isfinite(n.scale[i]) || !std::isfinite(n.bias[i]))
+                return IQO_HIP_EINVAL;
+        elem = n.dtype == IQO_OUT_F32 ? 4 : 2;
+        planes = static_cast<size_t>(n.planes);
+        rowB = dstW * elem;
+        if (reinterpret_cast<uintptr_t>(o.dst) % elem || o.rowSt % elem || o.planeSt % elem || o.frameSt % elem)
+            return IQO_HIP_EINVAL;
+        if (o.planeSt / dstH < o.rowSt || o.planeSt >= kLim)
+            return IQO_HIP_EINVAL;
+        nd->dtype = n.dtype;
+        nd->planes = n.planes;
+        nd->planeSt = static_cast<int>(o.planeSt);
+        for (int i = 0; i < 4; ++i) {
+            const bool used = i < n.planes;
+            nd->order[i] = used ? n.order[i] : 0;
+            nd->scale[i] = used ? n.scale[i] : 0.f;
+            nd->bias[i] = used ? n.bias[i] : 0.f;
+        }
+    } else {
+        if (o.channels < 3 || o.channels > 4)
+            return IQO_HIP_EINVAL;
+        for (int c = 0; c < o.channels; ++c)
+            if (o.order[c] < 0 || o.order[c] > 3)
+                return IQO_HIP_EINVAL;
+        rowB = dstW * static_cast<size_t>(o.channels);
+    }
+    // (divisions: no product of caller-supplied strides can wrap)
+    const size_t frameRows = o.norm ? o.planeSt : o.rowSt;  // a frame holds `planes` planes / dstH rows of these
+    if (o.rowSt < rowB || o.rowSt >= kLim || (nFrames > 1 && o.frameSt / (o.norm ? planes : dstH) < frameRows))
+        return IQO_HIP_EINVAL;
+    // the kernel addresses one destination frame and one workspace frame with 32-bit offsets
+    if ((planes - 1) * (o.norm ? o.planeSt : 0) + (dstH - 1) * o.rowSt + rowB >= kLim ||
+        yuv_rgb_ws(dstW, dstH).frame >= kLim)
+        return IQO_HIP_EINVAL;
+    if (workspaceBytes < iqo_hip_yuv_rgb_workspace_bytes(dstW, dstH, nFrames))
+        return IQO_HIP_EINVAL;
+    return IQO_HIP_OK;
+}
+
+static uint8_t *yuv_rgb_ws_base(void *workspace)
+{
+    return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~static_cast<uintptr_t>(15));
+}
+
+// The second pass: yuv_rgb_kernel over the workspace planes the first pass wrote.
+static int yuv_rgb_convert(const iqo_hip_plan *hy, size_t nFrames, const uint8_t *ws, bool interleavedUV, int standard,
+                           const YuvRgbOut &o, const iqo_amd::NormDev &nd, hipStream_t s)
+{
+    const Plan &py = hy->p;
+    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH));
+    DeviceGuard guard(hy->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    iqo_amd::YuvRgbDev d{};
+    d.dstW = py.dstW;
+    d.dstH = py.dstH;
+    d.cw = py.dstW / 2;
+    d.ch = py.dstH / 2;
+    d.k = iqo_amd::kYuvRgb[standard];
+    d.ySt = static_cast<int>(w.ySt);
+    d.cSt = static_cast<int>(interleavedUV ? 2 * w.cSt : w.cSt);
+    d.frameSt = static_cast<int64_t>(w.frame);
+    d.dstSt = static_cast<int>(o.rowSt);
+    d.dstFrameSt = static_cast<int64_t>(o.frameSt);
+    // frames per launch: the kernel counts (frame, row, pixel group) items in 31 bits, groups of 4 at the least
+    const size_t perFrame = static_cast<size_t>(py.dstH) * ((static_cast<size_t>(py.dstW) + 3) / 4);
+    const size_t chunk = std::max<size_t>(1, ((size_t(1) << 31) - 1) / perFrame);
+    for (size_t f0 = 0; f0 < nFrames; f0 += chunk) {
+        d.frames = static_cast<int>(std::min(chunk, nFrames - f0));
+        d.y = ws + f0 * w.frame;
+        d.u = d.y + w.ySt * static_cast<size_t>(py.dstH);
+        d.v = d.u + w.cSt * static_cast<size_t>(d.ch);
+        d.dst = static_cast<uint8_t *>(o.dst) + f0 * o.frameSt;
+        int order[4] = {0, 0, 0, 0};
+        for (int c = 0; !o.norm && c < o.channels; ++c)
+            order[c] = o.order[c];
+        const hipError_t e = o.norm ? iqo_amd::launch_yuv_rgb_norm(d, interleavedUV, nd, s)
+                                    : iqo_amd::launch_yuv_rgb_bytes(d, interleavedUV, o.channels, order, s);
+        if (e == hipErrorInvalidValue)
+            return IQO_HIP_EINVAL;
+        if (e != hipSuccess)
+            return IQO_HIP_EHIP;
+    }
+    return IQO_HIP_OK;
+}
+
+static int nv12_rgb(iqo_hip_nv12_plan *np, size_t nFrames, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                    const uint8_t *srcY, const uint8_t *srcUV, int standard, const YuvRgbOut &o, void *workspace,
+                    size_t workspaceBytes, void *stream)
+{
+    if (!np || !np->y || !np->uv || !srcY || !srcUV)
+        return IQO_HIP_EINVAL;
+    const Plan &py = np->y->p;
+    iqo_amd::NormDev nd{};
+    const int rc = yuv_rgb_check(py, nFrames, standard, o, workspace, workspaceBytes, &nd);
+    if (rc)
+        return rc;
+    if (!yuv_src_ok(py, 1, srcStY) || !yuv_src_ok(np->uv->p, 2, srcStUV))
+        return IQO_HIP_EINVAL;
+    if (nFrames == 0)
+        return IQO_HIP_OK;
+    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH));
+    uint8_t *ws = yuv_rgb_ws_base(workspace);
+    const int r1 = iqo_hip_resize_nv12_device(np, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcUV, w.ySt, 2 * w.cSt, w.frame,
+                                              ws, ws + w.ySt * static_cast<size_t>(py.dstH), stream);
+    if (r1)
+        return r1;
+    return yuv_rgb_convert(np->y, nFrames, ws, true, standard, o, nd, static_cast<hipStream_t>(stream));
+}
+
+static int yuv420_rgb(iqo_hip_yuv_plan *yp, size_t nFrames, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                      const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV, int standard, const YuvRgbOut &o,
+                      void *workspace, size_t workspaceBytes, void *stream, int *fused)
+{
+    if (fused)
+        *fused = 0;
+    if (!yp || !yp->y || !yp->c || !srcY || !srcU || !srcV)
+        return IQO_HIP_EINVAL;
+    const Plan &py = yp->y->p;
+    iqo_amd::NormDev nd{};
+    const int rc = yuv_rgb_check(py, nFrames, standard, o, workspace, workspaceBytes, &nd);
+    if (rc)
+        return rc;
+    if (!yuv_src_ok(py, 1, srcStY) || !yuv_src_ok(yp->c->p, 1, srcStUV))
+        return IQO_HIP_EINVAL;
+    if (nFrames == 0)
+        return IQO_HIP_OK;
+    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH));
+    uint8_t *ws = yuv_rgb_ws_base(workspace), *wu = ws + w.ySt * static_cast<size_t>(py.dstH);
+    const int r1 = iqo_hip_resize_yuv420_device(yp, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcU, srcV, w.ySt, w.cSt,
+                                                w.frame, ws, wu, wu + w.cSt * static_cast<size_t>(py.dstH / 2), stream, fused);
+    if (r1)
+        return r1;
+    return yuv_rgb_convert(yp->y, nFrames, ws, false, standard, o, nd, static_cast<hipStream_t>(stream));
+}
+
+int iqo_hip_resize_nv12_rgb_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                   size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, int standard,
+                                   int channels, const int *order, size_t dstSt, size_t dstFrameSt, uint8_t *dst,
+                                   void *workspace, size_t workspaceBytes, void *stream)
+{
+    const YuvRgbOut o{channels, order, nullptr, dstSt, 0, dstFrameSt, dst};
+    return nv12_rgb(plan, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcUV, standard, o, workspace, workspaceBytes, stream);
+}
+
+int iqo_hip_resize_nv12_norm_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                    size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, int standard,
+                                    const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt, size_t dstFrameSt,
+                                    void *dDst, void *workspace, size_t workspaceBytes, void *stream)
+{
+    if (!norm)
+        return IQO_HIP_EINVAL;
+    const YuvRgbOut o{3, nullptr, norm, dstRowSt, dstPlaneSt, dstFrameSt, dDst};
+    return nv12_rgb(plan, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcUV, standard, o, workspace, workspaceBytes, stream);
+}
+
+int iqo_hip_resize_yuv420_rgb_device(iqo_hip_yuv_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                     size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV,
+                                     int standard, int channels, const int *order, size_t dstSt, size_t dstFrameSt,
+                                     uint8_t *dst, void *workspace, size_t workspaceBytes, void *stream, int *fused)
+{
+    const YuvRgbOut o{channels, order, nullptr, dstSt, 0, dstFrameSt, dst};
+    return yuv420_rgb(plan, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcU, srcV, standard, o, workspace, workspaceBytes,
+                      stream, fused);
+}
+
+int iqo_hip_resize_yuv420_norm_device(iqo_hip_yuv_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
+                                      size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV,
+                                      int standard, const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt,
+                                      size_t dstFrameSt, void *dDst, void *workspace, size_t workspaceBytes, void *stream,
+                                      int *fused)
+{
+    if (fused)
+        *fused = 0;
+    if (!norm)
+        return IQO_HIP_EINVAL;
+    const YuvRgbOut o{3, nullptr, norm, dstRowSt, dstPlaneSt, dstFrameSt, dDst};
+    return yuv420_rgb(plan, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcU, srcV, standard, o, workspace, workspaceBytes,
+                      stream, fused);
+}
+
 int iqo_hip_resize_yuv420(iqo_hip_yuv_plan *yp, size_t srcStY, const uint8_t *srcY, size_t srcStUV,
                           const uint8_t *srcU, const uint8_t *srcV, size_t dstStY, uint8_t *dstY, size_t dstStUV,
                           uint8_t *dstU, uint8_t *dstV)

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "colorspace.hpp"
+
 namespace iqo_amd {
 
 // A device-side view of one batched call: frame f reads src + f*srcFrameSt, whose row 0 is
@@ -74,6 +76,31 @@ hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const I
                                       int rowEnd, hipStream_t s);
 hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io, const NormDev &n, int rowBegin,
                                    int rowEnd, hipStream_t s);
+
+// --- YUV 4:2:0 planes -> RGB (kernels_color.hip): the second pass of the NV12 / I420 "resize to RGB"
+// entries.  Reads resized planes from a workspace (Y dstW x dstH; chroma cw x ch, replicated to the
+// output grid: pixel (y, x) takes sample (min(y >> 1, ch - 1), min(x >> 1, cw - 1))), applies the
+// integer matrix of colorspace.hpp and writes packed bytes or NormDev's planar floats.
+// Workspace rows: the Y base and ySt are multiples of 8 with ySt >= 8 ceil(dstW / 8); the chroma
+// bases and cSt are multiples of 8 (interleaved UV) / 4 (separate U, V) with
+// cSt >= 8 / 4 ceil(dstW / 8) -- a thread loads 8 Y bytes and 4 chroma pairs whole; what it loads
+// past the planes' widths is never used.  No alignment of dst beyond the element size.
+struct YuvRgbDev {
+    int dstW, dstH, cw, ch;
+    YuvRgbCoef k;                      // the standard's six integers
+    const uint8_t *y, *u, *v;          // frame 0's planes; interleaved UV: u, and v is not read
+    int ySt, cSt;                      // row strides, bytes
+    int64_t frameSt;                   // workspace frame stride, bytes
+    uint8_t *dst;
+    int dstSt;                         // row stride, bytes (< 2^31; one frame's extent < 2^31)
+    int64_t dstFrameSt;
+    int frames;                        // frames x dstH x ceil(dstW / 4) < 2^31
+};
+// Packed bytes: `channels` 3 or 4 per pixel, byte c = order[c] of {0 R, 1 G, 2 B, 3 the constant 255}.
+hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, int channels, const int (&order)[4],
+                                hipStream_t s);
+// Planar floats as the packed kernels' NORM epilogue, of the 3-channel source (R, G, B).
+hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, const NormDev &n, hipStream_t s);
 
 // --- general-ratio wave walker: every wave walks a 256-column strip of one band of rows through
 // a private LDS ring of source rows widened to u16 (plan.hpp WalkTables; 4-byte aligned sources).

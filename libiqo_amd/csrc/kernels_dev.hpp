@@ -220,21 +220,25 @@ __device__ __forceinline__ void lds_barrier()
 
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 
-// (sat_u8(a >> 20), sat_u8(b >> 20)) into bits 0..15 of the result (bits 16..31 undefined) /
-// into bits 16..31 of w (bits 0..15 kept).  gfx950 v_ashr_pk_u8_i32: src0 -> byte 0, src1 ->
-// byte 1, the other half of the destination is preserved (probed on MI355X,
-// scripts/ubench/pk_test.hip).
-__device__ __forceinline__ uint32_t pack_lo(int a, int b)
+// gfx950 v_ashr_pk_u8_i32: (sat_u8(a >> S), sat_u8(b >> S)) into bits 0..15 of the result (bits 16..31
+// undefined) / into bits 16..31 of w (bits 0..15 kept): src0 -> byte 0, src1 -> byte 1, the other half
+// of the destination is preserved (probed on MI355X, scripts/ubench/pk_test.hip).
+template <int S>
+__device__ __forceinline__ uint32_t ashr_pk_lo(int a, int b)
 {
     uint32_t w;
-    asm("v_ashr_pk_u8_i32 %0, %1, %2, 20" : "=v"(w) : "v"(a), "v"(b));
+    asm("v_ashr_pk_u8_i32 %0, %1, %2, %3" : "=v"(w) : "v"(a), "v"(b), "n"(S));
     return w;
 }
-__device__ __forceinline__ uint32_t pack_hi(uint32_t w, int a, int b)
+template <int S>
+__device__ __forceinline__ uint32_t ashr_pk_hi(uint32_t w, int a, int b)
 {
-    asm("v_ashr_pk_u8_i32 %0, %1, %2, 20 op_sel:[0,0,0,1]" : "+v"(w) : "v"(a), "v"(b));
+    asm("v_ashr_pk_u8_i32 %0, %1, %2, %3 op_sel:[0,0,0,1]" : "+v"(w) : "v"(a), "v"(b), "n"(S));
     return w;
 }
+// shift 20: the Lanczos kernels' outputs
+__device__ __forceinline__ uint32_t pack_lo(int a, int b) { return ashr_pk_lo<20>(a, b); }
+__device__ __forceinline__ uint32_t pack_hi(uint32_t w, int a, int b) { return ashr_pk_hi<20>(w, a, b); }
 
 // int16(n * 64 / deno) for both int16 halves of w (C truncation), deno via (m, s) of magic_y.
 __device__ __forceinline__ uint32_t ydiv2(uint32_t w, uint32_t m, int s)
@@ -267,19 +271,43 @@ __device__ __forceinline__ int sld(const void *p, int i)
 }
 __device__ __forceinline__ int4 sload(const int4 *p) { return make_int4(sld(p, 0), sld(p, 1), sld(p, 2), sld(p, 3)); }
 
-// v_ashr_pk_u8_i32 with shift 23: (sat_u8(a >> 23), sat_u8(b >> 23)) into the low / high half
+// shift 23: the Area / Linear kernels' outputs
 __device__ __forceinline__ uint32_t pack23_lo(uint32_t a, uint32_t b)
 {
-    uint32_t w;
-    asm("v_ashr_pk_u8_i32 %0, %1, %2, 23" : "=v"(w) : "v"(a), "v"(b));
-    return w;
+    return ashr_pk_lo<23>(static_cast<int>(a), static_cast<int>(b));
 }
 __device__ __forceinline__ uint32_t pack23_hi(uint32_t w, uint32_t a, uint32_t b)
 {
-    asm("v_ashr_pk_u8_i32 %0, %1, %2, 23 op_sel:[0,0,0,1]" : "+v"(w) : "v"(a), "v"(b));
-    return w;
+    return ashr_pk_hi<23>(w, static_cast<int>(a), static_cast<int>(b));
 }
 
+// ---- float epilogue (NormDev) of the packed kernels and the YUV -> RGB kernel
+
+// fl32(fl32(v * s) + b), two roundings: the empty asm takes the product out of the compiler's
+// sight, so no contraction setting can fuse the pair into an FMA.
+__device__ __forceinline__ float norm_affine(uint32_t v, float s, float b)
+{
+    float m = static_cast<float>(v) * s;
+    asm("" : "+v"(m));
+    return m + b;
+}
+
+// round-to-nearest-even conversions (overflow to +-inf), as bit patterns
+__device__ __forceinline__ uint32_t f16_bits(float f)
+{
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));
+}
+__device__ __forceinline__ uint32_t bf16_bits(float f)
+{
+    return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f));
+}
+
+// entry p (wave-uniform, 0 .. 3) of a kernel-argument array: selects, never an indexed copy
+template <typename T>
+__device__ __forceinline__ T pick4(const T (&v)[4], int p)
+{
+    return p == 0 ? v[0] : p == 1 ? v[1] : p == 2 ? v[2] : v[3];
+}
 
 // ---- host-side launch helpers
 

@@ -125,31 +125,7 @@ struct PackedGeneralNormArgs : PackedGeneralArgs {
     NormDev n;
 };
 
-// fl32(fl32(v * s) + b), two roundings: the empty asm takes the product out of the compiler's
-// sight, so no contraction setting can fuse the pair into an FMA.
-__device__ __forceinline__ float norm_affine(uint32_t v, float s, float b)
-{
-    float m = static_cast<float>(v) * s;
-    asm("" : "+v"(m));
-    return m + b;
-}
-
-// round-to-nearest-even conversions (overflow to +-inf), as bit patterns
-__device__ __forceinline__ uint32_t f16_bits(float f)
-{
-    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));
-}
-__device__ __forceinline__ uint32_t bf16_bits(float f)
-{
-    return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f));
-}
-
-// entry p (wave-uniform, 0 .. 3) of a kernel-argument array: selects, never an indexed copy
-template <typename T>
-__device__ __forceinline__ T pick4(const T (&v)[4], int p)
-{
-    return p == 0 ? v[0] : p == 1 ? v[1] : p == 2 ? v[2] : v[3];
-}
+// (norm_affine, f16_bits, bf16_bits and pick4 are in kernels_dev.hpp: kernels_color.hip shares them)
 
 // One workgroup per (output row, frame, channel); NORM: per (output row, frame, output plane),
 // whose channel is order[plane].

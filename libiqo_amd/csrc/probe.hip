@@ -62,7 +62,7 @@ hipError_t launch(bool nt, const void *src, void *dst, size_t units, hipStream_t
 } // namespace
 
 // Reads R KiB and writes W KiB per unit, `units` units: srcBytes >= units R KiB, dstBytes >= units
-// W KiB (the caller sizes the buffers).  (R, W) in {(1, 4), (1, 1), (4, 1), (16, 1)}.  Returns 0, or
+// W KiB (the caller sizes the buffers).  (R, W) in {(1, 8), (1, 4), (1, 1), (4, 1), (16, 1)}.  Returns 0, or
 // -1 for an unsupported mix / bad arguments, -2 for a launch error.
 extern "C" int iqo_probe_stream(int R, int W, int nt, const void *src, size_t srcBytes, void *dst, size_t dstBytes,
                                 void *stream)
@@ -74,7 +74,9 @@ extern "C" int iqo_probe_stream(int R, int W, int nt, const void *src, size_t sr
         return -1;
     auto s = static_cast<hipStream_t>(stream);
     hipError_t e;
-    if (R == 1 && W == 4)
+    if (R == 1 && W == 8)  // fp32 planes out of 4:2:0 bytes (benchmark/nv12_rgb.py)
+        e = launch<1, 8>(nt != 0, src, dst, units, s);
+    else if (R == 1 && W == 4)
         e = launch<1, 4>(nt != 0, src, dst, units, s);
     else if (R == 1 && W == 1)
         e = launch<1, 1>(nt != 0, src, dst, units, s);
