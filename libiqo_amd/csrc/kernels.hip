@@ -635,8 +635,9 @@ __global__ __launch_bounds__(256, 3) void lanczos_stream_kernel(LanczosArgs a)
 //    needed source row are loaded out of range too (no HBM traffic).
 
 // 16-byte-per-lane LDS-DMA of one source row into LDS bytes [lds, lds + 1024) of this wave, with
-// the default cache policy (fresh data, C2: 2.7 % faster than nontemporal -- the halo rows that
-// neighbouring bands share stay in L2).  M0 is saved and restored inside the statement (it is
+// the default cache policy (fresh data, C2: 2.7 % faster than nontemporal on every row -- the halo
+// rows that neighbouring bands share stay in L2; the block-shared streamer loads the rows no other
+// band reads with dma_row_nt).  M0 is saved and restored inside the statement (it is
 // compiler-reserved).
 __device__ __forceinline__ void dma_row(uint32_t lds, int voff, __amdgpu_buffer_rsrc_t rsrc, int soff)
 {
@@ -666,9 +667,9 @@ __device__ __forceinline__ void dma_row_masked(uint32_t lds, int voff, __amdgpu_
 #define IQO_SYMB_EDGE_BATCH 16  // rows of border-column sums parked before a flush (narrow-row scheme; C2 before the line scheme: 64 -> 16 cut write traffic +4.5% -> +2%)
 #endif
 #ifndef IQO_SYMB_NT
-#define IQO_SYMB_NT 2  // block-shared streamer cache policy: nontemporal DMA loads (1) / stores (2); stores
-                       // by default (C2 x256: 0.549 -> 0.544 ms at 24 bands, 0.531 -> 0.520 at 96; nontemporal
-                       // loads lose the halo rows neighbouring bands share in L2: 0.560)
+#define IQO_SYMB_NT 2  // block-shared streamer cache policy: nontemporal DMA loads of every row (1) / stores (2);
+                       // stores by default (C2 x256: 0.549 -> 0.544 ms at 24 bands, 0.531 -> 0.520 at 96; nontemporal
+                       // loads of every row lose the halo rows neighbouring bands share in L2: 0.560)
 #endif
 // The block-shared streamer's border-column scheme: whole 128-byte pieces parked and stored once per
 // trip (rows of >= 256 outputs with >= 16 producing lanes per wave), else the divided bytes stored
@@ -705,6 +706,18 @@ __device__ __forceinline__ void dma_row_nt(uint32_t lds, int voff, __amdgpu_buff
                  "buffer_load_dwordx4 %2, %3, %4 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff)
+                 : "memory");
+}
+// dma_row_masked with the cache policy of dma_row_nt
+__device__ __forceinline__ void dma_row_masked_nt(uint32_t lds, int voff, __amdgpu_buffer_rsrc_t rsrc, int soff,
+                                                  uint64_t mask)
+{
+    uint32_t keep;
+    uint64_t save;
+    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %6\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "buffer_load_dwordx4 %3, %4, %5 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %0\n\ts_mov_b64 exec, %1"
+                 : "=&s"(keep), "=&s"(save)
+                 : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff), "s"(mask)
                  : "memory");
 }
 
@@ -1070,9 +1083,16 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     // (the last iteration brings the band's last two rows), so their offsets are one running
     // value instead of two range checks per row
     const int dmaSoff0 = (rowAt(0, NY - 2) - srcRow0) * srcSt, dmaStep = 2 * dir * srcSt, dmaNext = dir * srcSt;
+    // Cache policy by row class: the band's first NY-2 walk rows (the VGPR prologue loads) and its
+    // last NY-2 (DMA iterations j >= nRows - (NY-2)/2) are the halo rows a neighbouring band reads
+    // too, so they keep the default policy and stay in L2; the rows of every other DMA iteration
+    // are read by this band alone and go nontemporal (C2 x1024 1.822 -> 1.793 ms, x256 0.464 ->
+    // 0.454, profiles/r07/steady_ab_levers.txt).  Bands of <= (NY-2)/2 rows stay all-default.
+    const int ntEnd = nRows - (NY - 2) / 2;
     auto dma_iter = [&](int j, int slot) {
         const uint32_t s = ldsBase + static_cast<uint32_t>(slot * slotBytes);
         const bool in = j < nRows;
+        const bool nt = (IQO_SYMB_NT & 1) || j < ntEnd;  // uniform
         const int so0 = in ? dmaSoff0 + j * dmaStep : 0x7ff00000;
         const int so1 = in ? dmaSoff0 + j * dmaStep + dmaNext : 0x7ff00000;
 #pragma unroll
@@ -1084,9 +1104,14 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
             const uint32_t d0 = real ? s + 16 + 1024 * c : ldsBase + sinkLds;
             const uint32_t d1 = real ? d0 + rowPitch : d0;
             if (real && c == a.chunks - 1 && lastLanes < 64) {  // uniform
-                dma_row_masked(d0, v, srcR, so0, lastMask);
-                dma_row_masked(d1, v, srcR, so1, lastMask);
-            } else if (IQO_SYMB_NT & 1) {
+                if (nt) {
+                    dma_row_masked_nt(d0, v, srcR, so0, lastMask);
+                    dma_row_masked_nt(d1, v, srcR, so1, lastMask);
+                } else {
+                    dma_row_masked(d0, v, srcR, so0, lastMask);
+                    dma_row_masked(d1, v, srcR, so1, lastMask);
+                }
+            } else if (nt) {
                 dma_row_nt(d0, v, srcR, so0);
                 dma_row_nt(d1, v, srcR, so1);
             } else {
@@ -2758,9 +2783,15 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
             // 0.318, 20 bands 0.324); the 12- and 16-row windows keep ~22-row bands (Lanczos-4 4K:
             // 50 bands 0.267 ms, 90 bands 0.270), their per-band halo being larger
             // (profiles/r05/steady_streamer_bands.txt)
+            // Round 7, with the band's private rows loaded nontemporal: a private row costs less
+            // than a halo row, and the 10-row window (8 halo rows per band) wants bands of 15 rows
+            // -- C2 x1024 1.833 -> 1.790 ms and 1.847 -> 1.817 on two boxes, x256 0.463 -> 0.453;
+            // Lanczos-3 1080p -> 540p and 1440p -> 720p -2 % too -- while the 8-row window keeps 12
+            // (Lanczos-2 4K -> 1080p x512: 12 rows 0.859 ms, 14 0.871, 15 0.887;
+            // profiles/r07/band_sweep.txt)
             const int64_t want = static_cast<int64_t>(l.rounds > 0 ? l.rounds : 6) * (resident / wpr);
             const int64_t byRounds = (want + io.frames - 1) / io.frames;
-            const int rowsMax = l.NY <= 10 ? (l.dstW >= 640 ? 12 : 24)
+            const int rowsMax = l.NY <= 10 ? (l.dstW >= 640 ? (l.NY == 10 ? 15 : 12) : 24)
                                            : std::min(48, std::max(22, 22 * 1920 / std::max(1, l.dstW)));
             const int rowsMin = l.NY <= 10 ? 12 : 16;
             bands = static_cast<int>(std::min<int64_t>(std::max<int64_t>(byRounds, (rows + rowsMax - 1) / rowsMax),

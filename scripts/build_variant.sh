@@ -1,17 +1,29 @@
 #!/bin/bash
 # Build an experimental library variant: scripts/build_variant.sh NAME "-DFLAG=1 ..."
-# -> libiqo_amd/variants/NAME.so (kernels.hip, kernels_ratio.hip and abi.hip recompiled with the flags, the host
+# -> libiqo_amd/variants/NAME.so (every .hip translation unit recompiled with the flags, the host
 # objects shared).  -DIQO_VARIANT_DEBUG enables the wrong-output timing flags ("debug_flags").
+# KERNELS_ONLY=1 recompiles kernels.hip alone and links the in-tree build's other objects (flags
+# that only kernels.hip reads, e.g. IQO_SYMB_*).
 set -e
 cd "$(dirname "$0")/../libiqo_amd"
 make -s build/plan.o build/cpu_generic.o build/resizers.o
 mkdir -p variants
-F="-O3 -std=c++17 -fPIC -fno-strict-aliasing -I../include -Icsrc --offload-arch=gfx950 $2"
-/opt/rocm/bin/hipcc $F -c csrc/kernels.hip -o variants/$1_kernels.o &
-/opt/rocm/bin/hipcc $F -c csrc/kernels_ratio.hip -o variants/$1_kratio.o &
-/opt/rocm/bin/hipcc $F -ffp-contract=off -c csrc/abi.hip -o variants/$1_abi.o
-wait
+F="-O3 -std=c++17 -fPIC -fno-strict-aliasing -I../include -Icsrc --offload-arch=gfx950 -munsafe-fp-atomics $2"
+OBJS="variants/$1_kernels.o"
+if [ -n "$KERNELS_ONLY" ]; then
+    make -s build/kernels_ratio.o build/kernels_packed.o build/kernels_color.o build/abi.o
+    /opt/rocm/bin/hipcc $F -c csrc/kernels.hip -o variants/$1_kernels.o
+    REST="build/kernels_ratio.o build/kernels_packed.o build/kernels_color.o build/abi.o"
+else
+    for k in kernels kernels_ratio kernels_packed kernels_color; do
+        /opt/rocm/bin/hipcc $F -c csrc/$k.hip -o variants/$1_$k.o &
+    done
+    /opt/rocm/bin/hipcc $F -ffp-contract=off -c csrc/abi.hip -o variants/$1_abi.o
+    wait
+    OBJS="variants/$1_kernels.o variants/$1_kernels_ratio.o variants/$1_kernels_packed.o variants/$1_kernels_color.o variants/$1_abi.o"
+    REST=""
+fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$1.so build/plan.o build/cpu_generic.o build/resizers.o \
-    variants/$1_kernels.o variants/$1_kratio.o variants/$1_abi.o
-rm -f variants/$1_kernels.o variants/$1_kratio.o variants/$1_abi.o
+    $OBJS $REST
+rm -f $OBJS
 echo "variants/$1.so"
