@@ -299,7 +299,20 @@ struct iqo_oracle {
     uint16_t *tabXu, *tabYu;  /* Area / Linear */
     int16_t *work16, *deno16;
     uint16_t *worku;
+    iqo_oracle_stats *st; /* NULL, or the counters iqo_oracle_run_stats fills (Lanczos stages only) */
+    int rowMain;          /* the row in work16 came from resizeYmain (an interior row) */
 };
+
+/* tests/oracle_lib.py reads the struct as IQO_ORACLE_STATS_FIELDS int64 values */
+typedef char iqo_stats_layout_check[sizeof(iqo_oracle_stats) == IQO_ORACLE_STATS_FIELDS * sizeof(int64_t) ? 1 : -1];
+
+static void st_minmax(int64_t *lo, int64_t *hi, int64_t v)
+{
+    if (v < *lo)
+        *lo = v;
+    if (v > *hi)
+        *hi = v;
+}
 
 void iqo_oracle_free(iqo_oracle *o)
 {
@@ -457,6 +470,18 @@ static void lz_resize_x_border(const iqo_oracle *o, const int16_t *src, uint8_t 
         /* roundedDiv(nume, deno*kBias, 20): int16((a + 2^19) / b) -- :216-220.  deno == 0 traps
          * (SIGFPE) in the reference; such shapes are outside parity, the oracle writes 0. */
         int16_t q = deno ? (int16_t)((nume + (1 << 19)) / (deno * 64)) : 0;
+        if (o->st && deno) {
+            iqo_oracle_stats *st = o->st;
+            int32_t a = nume + (1 << 19), full = a / (deno * 64);
+            st->xb_n++;
+            st->xb_nume_neg += a < 0;
+            st->xb_deno_neg += deno < 0;
+            st->xb_dneg_nume_neg += deno < 0 && a < 0;
+            st->xb_dneg_nume_pos += deno < 0 && a > 0;
+            st->xb_q_lo += q < 0;
+            st->xb_q_hi += q > 255;
+            st->xb_q_wrap += full < -32768 || full > 32767;
+        }
         dst[dstX] = (uint8_t)clamp_i16(0, 255, q);
     }
 }
@@ -481,6 +506,15 @@ static void lz_resize_x_main(const iqo_oracle *o, const int16_t *src, uint8_t *d
             sum += src[srcOX - m + i] * (int32_t)coefs[i];
         /* convertToInt(sum, 20) -- :223-227 */
         int16_t v = (int16_t)((sum + (1 << 19)) >> 20);
+        if (o->st) {
+            iqo_oracle_stats *st = o->st;
+            st->xm_n++;
+            st->xm_neg += v < 0;
+            st->xm_hi += v > 255;
+            st_minmax(&st->xm_min, &st->xm_max, sum);
+            if (o->rowMain)
+                st_minmax(&st->xmi_min, &st->xmi_max, sum);
+        }
         dst[dstX] = (uint8_t)clamp_i16(0, 255, v);
     }
 }
@@ -528,6 +562,21 @@ static void lz_resize_y_border(iqo_oracle *o, ptrdiff_t srcSt, const uint8_t *sr
             }
         }
     }
+    if (o->st) {
+        iqo_oracle_stats *st = o->st;
+        st->yb_deno_zero_rows += deno[0] == 0;
+        for (ptrdiff_t x = 0; x < dstW && deno[0]; ++x) {
+            int n = nume[x], d = deno[x], q = n * 64 / d;
+            st->yb_n++;
+            st->yb_nume_neg += n < 0;
+            st->yb_deno_neg += d < 0;
+            st->yb_dneg_nume_neg += d < 0 && n < 0;
+            st->yb_dneg_nume_pos += d < 0 && n > 0;
+            st->yb_q_neg += q < 0;
+            st->yb_q_hi += q > 255 * 64;
+            st->yb_q_wrap += q < -32768 || q > 32767;
+        }
+    }
     for (ptrdiff_t x = 0; x < dstW; ++x) /* deno == 0 traps in the reference: outside parity */
         dst[x] = deno[x] ? (int16_t)((int)nume[x] * 64 / deno[x]) : 0;
 }
@@ -544,6 +593,15 @@ static void lz_resize_y_main(iqo_oracle *o, ptrdiff_t srcSt, const uint8_t *src,
         ptrdiff_t srcY = srcOY - m + i;
         for (ptrdiff_t x = 0; x < dstW; ++x)
             dst[x] = (int16_t)(dst[x] + src[x + srcSt * srcY] * coef);
+    }
+    if (o->st) {
+        iqo_oracle_stats *st = o->st;
+        for (ptrdiff_t x = 0; x < dstW; ++x) {
+            st->ym_n++;
+            st->ym_neg += dst[x] < 0;
+            st->ym_hi += dst[x] > 255 * 64;
+            st_minmax(&st->ym_min, &st->ym_max, dst[x]);
+        }
     }
 }
 
@@ -577,6 +635,7 @@ static void lz_resize(iqo_oracle *o, size_t srcSt_, const uint8_t *src, size_t d
         iTable += o->nY;
         if (iTable == tableSize)
             iTable = 0;
+        o->rowMain = 0;
         lz_resize_y_border(o, srcSt, src, work, srcOY, coefs);
         lz_resize_x(o, work, &dst[dstSt * dstY]);
     }
@@ -586,6 +645,7 @@ static void lz_resize(iqo_oracle *o, size_t srcSt_, const uint8_t *src, size_t d
         iTable += o->nY;
         if (iTable == tableSize)
             iTable = 0;
+        o->rowMain = 1;
         lz_resize_y_main(o, srcSt, src, work, srcOY, coefs);
         lz_resize_x(o, work, &dst[dstSt * dstY]);
     }
@@ -595,6 +655,7 @@ static void lz_resize(iqo_oracle *o, size_t srcSt_, const uint8_t *src, size_t d
         iTable += o->nY;
         if (iTable == tableSize)
             iTable = 0;
+        o->rowMain = 0;
         lz_resize_y_border(o, srcSt, src, work, srcOY, coefs);
         lz_resize_x(o, work, &dst[dstSt * dstY]);
     }
@@ -791,15 +852,28 @@ void iqo_oracle_resize(iqo_oracle *o, size_t srcSt, const uint8_t *src, size_t d
         ln_resize(o, srcSt, src, dstSt, dst);
 }
 
-int iqo_oracle_run(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
-                   size_t pxScale, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst)
+int iqo_oracle_run_stats(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                         size_t pxScale, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst,
+                         iqo_oracle_stats *st)
 {
     iqo_oracle *o = iqo_oracle_new(method, degree, srcW, srcH, dstW, dstH, pxScale);
     if (!o)
         return -1;
+    if (st) {
+        memset(st, 0, sizeof(*st));
+        st->ym_min = st->xm_min = st->xmi_min = INT64_MAX;
+        st->ym_max = st->xm_max = st->xmi_max = INT64_MIN;
+    }
+    o->st = st;
     iqo_oracle_resize(o, srcSt, src, dstSt, dst);
     iqo_oracle_free(o);
     return 0;
+}
+
+int iqo_oracle_run(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                   size_t pxScale, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst)
+{
+    return iqo_oracle_run_stats(method, degree, srcW, srcH, dstW, dstH, pxScale, srcSt, src, dstSt, dst, NULL);
 }
 
 typedef struct {

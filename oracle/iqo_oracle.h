@@ -41,6 +41,28 @@ int iqo_oracle_table(const iqo_oracle *o, int axis, int *nTaps, int *nPhases, in
 int iqo_oracle_run(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                    size_t pxScale, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst);
 
+/* What the Lanczos stages of one resize saw (all fields int64_t, so a flat array of
+ * IQO_ORACLE_STATS_FIELDS values; the names are tests/oracle_lib.STATS_FIELDS).  Area and Linear
+ * record nothing.  min / max stay INT64_MAX / INT64_MIN where a stage never ran.
+ *   Y main   (resizeYmain):   the int16 work value of every interior row
+ *   Y border (resizeYborder): every nume * 64 / deno; the quotient before its int16 cast
+ *   X main   (resizeXmain):   v = int16((sum + 2^19) >> 20) before the clamp; the int32 sum, over
+ *                             all rows (xm_min/max) and over interior rows only (xmi_min/max)
+ *   X border (resizeXborder): every (nume + 2^19) / (deno * 64); "nume" below is nume + 2^19 */
+typedef struct {
+    int64_t ym_n, ym_neg, ym_hi, ym_min, ym_max;
+    int64_t yb_n, yb_nume_neg, yb_deno_neg, yb_dneg_nume_neg, yb_dneg_nume_pos, yb_q_neg, yb_q_hi, yb_q_wrap,
+        yb_deno_zero_rows;
+    int64_t xm_n, xm_neg, xm_hi, xm_min, xm_max, xmi_min, xmi_max;
+    int64_t xb_n, xb_nume_neg, xb_deno_neg, xb_dneg_nume_neg, xb_dneg_nume_pos, xb_q_lo, xb_q_hi, xb_q_wrap;
+} iqo_oracle_stats;
+#define IQO_ORACLE_STATS_FIELDS 29
+
+/* iqo_oracle_run through the same functions, counting into *st (NULL: iqo_oracle_run itself). */
+int iqo_oracle_run_stats(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                         size_t pxScale, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst,
+                         iqo_oracle_stats *st);
+
 /* CPU baseline: resize nFrames frames (frame strides in bytes) with nThreads std-thread-style
  * workers (pthreads), one oracle instance per worker (instances are not re-entrant, exactly like
  * the reference's Generic impl).  Returns elapsed seconds (wall clock, CLOCK_MONOTONIC). */

@@ -43,6 +43,8 @@ def oracle():
         lib.iqo_oracle_run.restype = ctypes.c_int
         lib.iqo_oracle_run.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz,
                                        _c_sz, _u8p, _c_sz, _u8p]
+        lib.iqo_oracle_run_stats.restype = ctypes.c_int
+        lib.iqo_oracle_run_stats.argtypes = lib.iqo_oracle_run.argtypes + [ctypes.POINTER(ctypes.c_int64)]
         lib.iqo_oracle_new.restype = ctypes.c_void_p
         lib.iqo_oracle_new.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz]
         lib.iqo_oracle_free.argtypes = [ctypes.c_void_p]
@@ -210,6 +212,30 @@ def run_oracle(method, degree, sw, sh, dw, dh, px, src, dst_st=None):
     rc = oracle().iqo_oracle_run(METHODS[method], degree, sw, sh, dw, dh, px, src.shape[1], _ptr(src), dst_st, _ptr(dst))
     assert rc == 0
     return dst[:, :dw]
+
+
+# iqo_oracle_stats (oracle/iqo_oracle.h), field by field
+STATS_FIELDS = ("ym_n ym_neg ym_hi ym_min ym_max "
+                "yb_n yb_nume_neg yb_deno_neg yb_dneg_nume_neg yb_dneg_nume_pos yb_q_neg yb_q_hi yb_q_wrap "
+                "yb_deno_zero_rows "
+                "xm_n xm_neg xm_hi xm_min xm_max xmi_min xmi_max "
+                "xb_n xb_nume_neg xb_deno_neg xb_dneg_nume_neg xb_dneg_nume_pos xb_q_lo xb_q_hi xb_q_wrap").split()
+
+
+assert len(STATS_FIELDS) == 29  # IQO_ORACLE_STATS_FIELDS
+
+
+def run_oracle_stats(method, degree, sw, sh, dw, dh, px, src, dst_st=None):
+    """run_oracle through iqo_oracle_run_stats: (dst, what each Lanczos stage saw, as a dict of STATS_FIELDS)."""
+    assert method != "lanczos" or lanczos_rows_defined(degree, sh, dh, px), "no defined answer: never run on this shape"
+    src = np.ascontiguousarray(src)
+    dst_st = dst_st or dw
+    dst = np.zeros((dh, dst_st), dtype=np.uint8)
+    st = (ctypes.c_int64 * len(STATS_FIELDS))()
+    rc = oracle().iqo_oracle_run_stats(METHODS[method], degree, sw, sh, dw, dh, px, src.shape[1], _ptr(src), dst_st,
+                                       _ptr(dst), st)
+    assert rc == 0
+    return dst[:, :dw], dict(zip(STATS_FIELDS, (int(v) for v in st)))
 
 
 def run_ref(method, degree, sw, sh, dw, dh, px, src, strict=False):
