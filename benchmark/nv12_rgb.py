@@ -6,7 +6,7 @@ the int32 matrix, the clamps, float32(byte) * scale + bias, the cast).  Device-r
 rotated so that no timed step reads a batch the previous step left in the caches.  Not the headline
 metric (bench.py).
 
-  python benchmark/nv12_rgb.py [--frames 64] [--steps 10] [--reps 5] [--only 1080p-224]
+  python benchmark/nv12_rgb.py [--frames 64] [--steps 10] [--reps 5] [--only 1080p-224] [--chroma full]
 
 Prints one JSON line per configuration: ms per batch of both paths (the median of `reps` alternated
 windows of `steps` batches between device events, and every window), their ratio, the plane resize
@@ -14,6 +14,13 @@ alone, and -- as an estimate of the second pass -- the difference of the new pat
 with the bytes it moves, beside the on-box streaming probe of the pass's own read:write mix
 (libiqo_probe.so: 1.5 : 6 = 1 : 4 for fp16, 1.5 : 12 = 1 : 8 for fp32; a probe, not a ceiling).  The
 two paths are compared bit for bit before they are timed.
+
+--chroma full times Nv12Resizer(chroma="full") -- chroma filtered to the full output grid -- against what
+a caller can compose without it: a planar resizer for Y, a 2-channel packed resizer srcW/2 x srcH/2 ->
+dstW x dstH for UV (pxScale 1), and the same integer matrix per pixel in torch.  Its lines carry
+"chroma": "full", the two plane resizes alone instead of resize_frames, and whether every window of the
+new path was faster than every window of the composition; no streaming probe.  The default, --chroma
+replicate, prints the lines described above, unchanged.
 """
 import argparse
 import json
@@ -49,6 +56,26 @@ def composition(r, src, scale_t, bias_t, dtype):
     return (rgb * scale_t + bias_t).to(dtype)
 
 
+def composition_full(ry, ruv, src, ybuf, uvbuf, scale_t, bias_t, dtype, stream, planes_only=False):
+    """chroma="full" without the library's entry: Y and the UV plane resized to dstW x dstH by two resizers
+    straight from the NV12 frames (no copy), the rest in torch."""
+    import torch
+    sw, sh, dw, dh = ry.srcW, ry.srcH, ry.dstW, ry.dstH
+    n, b = src.shape[0], src.data_ptr()
+    ry.resize_device(n, sw, src.stride(0), b, dw, dw * dh, ybuf, stream)
+    ruv.resize_device(n, 2 * (sw // 2), src.stride(0), b + sw * sh, 2 * dw, 2 * dw * dh, uvbuf, stream)
+    if planes_only:
+        return None
+    yoff, cy, crv, cgu, cgv, cbu = BT709
+    y = ybuf.to(torch.int32) - yoff
+    uv = uvbuf.to(torch.int32) - 128
+    u, v = uv[..., 0], uv[..., 1]
+    lum = cy * y + 8192
+    rgb = torch.stack([lum + crv * v, lum - cgu * u - cgv * v, lum + cbu * u], dim=1)
+    rgb = (rgb >> 14).clamp_(0, 255).to(torch.float32)
+    return (rgb * scale_t + bias_t).to(dtype)
+
+
 def windows(step, stream, dev, steps):
     import torch
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -72,6 +99,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default="", help="a shape name of SHAPES")
+    ap.add_argument("--chroma", choices=("replicate", "full"), default="replicate")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU: a timing without one says nothing"
     dev = torch.device("cuda", 0)
@@ -92,7 +120,13 @@ def main():
         nb = max(2, -(-(640 << 20) // (n * ins)))
         srcs = [torch.randint(0, 256, (n, ins), dtype=torch.uint8, device=dev, generator=g) for _ in range(nb)]
         for mname, (m, d) in METHODS.items():
-            r = libiqo_amd.Nv12Resizer(m, d, sw, sh, dw, dh)
+            full = args.chroma == "full"
+            r = libiqo_amd.Nv12Resizer(m, d, sw, sh, dw, dh, chroma=args.chroma)
+            if full:
+                ry = libiqo_amd.make_resizer(m, d, sw, sh, dw, dh)
+                ruv = libiqo_amd.make_resizer(m, d, sw // 2, sh // 2, dw, dh, 1, channels=2)
+                ybuf = torch.empty((n, dh, dw), dtype=torch.uint8, device=dev)
+                uvbuf = torch.empty((n, dh, dw, 2), dtype=torch.uint8, device=dev)
             planes_out = torch.empty((n, dw * dh + 2 * (dw // 2) * (dh // 2)), dtype=torch.uint8, device=dev)
             for dname, dtype in (("fp16", torch.float16), ("fp32", torch.float32)):
                 out = torch.empty((n, 3, dh, dw), dtype=dtype, device=dev)
@@ -104,15 +138,21 @@ def main():
 
                 def old():
                     k[1] += 1
+                    if full:
+                        return composition_full(ry, ruv, srcs[k[1] % nb], ybuf, uvbuf, scale_t, bias_t, dtype, stream)
                     return composition(r, srcs[k[1] % nb], scale_t, bias_t, dtype)
 
                 def first():
                     k[2] += 1
-                    r.resize_frames(srcs[k[2] % nb], planes_out)
+                    if full:
+                        composition_full(ry, ruv, srcs[k[2] % nb], ybuf, uvbuf, scale_t, bias_t, dtype, stream, True)
+                    else:
+                        r.resize_frames(srcs[k[2] % nb], planes_out)
 
                 # the same bits first
                 a = r.resize_normalized(srcs[0], scale, bias, standard="bt709", dtype=dtype)
-                b = composition(r, srcs[0], scale_t, bias_t, dtype)
+                b = (composition_full(ry, ruv, srcs[0], ybuf, uvbuf, scale_t, bias_t, dtype, stream) if full
+                     else composition(r, srcs[0], scale_t, bias_t, dtype))
                 bits = torch.int32 if dtype == torch.float32 else torch.int16
                 same = bool(torch.equal(a.view(bits), b.view(bits)))
                 del a, b
@@ -129,7 +169,7 @@ def main():
                 ms_new, ms_old, ms_first = (statistics.median(t) for t in (t_new, t_old, t_first))
                 elem = out.element_size()
                 # second pass: reads the resized planes, writes three float planes
-                pass2_bytes = n * (dw * dh + 2 * (dw // 2) * (dh // 2) + 3 * dw * dh * elem)
+                pass2_bytes = n * ((3 * dw * dh if full else dw * dh + 2 * (dw // 2) * (dh // 2)) + 3 * dw * dh * elem)
                 pass2_ms = ms_new - ms_first
                 line = {"workload": "NV12 %s %s -> normalised RGB %s" % (sname, mname, dname), "frames": n,
                         "kernels": list(r.describe()), "bit_identical": same,
@@ -142,8 +182,14 @@ def main():
                             "ms": round(pass2_ms, 4), "bytes": pass2_bytes,
                             "gb_s": round(pass2_bytes / (pass2_ms / 1e3) / 1e9, 1) if pass2_ms > 0 else None,
                             "note": "new_ms - resize_frames_ms; launch gaps included"}}
+                if full:
+                    line["chroma"] = "full"
+                    line["kernels"].append(r.chroma_kernel())
+                    line["plane_resizes_ms"] = line.pop("resize_frames_ms")
+                    line["every_new_window_faster"] = max(t_new) < min(t_old)
+                    line["second_pass_estimate"]["note"] = "new_ms - plane_resizes_ms; launch gaps included"
                 # the streaming probe at the second pass's own mix, on buffers of its size
-                if pass2_bytes >= (8 << 20):
+                elif pass2_bytes >= (8 << 20):
                     mix = (1, 2 * elem)  # 1.5 bytes read per 3 * elem written
                     rb, wb = pass2_bytes // (1 + mix[1]), pass2_bytes // (1 + mix[1]) * mix[1]
                     ps = torch.empty((2, rb), dtype=torch.uint8, device=dev)
@@ -153,6 +199,8 @@ def main():
                 print(json.dumps(line), flush=True)
                 del out
             del r, planes_out
+            if full:
+                del ry, ruv, ybuf, uvbuf
         del srcs
         torch.cuda.empty_cache()
 

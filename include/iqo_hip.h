@@ -208,7 +208,8 @@ typedef struct iqo_hip_yuv_plan iqo_hip_yuv_plan;
 int iqo_hip_plan_yuv420(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                         int device, iqo_hip_yuv_plan **out);
 void iqo_hip_yuv_plan_destroy(iqo_hip_yuv_plan *plan);
-/* Plane 0 = the luma plan, 1 = the chroma plan (for iqo_hip_plan_set_option / _query). */
+/* Plane 0 = the luma plan, 1 = the chroma plan (for iqo_hip_plan_set_option / _query), 2 = the
+ * full-grid chroma plan of IQO_CHROMA_FULL (NULL before iqo_hip_yuv_plan_set_chroma built it). */
 iqo_hip_plan *iqo_hip_yuv_plane(iqo_hip_yuv_plan *plan, int plane);
 /* Device-resident batch, asynchronous on `stream`: frame f's planes start at srcY/srcU/srcV +
  * f*srcFrameSt (likewise dst).  All three planes go in ONE launch when the plane kernels have a
@@ -232,7 +233,8 @@ typedef struct iqo_hip_nv12_plan iqo_hip_nv12_plan;
 int iqo_hip_plan_nv12(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                       int device, iqo_hip_nv12_plan **out);
 void iqo_hip_nv12_plan_destroy(iqo_hip_nv12_plan *plan);
-/* Plane 0 = the luma plan, 1 = the packed UV plan (for iqo_hip_plan_set_option / _query). */
+/* Plane 0 = the luma plan, 1 = the packed UV plan (for iqo_hip_plan_set_option / _query), 2 = the
+ * full-grid UV plan of IQO_CHROMA_FULL (NULL before iqo_hip_nv12_plan_set_chroma built it). */
 iqo_hip_plan *iqo_hip_nv12_plane(iqo_hip_nv12_plan *plan, int plane);
 /* Device-resident batch, asynchronous on `stream`: frame f's planes start at srcY / srcUV +
  * f*srcFrameSt (likewise dst). */
@@ -288,8 +290,51 @@ int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t s
  * row, a source plane that reaches 2^31 bytes or a source stride >= 2^24; workspaceBytes below the
  * query's value.  On any error nothing is launched and the destination is untouched. */
 enum { IQO_CS_BT601_LIMITED = 0, IQO_CS_BT601_FULL = 1, IQO_CS_BT709_LIMITED = 2, IQO_CS_BT709_FULL = 3 };
+/* How the four calls bring chroma to the output grid; a property of the NV12 / I420 plan.
+ *
+ * IQO_CHROMA_REPLICATE (the default): the definition above.
+ * IQO_CHROMA_FULL: chroma is filtered straight to the output grid (4:4:4) instead of being resized to
+ * half size and doubled.  Y is exactly the bytes of the plan's Y plane, as above.  U and V are exactly
+ * the bytes a resizer of the plan's method and degree writes for srcW/2 x srcH/2 -> dstW x dstH (the
+ * 2-channel packed resizer for NV12, the planar one for I420, which agree); Lanczos uses pxScale 1 --
+ * pxScale 2 keeps a half-size chroma output in step with luma, but here the output grid is the luma
+ * grid, and pxScale 2 would cut Lanczos-3 to one lobe on down-scales.  Pixel (y, x) takes chroma sample
+ * (y, x): no shift and no clamp of the index.  The matrix, the rounding and the clamps are unchanged.
+ * The resizers map centre to centre, so chroma is treated as sited at the centre of its 2 x 2 luma
+ * block, as the plane resizes treat it; left-sited chroma is not addressed.
+ *
+ * iqo_hip_*_plan_set_chroma selects the mode for iqo_hip_resize_{nv12,yuv420}_{rgb,norm}_device only;
+ * the plane resizes (iqo_hip_resize_nv12_device, iqo_hip_resize_yuv420_device, iqo_hip_resize_yuv420)
+ * are the same in either mode.  The first IQO_CHROMA_FULL builds one more sub-plan, srcW/2 x srcH/2 ->
+ * dstW x dstH at pxScale 1 (NV12: 2-channel packed; I420: planar, run for U and then for V), which
+ * iqo_hip_nv12_plane / iqo_hip_yuv_plane return as plane 2 (NULL before that) for
+ * iqo_hip_plan_prepare, _query and _set_option; it is kept when the mode goes back.  Call it before the
+ * plan is used from other threads or captured into a graph.  In IQO_CHROMA_FULL the first pass is one
+ * launch per plane (NV12 two, I420 three; *fused reports 0), and the workspace is larger:
+ * iqo_hip_yuv_rgb_workspace_bytes_chroma with the plan's mode is what workspaceBytes is checked against.
+ *
+ * Returns (the mode keeps its value on any error): IQO_HIP_EINVAL for a null plan or a mode other than
+ * the two; IQO_HIP_EUNSUP for Linear with dstW > 2*(srcW/2) or dstH > 2*(srcH/2), a Linear up-scale of
+ * chroma above 2x, which has no pinned answer; and what the plan constructor returns for the chroma
+ * shape -- IQO_HIP_EINVAL for a Lanczos shape it rejects, which exist under NV12 / I420 plans it accepts
+ * (Lanczos-3 16x3 -> 16x3: the full-grid chroma plane is 8x1 -> 16x3). */
+enum { IQO_CHROMA_REPLICATE = 0, IQO_CHROMA_FULL = 1 };
+int iqo_hip_nv12_plan_set_chroma(iqo_hip_nv12_plan *plan, int mode);
+int iqo_hip_yuv_plan_set_chroma(iqo_hip_yuv_plan *plan, int mode);
+/* The plan's mode; IQO_HIP_EINVAL for a null plan. */
+int iqo_hip_nv12_plan_chroma(const iqo_hip_nv12_plan *plan);
+int iqo_hip_yuv_plan_chroma(const iqo_hip_yuv_plan *plan);
+/* Host-only, no GPU: the IQO_KERNEL_* family of the full-grid chroma sub-plan of such a plan
+ * (interleavedUV != 0: NV12's packed plan; 0: I420's planar plan, 16-byte-aligned layout), or the
+ * negative status set_chroma(IQO_CHROMA_FULL) would return. */
+int iqo_host_yuv_chroma_full_kernel(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                                    int interleavedUV);
 /* Host-only.  The layout of the workspace is internal. */
 size_t iqo_hip_yuv_rgb_workspace_bytes(size_t dstW, size_t dstH, size_t nFrames);
+/* ... for a plan in chroma mode `mode`: IQO_CHROMA_REPLICATE is the value above; IQO_CHROMA_FULL holds
+ * U and V at dstH rows of dstW samples (rows padded as Y's), three bytes per output pixel.  Saturates
+ * at SIZE_MAX instead of wrapping, as the function above; SIZE_MAX for an unknown mode. */
+size_t iqo_hip_yuv_rgb_workspace_bytes_chroma(size_t dstW, size_t dstH, size_t nFrames, int mode);
 int iqo_hip_resize_nv12_rgb_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
                                    size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, int standard,
                                    int channels, const int *order /* [4] */, size_t dstSt, size_t dstFrameSt,

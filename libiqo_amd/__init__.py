@@ -16,7 +16,8 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_yuv420_fused", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
            "ipc_close", "KERNELS", "YUV420_FUSED", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16",
            "CS_BT601_LIMITED", "CS_BT601_FULL", "CS_BT709_LIMITED", "CS_BT709_FULL", "COLOR_STANDARDS", "RGB_ORDERS",
-           "host_yuv_to_rgb", "yuv_rgb_workspace_bytes"]
+           "host_yuv_to_rgb", "yuv_rgb_workspace_bytes", "CHROMA_REPLICATE", "CHROMA_FULL", "CHROMA_MODES",
+           "host_chroma_full_kernel"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -56,6 +57,9 @@ COLOR_STANDARDS = {"bt601": CS_BT601_LIMITED, "bt601-full": CS_BT601_FULL, "bt70
                    "bt709-full": CS_BT709_FULL}
 # packed byte orders of resize_rgb: the source of each byte of a pixel (0 R, 1 G, 2 B, 3 the constant 255)
 RGB_ORDERS = {"rgb": (0, 1, 2), "bgr": (2, 1, 0), "rgba": (0, 1, 2, 3), "bgra": (2, 1, 0, 3)}
+# IQO_CHROMA_*: chroma resized to half the output and replicated 2 x 2, or filtered to the full output grid
+CHROMA_REPLICATE, CHROMA_FULL = 0, 1
+CHROMA_MODES = {"replicate": CHROMA_REPLICATE, "full": CHROMA_FULL}
 
 
 class IpcHandle(ctypes.Structure):
@@ -133,6 +137,13 @@ def lib():
     L.iqo_hip_resize_yuv420_rgb_device.argtypes = src_i420 + to_rgb + [ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_resize_yuv420_norm_device.argtypes = src_i420 + to_norm + [ctypes.POINTER(ctypes.c_int)]
     L.iqo_host_yuv_to_rgb.argtypes = [ctypes.c_int, _c_sz, _vp, _vp, _vp, _vp]
+    L.iqo_hip_yuv_rgb_workspace_bytes_chroma.argtypes = [_c_sz, _c_sz, _c_sz, ctypes.c_int]
+    L.iqo_hip_yuv_rgb_workspace_bytes_chroma.restype = _c_sz
+    for name in ("iqo_hip_nv12_plan_set_chroma", "iqo_hip_yuv_plan_set_chroma"):
+        getattr(L, name).argtypes = [_vp, ctypes.c_int]
+    for name in ("iqo_hip_nv12_plan_chroma", "iqo_hip_yuv_plan_chroma"):
+        getattr(L, name).argtypes = [_vp]
+    L.iqo_host_yuv_chroma_full_kernel.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -242,9 +253,29 @@ def _standard(standard):
     return int(standard)
 
 
-def yuv_rgb_workspace_bytes(dstW, dstH, nFrames):
-    """Bytes of device workspace the resize_rgb / resize_normalized calls of the YUV resizers need -- host only."""
-    return int(lib().iqo_hip_yuv_rgb_workspace_bytes(dstW, dstH, nFrames))
+def _chroma(chroma):
+    """IQO_CHROMA_* of a name in CHROMA_MODES."""
+    if not isinstance(chroma, str) or chroma not in CHROMA_MODES:
+        raise IqoError("chroma must be one of %s" % ", ".join(sorted(CHROMA_MODES)))
+    return CHROMA_MODES[chroma]
+
+
+def yuv_rgb_workspace_bytes(dstW, dstH, nFrames, chroma="replicate"):
+    """Bytes of device workspace the resize_rgb / resize_normalized calls of a YUV resizer in chroma mode
+    `chroma` need -- host only."""
+    return int(lib().iqo_hip_yuv_rgb_workspace_bytes_chroma(dstW, dstH, nFrames, _chroma(chroma)))
+
+
+def host_chroma_full_kernel(method, degree, srcW, srcH, dstW, dstH, layout="nv12"):
+    """Kernel family of the full-grid chroma plan (srcW/2 x srcH/2 -> dstW x dstH, pxScale 1) of a YUV resizer
+    with chroma="full": Nv12Resizer's 2-channel packed plan (layout "nv12") or Yuv420Resizer's planar plan
+    ("i420") -- host only, no GPU.  Raises IqoError, with the status chroma="full" would fail with, for a
+    shape that has no such plan."""
+    if layout not in ("nv12", "i420"):
+        raise IqoError("layout must be nv12 or i420")
+    k = lib().iqo_host_yuv_chroma_full_kernel(_METHODS[method], degree, srcW, srcH, dstW, dstH, int(layout == "nv12"))
+    _check(k if k < 0 else 0, "host_chroma_full_kernel")
+    return KERNELS[k]
 
 
 def host_yuv_to_rgb(standard, y, u, v):
@@ -478,7 +509,35 @@ def make_resizer(method, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None,
 class _YuvToRgb:
     """resize_rgb / resize_normalized of the two YUV 4:2:0 resizers: the planes resized as resize_frames
     does, then the integer YUV -> RGB matrix of include/iqo_hip.h (IQO_CS_*) with chroma replicated to the
-    output grid, in one more kernel.  The subclass supplies _frame_bytes() and _to_rgb() / _to_norm()."""
+    output grid, in one more kernel.  With chroma="full" (IQO_CHROMA_FULL) U and V are instead resized
+    srcW/2 x srcH/2 -> dstW x dstH (Lanczos: pxScale 1) and every pixel takes its own chroma sample.  The
+    subclass supplies _frame_bytes(), _to_rgb() / _to_norm() and the names _SET_CHROMA / _PLANE of its C
+    entries."""
+
+    chroma = "replicate"
+
+    def set_chroma(self, chroma):
+        """"replicate" or "full" for the later resize_rgb / resize_normalized calls (resize_frames is the same
+        in either mode).  The first "full" builds the full-grid chroma plan (plane 2 of set_option); on an
+        error (IqoError) the mode stays.  Not while another thread or a captured graph uses the resizer."""
+        mode = _chroma(chroma)
+        _check(getattr(lib(), self._SET_CHROMA)(self._plan, mode), "%s chroma=%r" % (type(self).__name__, chroma))
+        self.chroma = chroma
+
+    def chroma_kernel(self):
+        """Kernel name of the full-grid chroma plan, None before the first chroma="full"."""
+        p = getattr(lib(), self._PLANE)(self._plan, 2)
+        if not p:
+            return None
+        d = PlanDesc()
+        _check(lib().iqo_hip_plan_query(p, ctypes.byref(d)), "query")
+        return KERNELS.get(d.kernel, d.kernel)
+
+    def _plane(self, plane):
+        p = getattr(lib(), self._PLANE)(self._plan, plane)
+        if not p:
+            raise IqoError("plane %r: no such sub-plan (plane 2 exists after chroma=\"full\")" % (plane,))
+        return p
 
     def _src_frames(self, src):
         import torch
@@ -495,7 +554,7 @@ class _YuvToRgb:
         a raw stream handle the resizer must outlive the work it queued; a torch Stream is also recorded on
         the block, which then outlives the resizer as long as that stream needs it."""
         import torch
-        nbytes = yuv_rgb_workspace_bytes(self.dstW, self.dstH, src.shape[0])
+        nbytes = yuv_rgb_workspace_bytes(self.dstW, self.dstH, src.shape[0], self.chroma)
         cache = self.__dict__.setdefault("_ws", {})
         key = (src.device, _stream_ptr(stream))
         ws = cache.get(key)
@@ -575,15 +634,21 @@ class _YuvToRgb:
 
 class Yuv420Resizer(_YuvToRgb):
     """I420 three-plane resizer: the reference benchmark's workload (benchmark.cpp:131-229), Y at
-    full size and U, V at half size with the same method (Lanczos chroma: pxScale 2)."""
+    full size and U, V at half size with the same method (Lanczos chroma: pxScale 2).  chroma: "replicate" or
+    "full", how resize_rgb / resize_normalized bring chroma to the output grid (_YuvToRgb)."""
 
-    def __init__(self, method, degree, srcW, srcH, dstW, dstH, device=None):
+    _SET_CHROMA, _PLANE = "iqo_hip_yuv_plan_set_chroma", "iqo_hip_yuv_plane"
+
+    def __init__(self, method, degree, srcW, srcH, dstW, dstH, device=None, chroma="replicate"):
+        mode = _chroma(chroma)
         self.method, self.degree = method, int(degree)
         self.srcW, self.srcH, self.dstW, self.dstH = int(srcW), int(srcH), int(dstW), int(dstH)
         self.device = 0 if device is None else int(device)
         self._plan = _vp()
         _check(lib().iqo_hip_plan_yuv420(_METHODS[method], self.degree, self.srcW, self.srcH, self.dstW, self.dstH,
                                          self.device, ctypes.byref(self._plan)), "Yuv420Resizer")
+        if mode != CHROMA_REPLICATE:
+            self.set_chroma(chroma)
 
     def __del__(self):
         p = getattr(self, "_plan", None)
@@ -592,9 +657,9 @@ class Yuv420Resizer(_YuvToRgb):
             self._plan = _vp()
 
     def set_option(self, key, value, plane=None):
+        """plane: 0 luma, 1 chroma, 2 the full-grid chroma plan of chroma="full"; None: planes 0 and 1."""
         for pl in ((0, 1) if plane is None else (plane,)):
-            _check(lib().iqo_hip_plan_set_option(lib().iqo_hip_yuv_plane(self._plan, pl), key.encode(), int(value)),
-                   "set_option")
+            _check(lib().iqo_hip_plan_set_option(self._plane(pl), key.encode(), int(value)), "set_option")
 
     def resize(self, srcStY, srcY, srcStUV, srcU, srcV, dstStY, dstY, dstStUV, dstU, dstV):
         """Host pointers, synchronous."""
@@ -659,15 +724,21 @@ class Yuv420Resizer(_YuvToRgb):
 
 class Nv12Resizer(_YuvToRgb):
     """NV12 resizer: a planar Y plane at full size and one interleaved UV plane at half size, with
-    the same method (Lanczos chroma: pxScale 2).  U and V come out as Yuv420Resizer's planes do."""
+    the same method (Lanczos chroma: pxScale 2).  U and V come out as Yuv420Resizer's planes do.  chroma:
+    "replicate" or "full", how resize_rgb / resize_normalized bring chroma to the output grid (_YuvToRgb)."""
 
-    def __init__(self, method, degree, srcW, srcH, dstW, dstH, device=None):
+    _SET_CHROMA, _PLANE = "iqo_hip_nv12_plan_set_chroma", "iqo_hip_nv12_plane"
+
+    def __init__(self, method, degree, srcW, srcH, dstW, dstH, device=None, chroma="replicate"):
+        mode = _chroma(chroma)
         self.method, self.degree = method, int(degree)
         self.srcW, self.srcH, self.dstW, self.dstH = int(srcW), int(srcH), int(dstW), int(dstH)
         self.device = 0 if device is None else int(device)
         self._plan = _vp()
         _check(lib().iqo_hip_plan_nv12(_METHODS[method], self.degree, self.srcW, self.srcH, self.dstW, self.dstH,
                                        self.device, ctypes.byref(self._plan)), "Nv12Resizer")
+        if mode != CHROMA_REPLICATE:
+            self.set_chroma(chroma)
 
     def __del__(self):
         p = getattr(self, "_plan", None)
@@ -676,9 +747,9 @@ class Nv12Resizer(_YuvToRgb):
             self._plan = _vp()
 
     def set_option(self, key, value, plane=None):
+        """plane: 0 luma, 1 UV, 2 the full-grid UV plan of chroma="full"; None: planes 0 and 1."""
         for pl in ((0, 1) if plane is None else (plane,)):
-            _check(lib().iqo_hip_plan_set_option(lib().iqo_hip_nv12_plane(self._plan, pl), key.encode(), int(value)),
-                   "set_option")
+            _check(lib().iqo_hip_plan_set_option(self._plane(pl), key.encode(), int(value)), "set_option")
 
     def describe(self):
         """Kernel names of the (Y, UV) plans."""

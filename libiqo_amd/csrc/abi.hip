@@ -2084,7 +2084,45 @@ int iqo_hip_resize(iqo_hip_plan *h, size_t srcSt, const uint8_t *src, size_t dst
 
 struct iqo_hip_yuv_plan {
     iqo_hip_plan *y = nullptr, *c = nullptr;  // luma plan, chroma plan (shared by U and V)
+    iqo_hip_plan *cf = nullptr;               // full-grid chroma plan (iqo_hip_yuv_plan_set_chroma), shared likewise
+    int chroma = IQO_CHROMA_REPLICATE;        // of the RGB / norm entries
 };
+
+// The full-grid chroma plan of IQO_CHROMA_FULL under the luma plan hy: srcW/2 x srcH/2 -> dstW x dstH at
+// pxScale 1, `channels` 1 (I420) or 2 (NV12).  chroma_full_status: what rules a shape out before any
+// plan is built.
+static int chroma_full_status(int method, size_t srcW, size_t srcH, size_t dstW, size_t dstH)
+{
+    // Linear above 2x has no pinned answer (README, "Shapes without a pinned answer")
+    if (method == IQO_METHOD_LINEAR && (dstW > 2 * (srcW / 2) || dstH > 2 * (srcH / 2)))
+        return IQO_HIP_EUNSUP;
+    return IQO_HIP_OK;
+}
+
+static int chroma_full_plan(const iqo_hip_plan *hy, int channels, iqo_hip_plan **out)
+{
+    const Plan &p = hy->p;
+    const size_t sw = static_cast<size_t>(p.srcW), sh = static_cast<size_t>(p.srcH);
+    const size_t dw = static_cast<size_t>(p.dstW), dh = static_cast<size_t>(p.dstH);
+    const int rc = chroma_full_status(static_cast<int>(p.method), sw, sh, dw, dh);
+    if (rc)
+        return rc;
+    return iqo_hip_plan_packed(static_cast<int>(p.method), p.degree, channels, sw / 2, sh / 2, dw, dh, 1, hy->device, out);
+}
+
+// iqo_hip_{nv12,yuv}_plan_set_chroma on the plan's three members
+static int set_chroma(const iqo_hip_plan *hy, int channels, iqo_hip_plan **cf, int *chroma, int mode)
+{
+    if (mode != IQO_CHROMA_REPLICATE && mode != IQO_CHROMA_FULL)
+        return IQO_HIP_EINVAL;
+    if (mode == IQO_CHROMA_FULL && !*cf) {
+        const int rc = chroma_full_plan(hy, channels, cf);
+        if (rc)
+            return rc;
+    }
+    *chroma = mode;
+    return IQO_HIP_OK;
+}
 
 int iqo_hip_plan_yuv420(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, int device,
                         iqo_hip_yuv_plan **out)
@@ -2126,6 +2164,7 @@ void iqo_hip_yuv_plan_destroy(iqo_hip_yuv_plan *yp)
         return;
     iqo_hip_plan_destroy(yp->y);
     iqo_hip_plan_destroy(yp->c);
+    iqo_hip_plan_destroy(yp->cf);
     delete yp;
 }
 
@@ -2133,8 +2172,17 @@ iqo_hip_plan *iqo_hip_yuv_plane(iqo_hip_yuv_plan *yp, int plane)
 {
     if (!yp)
         return nullptr;
-    return plane == 0 ? yp->y : plane == 1 ? yp->c : nullptr;
+    return plane == 0 ? yp->y : plane == 1 ? yp->c : plane == 2 ? yp->cf : nullptr;
 }
+
+int iqo_hip_yuv_plan_set_chroma(iqo_hip_yuv_plan *yp, int mode)
+{
+    if (!yp || !yp->y)
+        return IQO_HIP_EINVAL;
+    return set_chroma(yp->y, 1, &yp->cf, &yp->chroma, mode);
+}
+
+int iqo_hip_yuv_plan_chroma(const iqo_hip_yuv_plan *yp) { return yp ? yp->chroma : IQO_HIP_EINVAL; }
 
 int iqo_hip_resize_yuv420_device(iqo_hip_yuv_plan *yp, size_t nFrames, size_t srcStY, size_t srcStUV,
                                  size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV,
@@ -2204,6 +2252,8 @@ int iqo_hip_resize_yuv420_device(iqo_hip_yuv_plan *yp, size_t nFrames, size_t sr
 
 struct iqo_hip_nv12_plan {
     iqo_hip_plan *y = nullptr, *uv = nullptr;
+    iqo_hip_plan *uvf = nullptr;         // full-grid UV plan (iqo_hip_nv12_plan_set_chroma)
+    int chroma = IQO_CHROMA_REPLICATE;   // of the RGB / norm entries
 };
 
 int iqo_hip_plan_nv12(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, int device,
@@ -2234,6 +2284,7 @@ void iqo_hip_nv12_plan_destroy(iqo_hip_nv12_plan *np)
         return;
     iqo_hip_plan_destroy(np->y);
     iqo_hip_plan_destroy(np->uv);
+    iqo_hip_plan_destroy(np->uvf);
     delete np;
 }
 
@@ -2241,8 +2292,17 @@ iqo_hip_plan *iqo_hip_nv12_plane(iqo_hip_nv12_plan *np, int plane)
 {
     if (!np)
         return nullptr;
-    return plane == 0 ? np->y : plane == 1 ? np->uv : nullptr;
+    return plane == 0 ? np->y : plane == 1 ? np->uv : plane == 2 ? np->uvf : nullptr;
 }
+
+int iqo_hip_nv12_plan_set_chroma(iqo_hip_nv12_plan *np, int mode)
+{
+    if (!np || !np->y)
+        return IQO_HIP_EINVAL;
+    return set_chroma(np->y, 2, &np->uvf, &np->chroma, mode);
+}
+
+int iqo_hip_nv12_plan_chroma(const iqo_hip_nv12_plan *np) { return np ? np->chroma : IQO_HIP_EINVAL; }
 
 int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *np, size_t nFrames, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
                                const uint8_t *srcY, const uint8_t *srcUV, size_t dstStY, size_t dstStUV,
@@ -2264,34 +2324,45 @@ int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *np, size_t nFrames, size_t src
 // resize entries above, unchanged, into the caller's workspace, then yuv_rgb_kernel
 // (kernels_color.hip) from the workspace to the destination.  Every check runs on the host before the
 // first launch, so a rejected call launches nothing and leaves the destination untouched.
+// In IQO_CHROMA_FULL the first pass is Y by its plan and chroma by the plan's full-grid chroma plan
+// (srcW/2 x srcH/2 -> dstW x dstH), plane by plane, and the second pass is the kernel's 4:4:4 form.
 
 // Workspace of one frame: the Y plane, then U and V (I420) or the interleaved UV plane (NV12, rows of
 // 2 * cSt bytes) in the same bytes.  Rows are padded to what a thread of yuv_rgb_kernel loads (8 Y
 // bytes, 4 chroma pairs) and to 16 bytes, so that every plane kernel finds its widest stores aligned
 // and the fused I420 instantiations stay one launch.
+// IQO_CHROMA_FULL: U and V (or the UV plane) hold dstH rows of dstW samples, padded as Y's rows, so a
+// thread's 8 chroma pairs (16 bytes of UV, 8 each of U and V) are one aligned load.
 struct YuvRgbWs {
-    size_t ySt, cSt, frame;
+    size_t ySt, cSt, cRows, frame;
 };
 
-static YuvRgbWs yuv_rgb_ws(size_t dstW, size_t dstH)
+static YuvRgbWs yuv_rgb_ws(size_t dstW, size_t dstH, int chroma)
 {
     const size_t w8 = (dstW + 7) / 8 * 8;
+    const bool full = chroma == IQO_CHROMA_FULL;
     YuvRgbWs w;
     w.ySt = (w8 + 15) & ~static_cast<size_t>(15);
-    w.cSt = (w8 / 2 + 15) & ~static_cast<size_t>(15);
-    w.frame = w.ySt * dstH + 2 * w.cSt * (dstH / 2);
+    w.cSt = full ? w.ySt : (w8 / 2 + 15) & ~static_cast<size_t>(15);
+    w.cRows = full ? dstH : dstH / 2;
+    w.frame = w.ySt * dstH + 2 * w.cSt * w.cRows;
     return w;
+}
+
+size_t iqo_hip_yuv_rgb_workspace_bytes_chroma(size_t dstW, size_t dstH, size_t nFrames, int mode)
+{
+    const size_t kMaxSize = std::numeric_limits<size_t>::max(), kLim = size_t(1) << 31;
+    if (dstW >= kLim || dstH >= kLim || (mode != IQO_CHROMA_REPLICATE && mode != IQO_CHROMA_FULL))
+        return kMaxSize;  // (no plan has such a frame)
+    const size_t frame = yuv_rgb_ws(dstW, dstH, mode).frame;
+    if (frame && nFrames > (kMaxSize - 15) / frame)
+        return kMaxSize;
+    return nFrames * frame + 15;  // + 15: the calls round the base up to 16 bytes
 }
 
 size_t iqo_hip_yuv_rgb_workspace_bytes(size_t dstW, size_t dstH, size_t nFrames)
 {
-    const size_t kMaxSize = std::numeric_limits<size_t>::max(), kLim = size_t(1) << 31;
-    if (dstW >= kLim || dstH >= kLim)
-        return kMaxSize;  // (no plan has such a frame)
-    const size_t frame = yuv_rgb_ws(dstW, dstH).frame;
-    if (frame && nFrames > (kMaxSize - 15) / frame)
-        return kMaxSize;
-    return nFrames * frame + 15;  // + 15: the calls round the base up to 16 bytes
+    return iqo_hip_yuv_rgb_workspace_bytes_chroma(dstW, dstH, nFrames, IQO_CHROMA_REPLICATE);
 }
 
 int iqo_host_yuv_to_rgb(int standard, size_t n, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *rgb)
@@ -2326,8 +2397,8 @@ static bool yuv_src_ok(const Plan &p, size_t bpp, size_t srcSt)
 }
 
 // Everything the second pass needs checked (as run_norm for the float form); fills *nd for it.
-static int yuv_rgb_check(const Plan &py, size_t nFrames, int standard, const YuvRgbOut &o, const void *workspace,
-                         size_t workspaceBytes, iqo_amd::NormDev *nd)
+static int yuv_rgb_check(const Plan &py, int chroma, size_t nFrames, int standard, const YuvRgbOut &o,
+                         const void *workspace, size_t workspaceBytes, iqo_amd::NormDev *nd)
 {
     if (!o.dst || !workspace || (!o.norm && !o.order))
         return IQO_HIP_EINVAL;
@@ -2374,9 +2445,9 @@ static int yuv_rgb_check(const Plan &py, size_t nFrames, int standard, const Yuv
         return IQO_HIP_EINVAL;
     // the kernel addresses one destination frame and one workspace frame with 32-bit offsets
     if ((planes - 1) * (o.norm ? o.planeSt : 0) + (dstH - 1) * o.rowSt + rowB >= kLim ||
-        yuv_rgb_ws(dstW, dstH).frame >= kLim)
+        yuv_rgb_ws(dstW, dstH, chroma).frame >= kLim)
         return IQO_HIP_EINVAL;
-    if (workspaceBytes < iqo_hip_yuv_rgb_workspace_bytes(dstW, dstH, nFrames))
+    if (workspaceBytes < iqo_hip_yuv_rgb_workspace_bytes_chroma(dstW, dstH, nFrames, chroma))
         return IQO_HIP_EINVAL;
     return IQO_HIP_OK;
 }
@@ -2387,19 +2458,20 @@ static uint8_t *yuv_rgb_ws_base(void *workspace)
 }
 
 // The second pass: yuv_rgb_kernel over the workspace planes the first pass wrote.
-static int yuv_rgb_convert(const iqo_hip_plan *hy, size_t nFrames, const uint8_t *ws, bool interleavedUV, int standard,
-                           const YuvRgbOut &o, const iqo_amd::NormDev &nd, hipStream_t s)
+static int yuv_rgb_convert(const iqo_hip_plan *hy, int chroma, size_t nFrames, const uint8_t *ws, bool interleavedUV,
+                           int standard, const YuvRgbOut &o, const iqo_amd::NormDev &nd, hipStream_t s)
 {
     const Plan &py = hy->p;
-    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH));
+    const bool full = chroma == IQO_CHROMA_FULL;
+    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH), chroma);
     DeviceGuard guard(hy->device);
     if (!guard.ok())
         return IQO_HIP_ENODEV;
     iqo_amd::YuvRgbDev d{};
     d.dstW = py.dstW;
     d.dstH = py.dstH;
-    d.cw = py.dstW / 2;
-    d.ch = py.dstH / 2;
+    d.cw = full ? py.dstW : py.dstW / 2;
+    d.ch = full ? py.dstH : py.dstH / 2;
     d.k = iqo_amd::kYuvRgb[standard];
     d.ySt = static_cast<int>(w.ySt);
     d.cSt = static_cast<int>(interleavedUV ? 2 * w.cSt : w.cSt);
@@ -2413,13 +2485,13 @@ static int yuv_rgb_convert(const iqo_hip_plan *hy, size_t nFrames, const uint8_t
         d.frames = static_cast<int>(std::min(chunk, nFrames - f0));
         d.y = ws + f0 * w.frame;
         d.u = d.y + w.ySt * static_cast<size_t>(py.dstH);
-        d.v = d.u + w.cSt * static_cast<size_t>(d.ch);
+        d.v = d.u + w.cSt * w.cRows;
         d.dst = static_cast<uint8_t *>(o.dst) + f0 * o.frameSt;
         int order[4] = {0, 0, 0, 0};
         for (int c = 0; !o.norm && c < o.channels; ++c)
             order[c] = o.order[c];
-        const hipError_t e = o.norm ? iqo_amd::launch_yuv_rgb_norm(d, interleavedUV, nd, s)
-                                    : iqo_amd::launch_yuv_rgb_bytes(d, interleavedUV, o.channels, order, s);
+        const hipError_t e = o.norm ? iqo_amd::launch_yuv_rgb_norm(d, interleavedUV, full, nd, s)
+                                    : iqo_amd::launch_yuv_rgb_bytes(d, interleavedUV, full, o.channels, order, s);
         if (e == hipErrorInvalidValue)
             return IQO_HIP_EINVAL;
         if (e != hipSuccess)
@@ -2436,20 +2508,33 @@ static int nv12_rgb(iqo_hip_nv12_plan *np, size_t nFrames, size_t srcStY, size_t
         return IQO_HIP_EINVAL;
     const Plan &py = np->y->p;
     iqo_amd::NormDev nd{};
-    const int rc = yuv_rgb_check(py, nFrames, standard, o, workspace, workspaceBytes, &nd);
+    const bool full = np->chroma == IQO_CHROMA_FULL;
+    if (full && !np->uvf)
+        return IQO_HIP_EINVAL;
+    const int rc = yuv_rgb_check(py, np->chroma, nFrames, standard, o, workspace, workspaceBytes, &nd);
     if (rc)
         return rc;
     if (!yuv_src_ok(py, 1, srcStY) || !yuv_src_ok(np->uv->p, 2, srcStUV))
         return IQO_HIP_EINVAL;
     if (nFrames == 0)
         return IQO_HIP_OK;
-    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH));
-    uint8_t *ws = yuv_rgb_ws_base(workspace);
-    const int r1 = iqo_hip_resize_nv12_device(np, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcUV, w.ySt, 2 * w.cSt, w.frame,
-                                              ws, ws + w.ySt * static_cast<size_t>(py.dstH), stream);
+    const size_t dstH = static_cast<size_t>(py.dstH);
+    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), dstH, np->chroma);
+    uint8_t *ws = yuv_rgb_ws_base(workspace), *wuv = ws + w.ySt * dstH;
+    int r1;
+    if (full) {
+        // Y by its plan, UV by the full-grid plan: the launches of iqo_hip_resize_nv12_device
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        r1 = run_band(np->y, nFrames, 0, dstH, 0, srcStY, srcFrameSt, srcY, w.ySt, w.frame, ws, s);
+        if (!r1)
+            r1 = run_band(np->uvf, nFrames, 0, dstH, 0, srcStUV, srcFrameSt, srcUV, 2 * w.cSt, w.frame, wuv, s);
+    } else {
+        r1 = iqo_hip_resize_nv12_device(np, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcUV, w.ySt, 2 * w.cSt, w.frame, ws,
+                                        wuv, stream);
+    }
     if (r1)
         return r1;
-    return yuv_rgb_convert(np->y, nFrames, ws, true, standard, o, nd, static_cast<hipStream_t>(stream));
+    return yuv_rgb_convert(np->y, np->chroma, nFrames, ws, true, standard, o, nd, static_cast<hipStream_t>(stream));
 }
 
 static int yuv420_rgb(iqo_hip_yuv_plan *yp, size_t nFrames, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
@@ -2462,20 +2547,35 @@ static int yuv420_rgb(iqo_hip_yuv_plan *yp, size_t nFrames, size_t srcStY, size_
         return IQO_HIP_EINVAL;
     const Plan &py = yp->y->p;
     iqo_amd::NormDev nd{};
-    const int rc = yuv_rgb_check(py, nFrames, standard, o, workspace, workspaceBytes, &nd);
+    const bool full = yp->chroma == IQO_CHROMA_FULL;
+    if (full && !yp->cf)
+        return IQO_HIP_EINVAL;
+    const int rc = yuv_rgb_check(py, yp->chroma, nFrames, standard, o, workspace, workspaceBytes, &nd);
     if (rc)
         return rc;
     if (!yuv_src_ok(py, 1, srcStY) || !yuv_src_ok(yp->c->p, 1, srcStUV))
         return IQO_HIP_EINVAL;
     if (nFrames == 0)
         return IQO_HIP_OK;
-    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), static_cast<size_t>(py.dstH));
-    uint8_t *ws = yuv_rgb_ws_base(workspace), *wu = ws + w.ySt * static_cast<size_t>(py.dstH);
-    const int r1 = iqo_hip_resize_yuv420_device(yp, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcU, srcV, w.ySt, w.cSt,
-                                                w.frame, ws, wu, wu + w.cSt * static_cast<size_t>(py.dstH / 2), stream, fused);
+    const size_t dstH = static_cast<size_t>(py.dstH);
+    const YuvRgbWs w = yuv_rgb_ws(static_cast<size_t>(py.dstW), dstH, yp->chroma);
+    uint8_t *ws = yuv_rgb_ws_base(workspace), *wu = ws + w.ySt * dstH, *wv = wu + w.cSt * w.cRows;
+    int r1;
+    if (full) {
+        // plane by plane: Y by its plan, U and then V by the full-grid plan (*fused stays 0)
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        r1 = run_band(yp->y, nFrames, 0, dstH, 0, srcStY, srcFrameSt, srcY, w.ySt, w.frame, ws, s);
+        if (!r1)
+            r1 = run_band(yp->cf, nFrames, 0, dstH, 0, srcStUV, srcFrameSt, srcU, w.cSt, w.frame, wu, s);
+        if (!r1)
+            r1 = run_band(yp->cf, nFrames, 0, dstH, 0, srcStUV, srcFrameSt, srcV, w.cSt, w.frame, wv, s);
+    } else {
+        r1 = iqo_hip_resize_yuv420_device(yp, nFrames, srcStY, srcStUV, srcFrameSt, srcY, srcU, srcV, w.ySt, w.cSt, w.frame,
+                                          ws, wu, wv, stream, fused);
+    }
     if (r1)
         return r1;
-    return yuv_rgb_convert(yp->y, nFrames, ws, false, standard, o, nd, static_cast<hipStream_t>(stream));
+    return yuv_rgb_convert(yp->y, yp->chroma, nFrames, ws, false, standard, o, nd, static_cast<hipStream_t>(stream));
 }
 
 int iqo_hip_resize_nv12_rgb_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
@@ -2880,6 +2980,19 @@ int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t
     h.channels = channels;
     build_host_tables(&h);
     return plan_kernel(&h);
+}
+
+int iqo_host_yuv_chroma_full_kernel(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                                    int interleavedUV)
+{
+    // the requests iqo_hip_plan_nv12 / iqo_hip_plan_yuv420 reject, then set_chroma's own rule and plan
+    if (method < 0 || method > 2 || srcW < 2 || srcH < 2 || dstW < 2 || dstH < 2)
+        return IQO_HIP_EINVAL;
+    const int rc = chroma_full_status(method, srcW, srcH, dstW, dstH);
+    if (rc)
+        return rc;
+    const unsigned deg = method == IQO_METHOD_LANCZOS ? degree : 0;
+    return iqo_host_packed_kernel_for(method, deg, interleavedUV ? 2 : 1, srcW / 2, srcH / 2, dstW, dstH, 1);
 }
 
 int iqo_host_yuv420_fused(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH)

@@ -85,6 +85,9 @@ hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io,
 // bases and cSt are multiples of 8 (interleaved UV) / 4 (separate U, V) with
 // cSt >= 8 / 4 ceil(dstW / 8) -- a thread loads 8 Y bytes and 4 chroma pairs whole; what it loads
 // past the planes' widths is never used.  No alignment of dst beyond the element size.
+// chroma444 (IQO_CHROMA_FULL): the chroma planes are on the output grid, cw x ch = dstW x dstH, and
+// pixel (y, x) takes sample (y, x).  A thread then loads 8 chroma pairs whole: the chroma bases and cSt
+// are multiples of 16 (interleaved UV; frameSt too) / 8 (separate U, V) with cSt >= 16 / 8 ceil(dstW / 8).
 struct YuvRgbDev {
     int dstW, dstH, cw, ch;
     YuvRgbCoef k;                      // the standard's six integers
@@ -97,10 +100,10 @@ struct YuvRgbDev {
     int frames;                        // frames x dstH x ceil(dstW / 4) < 2^31
 };
 // Packed bytes: `channels` 3 or 4 per pixel, byte c = order[c] of {0 R, 1 G, 2 B, 3 the constant 255}.
-hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, int channels, const int (&order)[4],
-                                hipStream_t s);
+hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, bool chroma444, int channels,
+                                const int (&order)[4], hipStream_t s);
 // Planar floats as the packed kernels' NORM epilogue, of the 3-channel source (R, G, B).
-hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, const NormDev &n, hipStream_t s);
+hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, bool chroma444, const NormDev &n, hipStream_t s);
 
 // --- general-ratio wave walker: every wave walks a 256-column strip of one band of rows through
 // a private LDS ring of source rows widened to u16 (plan.hpp WalkTables; 4-byte aligned sources).

@@ -2,9 +2,11 @@
 // (include/iqo_hip.h iqo_hip_resize_nv12_rgb_device and its three siblings): resized Y and chroma
 // planes in, packed RGB(A) bytes or normalised planar fp32 / fp16 / bf16 tensors out.
 //
-//   yuv_rgb_kernel<UV2, NORM, PX>   UV2: interleaved UV plane (NV12) / separate U and V planes (I420)
-//                                   NORM: planar floats (kernels.hpp NormDev) / packed bytes
-//                                   PX: pixels per thread, 8 (4 for fp32 planes)
+//   yuv_rgb_kernel<UV2, NORM, PX, C444>   UV2: interleaved UV plane (NV12) / separate U and V planes (I420)
+//                                         NORM: planar floats (kernels.hpp NormDev) / packed bytes
+//                                         PX: pixels per thread, 8 (4 for fp32 planes)
+//                                         C444: chroma planes on the output grid (IQO_CHROMA_FULL) /
+//                                               at half size, replicated 2 x 2 (IQO_CHROMA_REPLICATE)
 //
 // Memory-bound, no LDS.  A thread owns 8 adjacent output pixels of one row: one 8-byte load of Y,
 // 4 chroma pairs (one 8-byte load of UV, or 4 bytes each of U and V), the integer matrix of
@@ -13,6 +15,8 @@
 // destination beyond its element size).  With fp32 planes a thread owns 4 pixels and loads half of
 // that (see yuv_rgb_kernel).  Threads run over (frame, row, pixel group) in that order,
 // so a wave's loads and stores are contiguous within a row and follow on into the next one.
+// With C444 pixel (y, x) takes chroma sample (y, x): 8 chroma pairs per thread (one 16-byte load of
+// UV, or 8 bytes each of U and V), the chroma terms once per pixel, and no index clamp or edge fetch.
 #include "kernels_dev.hpp"
 
 namespace iqo_amd {
@@ -45,11 +49,11 @@ __device__ __forceinline__ uint32_t rgb_word(int r, int g, int b)
 }
 
 // The PX pixels [PX g, PX g + PX) of output row `row` of frame f, each a word (R, G, B, 255).
-template <bool UV2, int PX>
+template <bool UV2, int PX, bool C444>
 __device__ __forceinline__ void rgb_run(const YuvRgbDev &d, int f, int row, int g, uint32_t (&w)[PX])
 {
     static_assert(PX == 8 || PX == 4, "a thread's run: 8 Y bytes and 4 chroma pairs, or half of that");
-    constexpr int NC = PX / 2;  // chroma samples of the run
+    constexpr int NC = PX / 2;  // chroma samples of the run at half size (C444: PX of them)
     const int64_t fo = static_cast<int64_t>(f) * d.frameSt;
     const uint8_t *yp = d.y + fo + static_cast<int64_t>(row) * d.ySt + PX * g;
     uint32_t yy[2] = {0u, 0u};
@@ -59,6 +63,41 @@ __device__ __forceinline__ void rgb_run(const YuvRgbDev &d, int f, int row, int 
         yy[1] = v2.y;
     } else {
         yy[0] = *reinterpret_cast<const uint32_t *>(yp);
+    }
+    if constexpr (C444) {
+        // chroma on the output grid: samples PX g .. PX g + PX - 1 of row `row`, one per byte of UU / VV
+        const int64_t co = fo + static_cast<int64_t>(row) * d.cSt;
+        uint32_t UU[2] = {0u, 0u}, VV[2] = {0u, 0u};
+        if constexpr (UV2 && PX == 8) {
+            const u32x4 uv = *reinterpret_cast<const u32x4 *>(d.u + co + 16 * g);
+            UU[0] = __builtin_amdgcn_perm(uv.y, uv.x, 0x06040200u);
+            VV[0] = __builtin_amdgcn_perm(uv.y, uv.x, 0x07050301u);
+            UU[1] = __builtin_amdgcn_perm(uv.w, uv.z, 0x06040200u);
+            VV[1] = __builtin_amdgcn_perm(uv.w, uv.z, 0x07050301u);
+        } else if constexpr (UV2) {
+            const u32x2 uv = *reinterpret_cast<const u32x2 *>(d.u + co + 8 * g);
+            UU[0] = __builtin_amdgcn_perm(uv.y, uv.x, 0x06040200u);
+            VV[0] = __builtin_amdgcn_perm(uv.y, uv.x, 0x07050301u);
+        } else if constexpr (PX == 8) {
+            const u32x2 u2 = *reinterpret_cast<const u32x2 *>(d.u + co + 8 * g);
+            const u32x2 v2 = *reinterpret_cast<const u32x2 *>(d.v + co + 8 * g);
+            UU[0] = u2.x;
+            UU[1] = u2.y;
+            VV[0] = v2.x;
+            VV[1] = v2.y;
+        } else {
+            UU[0] = *reinterpret_cast<const uint32_t *>(d.u + co + 4 * g);
+            VV[0] = *reinterpret_cast<const uint32_t *>(d.v + co + 4 * g);
+        }
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+            const YuvChroma c = yuv_chroma_terms(d.k, static_cast<int>(byte_of(UU[k >> 2], k & 3)),
+                                                 static_cast<int>(byte_of(VV[k >> 2], k & 3)));
+            int r, gg, b;
+            yuv_sums(d.k, static_cast<int>(byte_of(yy[k >> 2], k & 3)), c, r, gg, b);
+            w[k] = rgb_word(r, gg, b);
+        }
+        return;
     }
     const int cr = min(row >> 1, d.ch - 1);
     const int64_t co = fo + static_cast<int64_t>(cr) * d.cSt;
@@ -126,7 +165,7 @@ __device__ __forceinline__ void store_bytes(uint8_t *p, const uint32_t (&o)[2 * 
 // thread's fp32 run is 32 bytes, two 16-byte stores per plane with neighbouring lanes 32 bytes apart,
 // so every store instruction fills half of each cache line it touches; with 4 pixels a wave's store
 // is 1 KiB contiguous.
-template <bool UV2, bool NORM, int PX>
+template <bool UV2, bool NORM, int PX, bool C444>
 __global__ __launch_bounds__(256) void yuv_rgb_kernel(std::conditional_t<NORM, YuvRgbNormArgs, YuvRgbBytesArgs> a)
 {
     static_assert(NORM || PX == 8, "the byte form owns 8 pixels per thread");
@@ -136,7 +175,7 @@ __global__ __launch_bounds__(256) void yuv_rgb_kernel(std::conditional_t<NORM, Y
         const unsigned t = it / nG;
         const int g = static_cast<int>(it - t * nG), f = static_cast<int>(t / H), row = static_cast<int>(t - (t / H) * H);
         uint32_t w[PX];  // the pixels' (R, G, B, 255)
-        rgb_run<UV2, PX>(d, f, row, g, w);
+        rgb_run<UV2, PX, C444>(d, f, row, g, w);
         const int x0 = PX * g, valid = min(PX, d.dstW - x0);
         const bool full = valid == PX;
         uint8_t *rowp = d.dst + static_cast<int64_t>(f) * d.dstFrameSt + static_cast<int64_t>(row) * d.dstSt;
@@ -222,26 +261,41 @@ __global__ __launch_bounds__(256) void yuv_rgb_kernel(std::conditional_t<NORM, Y
 // kernel strides over the rest.
 constexpr unsigned kMaxBlocks = 2048;
 
-bool dev_ok(const YuvRgbDev &d, bool uv2)
+// c444: the chroma planes are on the output grid (cw x ch = dstW x dstH) and a thread loads as many
+// chroma samples per component as pixels -- 16 bytes of UV, or 8 each of U and V, for 8 pixels.
+bool dev_ok(const YuvRgbDev &d, bool uv2, bool c444)
 {
-    if (d.dstW < 2 || d.dstH < 2 || d.cw != d.dstW / 2 || d.ch != d.dstH / 2 || d.frames < 0 || !d.y || !d.u ||
-        (!uv2 && !d.v) || !d.dst || d.dstSt < 0)
+    if (d.dstW < 2 || d.dstH < 2 || d.cw != (c444 ? d.dstW : d.dstW / 2) || d.ch != (c444 ? d.dstH : d.dstH / 2) ||
+        d.frames < 0 || !d.y || !d.u || (!uv2 && !d.v) || !d.dst || d.dstSt < 0)
         return false;
     const int nG = (d.dstW + 7) / 8;
-    const uintptr_t ca = uv2 ? 7 : 3;
-    if (d.ySt < 8 * nG || d.cSt < (uv2 ? 8 : 4) * nG || (d.ySt & 7) || (static_cast<uintptr_t>(d.cSt) & ca) ||
-        (d.frameSt & 7) || (reinterpret_cast<uintptr_t>(d.y) & 7) || (reinterpret_cast<uintptr_t>(d.u) & ca) ||
-        (!uv2 && (reinterpret_cast<uintptr_t>(d.v) & ca)))
+    const uintptr_t ca = c444 ? (uv2 ? 15 : 7) : (uv2 ? 7 : 3);  // a thread's widest chroma load
+    const uintptr_t fa = c444 && uv2 ? 15 : 7;
+    if (d.ySt < 8 * nG || d.cSt < static_cast<int>(ca + 1) * nG || (d.ySt & 7) || (static_cast<uintptr_t>(d.cSt) & ca) ||
+        (static_cast<uintptr_t>(d.frameSt) & fa) || (reinterpret_cast<uintptr_t>(d.y) & 7) ||
+        (reinterpret_cast<uintptr_t>(d.u) & ca) || (!uv2 && (reinterpret_cast<uintptr_t>(d.v) & ca)))
         return false;
     // (counted in 4-pixel groups, the finer of the two runs a thread can own)
     return static_cast<uint64_t>(d.frames) * static_cast<uint64_t>(d.dstH) * static_cast<uint64_t>((d.dstW + 3) / 4) < (uint64_t(1) << 31);
 }
 
+// the instantiation of a launch
+template <bool NORM, int PX>
+const void *kernel_of(bool uv2, bool c444)
+{
+    if (c444)
+        return uv2 ? reinterpret_cast<const void *>(yuv_rgb_kernel<true, NORM, PX, true>)
+                   : reinterpret_cast<const void *>(yuv_rgb_kernel<false, NORM, PX, true>);
+    return uv2 ? reinterpret_cast<const void *>(yuv_rgb_kernel<true, NORM, PX, false>)
+               : reinterpret_cast<const void *>(yuv_rgb_kernel<false, NORM, PX, false>);
+}
+
 } // namespace
 
-hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, int channels, const int (&order)[4], hipStream_t s)
+hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, bool chroma444, int channels,
+                                const int (&order)[4], hipStream_t s)
 {
-    if (!dev_ok(d, interleavedUV) || channels < 3 || channels > 4)
+    if (!dev_ok(d, interleavedUV, chroma444) || channels < 3 || channels > 4)
         return hipErrorInvalidValue;
     for (int c = 0; c < channels; ++c)
         if (order[c] < 0 || order[c] > 3)
@@ -264,15 +318,14 @@ hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, int chan
         a.sel[2] = o2 | ((o0 + 4) << 8) | ((o1 + 4) << 16) | ((o2 + 4) << 24);
     }
     const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
-    const void *kern = interleavedUV ? reinterpret_cast<const void *>(yuv_rgb_kernel<true, false, 8>)
-                                     : reinterpret_cast<const void *>(yuv_rgb_kernel<false, false, 8>);
+    const void *kern = kernel_of<false, 8>(interleavedUV, chroma444);
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(blocks), dim3(256), args, 0, s);
 }
 
-hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, const NormDev &n, hipStream_t s)
+hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, bool chroma444, const NormDev &n, hipStream_t s)
 {
-    if (!dev_ok(d, interleavedUV) || n.dtype < 1 || n.dtype > 3 || n.planes < 1 || n.planes > 4 || n.planeSt < 0)
+    if (!dev_ok(d, interleavedUV, chroma444) || n.dtype < 1 || n.dtype > 3 || n.planes < 1 || n.planes > 4 || n.planeSt < 0)
         return hipErrorInvalidValue;
     for (int p = 0; p < n.planes; ++p)
         if (n.order[p] < 0 || n.order[p] > 2)
@@ -286,10 +339,7 @@ hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, const Nor
     a.items = static_cast<unsigned>(d.frames) * static_cast<unsigned>(d.dstH) * static_cast<unsigned>(a.nG);
     a.n = n;
     const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
-    const void *kern = interleavedUV ? (px == 4 ? reinterpret_cast<const void *>(yuv_rgb_kernel<true, true, 4>)
-                                                : reinterpret_cast<const void *>(yuv_rgb_kernel<true, true, 8>))
-                                     : (px == 4 ? reinterpret_cast<const void *>(yuv_rgb_kernel<false, true, 4>)
-                                                : reinterpret_cast<const void *>(yuv_rgb_kernel<false, true, 8>));
+    const void *kern = px == 4 ? kernel_of<true, 4>(interleavedUV, chroma444) : kernel_of<true, 8>(interleavedUV, chroma444);
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(blocks), dim3(256), args, 0, s);
 }
