@@ -357,6 +357,76 @@ int iqo_hip_resize_yuv420_norm_device(iqo_hip_yuv_plan *plan, size_t nFrames, si
  * rgb receives 3 n bytes (R, G, B per triple).  IQO_HIP_EINVAL for an unknown standard or a null pointer. */
 int iqo_host_yuv_to_rgb(int standard, size_t n, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *rgb);
 
+/* ---- Packed RGB(A) straight to NV12 / I420: the opposite direction, what a hardware encoder takes from a
+ * renderer, a compositor or a generative model.  The packed resize above (iqo_hip_resize_device on a plan of
+ * iqo_hip_plan_packed with 3 or 4 channels), then ONE integer RGB -> YUV definition with 4:2:0 chroma.
+ *
+ * Let P(f, y, x, c) be exactly the bytes iqo_hip_resize_device writes for the same plan and source, and
+ * R, G, B = P(.., order[0]), P(.., order[1]), P(.., order[2]).  The IQO_CS_* standards as above, 14-bit
+ * coefficients, everything in int32, >> a shift of a non-negative value:
+ *
+ *   Y = (cYR R + cYG G + cYB B + (yOff << 14) + 8192) >> 14
+ *   U = min(255, (cUB B - cUR R - cUG G + (128 << 14) + 8192) >> 14)       (4:4:4, iqo_host_rgb_to_yuv only)
+ *   V = min(255, (cVR R - cVG G - cVB B + (128 << 14) + 8192) >> 14)
+ *
+ * Chroma sample (j, i) of the cw x ch = dstW/2 x dstH/2 (rounded down) planes takes SR, SG, SB, the sums
+ * over the resized pixels of rows 2j, 2j+1 and columns 2i, 2i+1, and is rounded once, on the sum:
+ *
+ *   U = min(255, (cUB SB - cUR SR - cUG SG + (128 << 16) + 32768) >> 16)
+ *   V = min(255, (cVR SR - cVG SG - cVB SB + (128 << 16) + 32768) >> 16)
+ *
+ *   standard               yOff   cYR    cYG   cYB   cUR   cUG   cUB   cVR   cVG   cVB
+ *   IQO_CS_BT601_LIMITED     16  4207   8260  1604  2428  4768  7196  7196  6026  1170
+ *   IQO_CS_BT601_FULL         0  4899   9617  1868  2765  5427  8192  8192  6860  1332
+ *   IQO_CS_BT709_LIMITED     16  2991  10064  1016  1649  5547  7196  7196  6536   660
+ *   IQO_CS_BT709_FULL         0  3483  11718  1183  1877  6315  8192  8192  7441   751
+ *
+ * round(k 2^14) of the real coefficients: Kr, Kg, Kb for Y; Kr/(2(1-Kb)), Kg/(2(1-Kb)), 1/2 for U; 1/2,
+ * Kg/(2(1-Kr)), Kb/(2(1-Kr)) for V; limited range scales luma by 219/255 and chroma by 224/255
+ * (libiqo_amd/csrc/colorspace.hpp holds the table for host and device code).  Rounded one by one they keep
+ * cUR + cUG = cUB, cVG + cVB = cVR and cYR + cYG + cYB = 14071 (limited) / 16384 (full): grey gives
+ * U = V = 128, black and white give Y = 16 and 235 (limited) or 0 and 255 (full).  No accumulator is ever
+ * negative, so there is no lower clamp and none of Y; limited range stays inside 16..235 / 16..240, and in
+ * the full-range standards U and V reach 256 before the min (pure blue, pure red).  The chroma planes are
+ * centre-sited, as everywhere in this library: the layout iqo_hip_plan_nv12 / _yuv420 read.  An odd dstW's
+ * last column and an odd dstH's last row contribute to Y only.
+ *
+ * order[k] (k = 0, 1, 2) is the byte of a source pixel that holds R, G, B: RGB(A) {0,1,2}, BGR(A) {2,1,0};
+ * distinct values below the plan's channels.  A fourth channel is resized and ignored.  The planes of frame
+ * f start at dstY / dstUV (or dstU, dstV) + f*dstFrameSt with rows dstStY and dstStUV bytes apart; they need
+ * no alignment beyond a byte.
+ *
+ * Two passes on `stream`: the plan's own resize into `workspace` (device memory of at least
+ * iqo_hip_rgb_yuv_workspace_bytes(dstW, dstH, channels, nFrames) bytes, any alignment, contents unspecified
+ * afterwards, layout internal), then one kernel writes the planes.  No call allocates or synchronises:
+ * after iqo_hip_plan_prepare they can be captured into a hipGraph.  The plan's options apply to the first
+ * pass.
+ *
+ * IQO_HIP_EUNSUP: a plan whose channels are not 3 or 4.  IQO_HIP_EINVAL: a null plan, source, destination,
+ * workspace or order; an unknown standard; an order[k] outside 0..channels-1 or two equal ones; dstW < 2 or
+ * dstH < 2; dstStY < dstW; dstStUV < 2*cw (NV12) or < cw (I420); a destination stride or plane (first byte
+ * to last byte of one frame) that reaches 2^31 bytes; destination planes that overlap (each plane's bytes,
+ * first to last, taken as one range); with nFrames > 1 a dstFrameSt below the distance from the first byte
+ * of a frame's lowest plane to the end of its highest; a source stride below its row or >= 2^24, a source
+ * frame that reaches 2^31 bytes; workspaceBytes below the query's value.  On any error nothing is launched
+ * and the destination is untouched. */
+/* Host-only.  Saturates at SIZE_MAX instead of wrapping; SIZE_MAX for channels outside 3..4. */
+size_t iqo_hip_rgb_yuv_workspace_bytes(size_t dstW, size_t dstH, int channels, size_t nFrames);
+int iqo_hip_resize_rgb_nv12_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt,
+                                   const uint8_t *src, int standard, const int *order /* [3] */, size_t dstStY,
+                                   size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstUV, void *workspace,
+                                   size_t workspaceBytes, void *stream);
+int iqo_hip_resize_rgb_yuv420_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt,
+                                     const uint8_t *src, int standard, const int *order /* [3] */, size_t dstStY,
+                                     size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstU, uint8_t *dstV,
+                                     void *workspace, size_t workspaceBytes, void *stream);
+/* Host-only, no GPU: the 4:4:4 form on n (R, G, B) triples (rgb: 3 n bytes) in plain C++ from the same
+ * table; y, u, v receive n bytes each.  IQO_HIP_EINVAL for an unknown standard or a null pointer. */
+int iqo_host_rgb_to_yuv(int standard, size_t n, const uint8_t *rgb, uint8_t *y, uint8_t *u, uint8_t *v);
+/* Host-only, no GPU: the 4:2:0 form on one tight image rgb[h][w][3]; y receives w*h bytes, u and v
+ * (w/2)*(h/2) each, tight.  IQO_HIP_EINVAL also for w < 2 or h < 2. */
+int iqo_host_rgb_to_yuv420(int standard, size_t w, size_t h, const uint8_t *rgb, uint8_t *y, uint8_t *u, uint8_t *v);
+
 /* ---- Multi-GPU data movement for row-band / image sharding.  The reference
  * splits a frame's output rows over OpenMP threads (src/IQOLanczosResizerImpl_AVX512.cpp:269-308);
  * across GPUs the same split needs each band's source window (halo rows) on its device and the

@@ -17,7 +17,8 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "ipc_close", "KERNELS", "YUV420_FUSED", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16",
            "CS_BT601_LIMITED", "CS_BT601_FULL", "CS_BT709_LIMITED", "CS_BT709_FULL", "COLOR_STANDARDS", "RGB_ORDERS",
            "host_yuv_to_rgb", "yuv_rgb_workspace_bytes", "CHROMA_REPLICATE", "CHROMA_FULL", "CHROMA_MODES",
-           "host_chroma_full_kernel"]
+           "host_chroma_full_kernel", "host_rgb_to_yuv", "host_rgb_to_yuv420", "rgb_yuv_workspace_bytes",
+           "SOURCE_ORDERS"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -57,6 +58,8 @@ COLOR_STANDARDS = {"bt601": CS_BT601_LIMITED, "bt601-full": CS_BT601_FULL, "bt70
                    "bt709-full": CS_BT709_FULL}
 # packed byte orders of resize_rgb: the source of each byte of a pixel (0 R, 1 G, 2 B, 3 the constant 255)
 RGB_ORDERS = {"rgb": (0, 1, 2), "bgr": (2, 1, 0), "rgba": (0, 1, 2, 3), "bgra": (2, 1, 0, 3)}
+# source pixel orders of resize_nv12 / resize_i420: the byte of a packed pixel that holds R, G, B
+SOURCE_ORDERS = {"rgb": (0, 1, 2), "bgr": (2, 1, 0)}
 # IQO_CHROMA_*: chroma resized to half the output and replicated 2 x 2, or filtered to the full output grid
 CHROMA_REPLICATE, CHROMA_FULL = 0, 1
 CHROMA_MODES = {"replicate": CHROMA_REPLICATE, "full": CHROMA_FULL}
@@ -144,6 +147,14 @@ def lib():
     for name in ("iqo_hip_nv12_plan_chroma", "iqo_hip_yuv_plan_chroma"):
         getattr(L, name).argtypes = [_vp]
     L.iqo_host_yuv_chroma_full_kernel.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int]
+    L.iqo_hip_rgb_yuv_workspace_bytes.argtypes = [_c_sz, _c_sz, ctypes.c_int, _c_sz]
+    L.iqo_hip_rgb_yuv_workspace_bytes.restype = _c_sz
+    # plan, nFrames, srcSt, srcFrameSt, src, standard, order, dstStY, dstStUV, dstFrameSt, then the planes
+    to_yuv = [_vp, _c_sz, _c_sz, _c_sz, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _c_sz, _c_sz, _c_sz]
+    L.iqo_hip_resize_rgb_nv12_device.argtypes = to_yuv + [_vp, _vp, _vp, _c_sz, _vp]
+    L.iqo_hip_resize_rgb_yuv420_device.argtypes = to_yuv + [_vp, _vp, _vp, _vp, _c_sz, _vp]
+    L.iqo_host_rgb_to_yuv.argtypes = [ctypes.c_int, _c_sz, _vp, _vp, _vp, _vp]
+    L.iqo_host_rgb_to_yuv420.argtypes = [ctypes.c_int, _c_sz, _c_sz, _vp, _vp, _vp, _vp]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -289,6 +300,40 @@ def host_yuv_to_rgb(standard, y, u, v):
     _check(lib().iqo_host_yuv_to_rgb(_standard(standard), y.size, _ptr(y), _ptr(u), _ptr(v), _ptr(rgb)),
            "host_yuv_to_rgb")
     return rgb
+
+
+def rgb_yuv_workspace_bytes(dstW, dstH, channels, nFrames):
+    """Bytes of device workspace the resize_nv12 / resize_i420 calls of a packed resizer with `channels` (3 or
+    4) bytes per pixel need -- host only."""
+    return int(lib().iqo_hip_rgb_yuv_workspace_bytes(dstW, dstH, channels, nFrames))
+
+
+def host_rgb_to_yuv(standard, rgb):
+    """The library's integer RGB -> YUV formula in its 4:4:4 form (include/iqo_hip.h, IQO_CS_*) on a numpy
+    uint8 array [..., 3] (R, G, B), in plain C++ on the host -- no GPU.  Returns (y, u, v), uint8 [...]."""
+    import numpy as np
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim < 1 or rgb.shape[-1] != 3:
+        raise IqoError("rgb must be [..., 3]")
+    y, u, v = (np.empty(rgb.shape[:-1], np.uint8) for _ in range(3))
+    _check(lib().iqo_host_rgb_to_yuv(_standard(standard), y.size, _ptr(rgb), _ptr(y), _ptr(u), _ptr(v)),
+           "host_rgb_to_yuv")
+    return y, u, v
+
+
+def host_rgb_to_yuv420(standard, rgb):
+    """The 4:2:0 form on one image, numpy uint8 [h, w, 3] (R, G, B): Y per pixel, U and V once per 2 x 2 block
+    on the block's sums -- no GPU.  Returns (y [h, w], u [h/2, w/2], v [h/2, w/2])."""
+    import numpy as np
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise IqoError("rgb must be [h, w, 3]")
+    h, w = rgb.shape[:2]
+    y = np.empty((h, w), np.uint8)
+    u, v = (np.empty((h // 2, w // 2), np.uint8) for _ in range(2))
+    _check(lib().iqo_host_rgb_to_yuv420(_standard(standard), w, h, _ptr(rgb), _ptr(y), _ptr(u), _ptr(v)),
+           "host_rgb_to_yuv420")
+    return y, u, v
 
 
 def _ptr(obj):
@@ -462,6 +507,71 @@ class _Resizer:
                                                 ctypes.byref(n), o.stride(2) * e, o.stride(1) * e, o.stride(0) * e,
                                                 _ptr(o), _stream_ptr(stream)), "resize_normalized")
         return out
+
+    # -- packed RGB(A) plans straight to an encoder's input: a Y plane and 4:2:0 chroma
+    def _yuv_workspace(self, nbytes, device, stream):
+        """The device workspace of a call on `stream`: one per (device, stream), kept on the resizer and grown
+        when a batch needs more (_YuvToRgb._workspace has the reasons)."""
+        import torch
+        cache = self.__dict__.setdefault("_ws", {})
+        key = (device, _stream_ptr(stream))
+        ws = cache.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = cache[key] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        if hasattr(stream, "cuda_stream"):
+            ws.record_stream(stream)
+        return ws
+
+    def _resize_yuv(self, nv12, src, standard, order, out, stream):
+        import torch
+        what = "resize_nv12" if nv12 else "resize_i420"
+        C = self.channels
+        if C not in (3, 4):
+            raise IqoError("%s needs a packed resizer with 3 or 4 channels" % what)
+        if not isinstance(order, str) or order not in SOURCE_ORDERS:
+            raise IqoError("order must be one of %s" % ", ".join(sorted(SOURCE_ORDERS)))
+        cs = _standard(standard)
+        squeeze = src.dim() == 3
+        s = src.unsqueeze(0) if squeeze else src
+        if s.dtype != torch.uint8 or not s.is_cuda or s.dim() != 4 or tuple(s.shape[1:]) != (self.srcH, self.srcW, C):
+            raise IqoError("expected uint8 device tensor [F, %d, %d, %d]" % (self.srcH, self.srcW, C))
+        s = s.contiguous()
+        dw, dh = self.dstW, self.dstH
+        cw, ch = dw // 2, dh // 2
+        n, nbytes = s.shape[0], dw * dh + 2 * cw * ch
+        if out is None:
+            out = torch.empty((nbytes,) if squeeze else (n, nbytes), dtype=torch.uint8, device=s.device)
+        o = out.unsqueeze(0) if out.dim() == 1 else out
+        if (o.dtype != torch.uint8 or o.device != s.device or tuple(o.shape) != (n, nbytes) or not o.is_contiguous()):
+            raise IqoError("out must be a contiguous uint8 tensor [%d, %d] on %s" % (n, nbytes, s.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        wsb = rgb_yuv_workspace_bytes(dw, dh, C, n)
+        ws = self._yuv_workspace(wsb, s.device, stream)
+        head = (self._plan, n, s.stride(1), s.stride(0), _ptr(s), cs, (ctypes.c_int * 3)(*SOURCE_ORDERS[order]), dw)
+        b = o.data_ptr()
+        tail = (_ptr(ws), ws.numel(), _stream_ptr(stream))
+        if nv12:
+            rc = lib().iqo_hip_resize_rgb_nv12_device(*head, 2 * cw, o.stride(0), b, b + dw * dh, *tail)
+        else:
+            rc = lib().iqo_hip_resize_rgb_yuv420_device(*head, cw, o.stride(0), b, b + dw * dh, b + dw * dh + cw * ch,
+                                                        *tail)
+        _check(rc, what)
+        return out
+
+    def resize_nv12(self, src, standard="bt709", order="rgb", out=None, stream=None):
+        """iqo_hip_resize_rgb_nv12_device on torch tensors, for packed resizers with 3 or 4 channels.  src: the
+        tensor resize_tensor takes, [F, srcH, srcW, C] (or [srcH, srcW, C]) uint8 on the plan's device; order:
+        "rgb" or "bgr", where R, G, B sit in a source pixel (a fourth channel is resized and ignored); standard: a
+        COLOR_STANDARDS name or an IQO_CS_* value.  Returns / fills out [F, dstW*dstH + 2*(dstW/2)*(dstH/2)] uint8
+        (or one such row), each frame laid out NV12 (Y, then the interleaved UV plane, tightly packed): the
+        layout Nv12Resizer.resize_frames takes and gives."""
+        return self._resize_yuv(True, src, standard, order, out, stream)
+
+    def resize_i420(self, src, standard="bt709", order="rgb", out=None, stream=None):
+        """resize_nv12 with separate chroma planes (iqo_hip_resize_rgb_yuv420_device): each frame laid out I420
+        (Y, then U, then V, tightly packed), the layout of Yuv420Resizer.resize_frames."""
+        return self._resize_yuv(False, src, standard, order, out, stream)
 
 
 class LanczosResizer(_Resizer):

@@ -2623,6 +2623,169 @@ int iqo_hip_resize_yuv420_norm_device(iqo_hip_yuv_plan *plan, size_t nFrames, si
                       stream, fused);
 }
 
+// ---- Packed RGB(A) straight to NV12 / I420, the opposite direction.  Two passes on the stream: the
+// packed plan's own resize, unchanged, into the caller's workspace, then rgb_yuv_kernel
+// (kernels_color.hip) from the workspace to the planes.  Every check runs on the host before the first
+// launch, so a rejected call launches nothing and leaves the destination untouched.
+
+// Workspace of one frame: dstH rows of packed pixels, padded to the 8 pixels a thread of rgb_yuv_kernel
+// loads and to 16 bytes, so that the first pass finds its widest stores aligned.
+static size_t rgb_yuv_ws_stride(size_t dstW, size_t C)
+{
+    return ((dstW + 7) / 8 * 8 * C + 15) & ~static_cast<size_t>(15);
+}
+
+size_t iqo_hip_rgb_yuv_workspace_bytes(size_t dstW, size_t dstH, int channels, size_t nFrames)
+{
+    const size_t kMaxSize = std::numeric_limits<size_t>::max(), kLim = size_t(1) << 31;
+    if (dstW >= kLim || dstH >= kLim || channels < 3 || channels > 4)
+        return kMaxSize;  // (no plan has such a frame)
+    const size_t frame = rgb_yuv_ws_stride(dstW, static_cast<size_t>(channels)) * dstH;
+    if (frame && nFrames > (kMaxSize - 15) / frame)
+        return kMaxSize;
+    return nFrames * frame + 15;  // + 15: the calls round the base up to 16 bytes
+}
+
+int iqo_host_rgb_to_yuv(int standard, size_t n, const uint8_t *rgb, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+    if (standard < 0 || standard >= iqo_amd::kYuvRgbStandards || !rgb || !y || !u || !v)
+        return IQO_HIP_EINVAL;
+    const iqo_amd::RgbYuvCoef &k = iqo_amd::kRgbYuv[standard];
+    constexpr int S = iqo_amd::kRgbYuvShift;
+    for (size_t i = 0; i < n; ++i) {
+        const int R = rgb[3 * i], G = rgb[3 * i + 1], B = rgb[3 * i + 2];
+        y[i] = static_cast<uint8_t>(iqo_amd::rgb_y_sum(k, R, G, B) >> S);
+        u[i] = static_cast<uint8_t>(iqo_amd::rgb_yuv_min255(iqo_amd::rgb_u_sum<S>(k, R, G, B) >> S));
+        v[i] = static_cast<uint8_t>(iqo_amd::rgb_yuv_min255(iqo_amd::rgb_v_sum<S>(k, R, G, B) >> S));
+    }
+    return IQO_HIP_OK;
+}
+
+int iqo_host_rgb_to_yuv420(int standard, size_t w, size_t h, const uint8_t *rgb, uint8_t *y, uint8_t *u, uint8_t *v)
+{
+    if (standard < 0 || standard >= iqo_amd::kYuvRgbStandards || !rgb || !y || !u || !v || w < 2 || h < 2)
+        return IQO_HIP_EINVAL;
+    const iqo_amd::RgbYuvCoef &k = iqo_amd::kRgbYuv[standard];
+    for (size_t i = 0; i < w * h; ++i)
+        y[i] = static_cast<uint8_t>(iqo_amd::rgb_y_sum(k, rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]) >> iqo_amd::kRgbYuvShift);
+    constexpr int S = iqo_amd::kRgbYuvSumShift;
+    const size_t cw = w / 2, ch = h / 2;
+    for (size_t j = 0; j < ch; ++j)
+        for (size_t i = 0; i < cw; ++i) {
+            int s[3] = {0, 0, 0};
+            for (size_t e = 0; e < 4; ++e) {
+                const uint8_t *p = rgb + 3 * ((2 * j + e / 2) * w + 2 * i + e % 2);
+                for (int c = 0; c < 3; ++c)
+                    s[c] += p[c];
+            }
+            u[j * cw + i] = static_cast<uint8_t>(iqo_amd::rgb_yuv_min255(iqo_amd::rgb_u_sum<S>(k, s[0], s[1], s[2]) >> S));
+            v[j * cw + i] = static_cast<uint8_t>(iqo_amd::rgb_yuv_min255(iqo_amd::rgb_v_sum<S>(k, s[0], s[1], s[2]) >> S));
+        }
+    return IQO_HIP_OK;
+}
+
+// A destination plane of one frame: rows of rowB bytes, `rows` of them, `st` apart
+struct RgbYuvPlane {
+    const uint8_t *p;
+    size_t rowB, rows, st;
+    uintptr_t begin() const { return reinterpret_cast<uintptr_t>(p); }
+    size_t extent() const { return (rows - 1) * st + rowB; }  // first byte to one past the last
+};
+
+static int rgb_yuv(iqo_hip_plan *h, size_t nFrames, size_t srcSt, size_t srcFrameSt, const uint8_t *src, int standard,
+                   const int *order, size_t dstStY, size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstU,
+                   uint8_t *dstV, bool interleavedUV, void *workspace, size_t workspaceBytes, void *stream)
+{
+    if (!h || !src || !dstY || !dstU || (!interleavedUV && !dstV) || !workspace || !order)
+        return IQO_HIP_EINVAL;
+    if (h->channels < 3 || h->channels > 4)
+        return IQO_HIP_EUNSUP;  // a planar plan, or 2 channels: no R, G, B to take
+    if (standard < 0 || standard >= iqo_amd::kYuvRgbStandards)
+        return IQO_HIP_EINVAL;
+    const size_t C = static_cast<size_t>(h->channels);
+    for (int c = 0; c < 3; ++c)
+        if (order[c] < 0 || order[c] >= h->channels || order[c] == order[(c + 1) % 3])
+            return IQO_HIP_EINVAL;
+    const Plan &p = h->p;
+    const size_t dstW = static_cast<size_t>(p.dstW), dstH = static_cast<size_t>(p.dstH), kLim = size_t(1) << 31;
+    if (dstW < 2 || dstH < 2)
+        return IQO_HIP_EINVAL;
+    const size_t cw = dstW / 2, ch = dstH / 2;
+    // the planes of one frame, lowest address first; none may reach into the next
+    RgbYuvPlane pl[3] = {{dstY, dstW, dstH, dstStY}, {dstU, interleavedUV ? 2 * cw : cw, ch, dstStUV}, {dstV, cw, ch, dstStUV}};
+    const int nPl = interleavedUV ? 2 : 3;
+    for (int i = 0; i < nPl; ++i)
+        if (pl[i].st < pl[i].rowB || pl[i].st >= kLim || pl[i].extent() >= kLim)
+            return IQO_HIP_EINVAL;
+    std::sort(pl, pl + nPl, [](const RgbYuvPlane &a, const RgbYuvPlane &b) { return a.begin() < b.begin(); });
+    for (int i = 0; i + 1 < nPl; ++i)
+        if (pl[i + 1].begin() - pl[i].begin() < pl[i].extent())
+            return IQO_HIP_EINVAL;
+    // frames follow each other dstFrameSt apart: the highest plane must end before the lowest begins again
+    if (nFrames > 1 && dstFrameSt < pl[nPl - 1].begin() - pl[0].begin() + pl[nPl - 1].extent())
+        return IQO_HIP_EINVAL;
+    if (!yuv_src_ok(p, C, srcSt))
+        return IQO_HIP_EINVAL;
+    // the kernel addresses one workspace frame with 32-bit offsets
+    const size_t wsSt = rgb_yuv_ws_stride(dstW, C), wsFrame = wsSt * dstH;
+    if (wsFrame >= kLim || workspaceBytes < iqo_hip_rgb_yuv_workspace_bytes(dstW, dstH, h->channels, nFrames))
+        return IQO_HIP_EINVAL;
+    if (nFrames == 0)
+        return IQO_HIP_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *ws = yuv_rgb_ws_base(workspace);
+    const int r1 = run_band(h, nFrames, 0, dstH, 0, srcSt, srcFrameSt, src, wsSt, wsFrame, ws, s);
+    if (r1)
+        return r1;
+    DeviceGuard guard(h->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    iqo_amd::RgbYuvDev d{};
+    d.dstW = p.dstW;
+    d.dstH = p.dstH;
+    d.k = iqo_amd::kRgbYuv[standard];
+    for (int c = 0; c < 3; ++c)
+        d.order[c] = order[c];
+    d.srcSt = static_cast<int>(wsSt);
+    d.srcFrameSt = static_cast<int64_t>(wsFrame);
+    d.ySt = static_cast<int>(dstStY);
+    d.cSt = static_cast<int>(dstStUV);
+    d.dstFrameSt = static_cast<int64_t>(dstFrameSt);
+    // frames per launch: the kernel counts (frame, row pair, pixel group) items in 31 bits
+    const size_t perFrame = ((dstH + 1) / 2) * ((dstW + 7) / 8);
+    const size_t chunk = std::max<size_t>(1, ((size_t(1) << 31) - 1) / perFrame);
+    for (size_t f0 = 0; f0 < nFrames; f0 += chunk) {
+        d.frames = static_cast<int>(std::min(chunk, nFrames - f0));
+        d.src = ws + f0 * wsFrame;
+        d.y = dstY + f0 * dstFrameSt;
+        d.u = dstU + f0 * dstFrameSt;
+        d.v = interleavedUV ? nullptr : dstV + f0 * dstFrameSt;
+        const hipError_t e = iqo_amd::launch_rgb_yuv(d, h->channels, interleavedUV, s);
+        if (e == hipErrorInvalidValue)
+            return IQO_HIP_EINVAL;
+        if (e != hipSuccess)
+            return IQO_HIP_EHIP;
+    }
+    return IQO_HIP_OK;
+}
+
+int iqo_hip_resize_rgb_nv12_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
+                                   int standard, const int *order, size_t dstStY, size_t dstStUV, size_t dstFrameSt,
+                                   uint8_t *dstY, uint8_t *dstUV, void *workspace, size_t workspaceBytes, void *stream)
+{
+    return rgb_yuv(plan, nFrames, srcSt, srcFrameSt, src, standard, order, dstStY, dstStUV, dstFrameSt, dstY, dstUV, nullptr,
+                   true, workspace, workspaceBytes, stream);
+}
+
+int iqo_hip_resize_rgb_yuv420_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
+                                     int standard, const int *order, size_t dstStY, size_t dstStUV, size_t dstFrameSt,
+                                     uint8_t *dstY, uint8_t *dstU, uint8_t *dstV, void *workspace, size_t workspaceBytes,
+                                     void *stream)
+{
+    return rgb_yuv(plan, nFrames, srcSt, srcFrameSt, src, standard, order, dstStY, dstStUV, dstFrameSt, dstY, dstU, dstV,
+                   false, workspace, workspaceBytes, stream);
+}
+
 int iqo_hip_resize_yuv420(iqo_hip_yuv_plan *yp, size_t srcStY, const uint8_t *srcY, size_t srcStUV,
                           const uint8_t *srcU, const uint8_t *srcV, size_t dstStY, uint8_t *dstY, size_t dstStUV,
                           uint8_t *dstU, uint8_t *dstV)

@@ -105,6 +105,28 @@ hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, bool chr
 // Planar floats as the packed kernels' NORM epilogue, of the 3-channel source (R, G, B).
 hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, bool chroma444, const NormDev &n, hipStream_t s);
 
+// --- packed RGB(A) -> YUV 4:2:0 planes (kernels_color.hip): the second pass of the "resize to NV12 /
+// I420" entries.  Reads resized packed pixels (C = 3 or 4 bytes each, dstW x dstH) from a workspace,
+// applies the forward integer matrix of colorspace.hpp -- Y per pixel, U and V once per 2 x 2 block on the
+// block's sums, cw x ch = dstW/2 x dstH/2 samples -- and writes a Y plane and an interleaved UV plane
+// (NV12) or U and V planes (I420).  An odd dstW's last column and an odd dstH's last row give Y only.
+// Workspace rows: base, srcSt and srcFrameSt are multiples of 16 with srcSt >= 8 C ceil(dstW / 8) -- a
+// thread loads its 8 pixels of two rows whole; the pad pixels past dstW are never stored.  No alignment of
+// the destinations beyond a byte.
+struct RgbYuvDev {
+    int dstW, dstH;
+    RgbYuvCoef k;                      // the standard's ten integers
+    int order[3];                      // the byte of a source pixel that holds R, G, B (distinct, < C)
+    const uint8_t *src;                // frame 0 of the workspace
+    int srcSt;                         // row stride, bytes (one frame < 2^31)
+    int64_t srcFrameSt;
+    uint8_t *y, *u, *v;                // frame 0's planes; interleaved UV: u, and v is not written
+    int ySt, cSt;                      // row strides, bytes (each plane of one frame < 2^31)
+    int64_t dstFrameSt;
+    int frames;                        // frames x ceil(dstH / 2) x ceil(dstW / 8) < 2^31
+};
+hipError_t launch_rgb_yuv(const RgbYuvDev &d, int channels, bool interleavedUV, hipStream_t s);
+
 // --- general-ratio wave walker: every wave walks a 256-column strip of one band of rows through
 // a private LDS ring of source rows widened to u16 (plan.hpp WalkTables; 4-byte aligned sources).
 struct WalkDev {

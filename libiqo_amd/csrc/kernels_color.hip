@@ -17,6 +17,10 @@
 // so a wave's loads and stores are contiguous within a row and follow on into the next one.
 // With C444 pixel (y, x) takes chroma sample (y, x): 8 chroma pairs per thread (one 16-byte load of
 // UV, or 8 bytes each of U and V), the chroma terms once per pixel, and no index clamp or edge fetch.
+//
+// The opposite direction, rgb_yuv_kernel<C, UV2> (resized packed RGB(A) pixels in, a Y plane and 4:2:0
+// chroma out: the second pass of iqo_hip_resize_rgb_nv12_device / _rgb_yuv420_device), is at the end of
+// the file with its own description.
 #include "kernels_dev.hpp"
 
 namespace iqo_amd {
@@ -340,6 +344,193 @@ hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, bool chro
     a.n = n;
     const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
     const void *kern = px == 4 ? kernel_of<true, 4>(interleavedUV, chroma444) : kernel_of<true, 8>(interleavedUV, chroma444);
+    void *args[] = {&a};
+    return hipLaunchKernel(kern, dim3(blocks), dim3(256), args, 0, s);
+}
+
+// ---- rgb_yuv_kernel<C, UV2>: the second pass of the "resize to NV12 / I420" entries
+// (include/iqo_hip.h iqo_hip_resize_rgb_nv12_device / _rgb_yuv420_device): resized packed pixels in, a Y
+// plane and 4:2:0 chroma out.  C: 3 or 4 bytes per pixel; UV2: one interleaved UV plane (NV12) / separate
+// U and V planes (I420).
+//
+// Memory-bound, no LDS.  A thread owns 8 adjacent pixels of a ROW PAIR (rows 2 p and 2 p + 1): whole
+// loads of its 8 C bytes of both rows (two 16-byte loads per row at C = 4, 16 + 8 bytes at C = 3), the
+// forward matrix of colorspace.hpp in registers, 8 Y bytes per row, and 4 chroma samples from the sums of
+// its four 2 x 2 blocks: one 8-byte UV store, or 4 bytes each of U and V.  Stores follow store_bytes'
+// rule: the widest the address allows, single bytes in a row's partial last group or at a misaligned
+// destination.  Threads run over (frame, row pair, pixel group) in that order.
+// An odd dstH's last row has no partner: it is a pair of its own whose second row is neither loaded nor
+// given chroma.  An odd dstW's last column lies past the last whole 2 x 2 block and gives Y only.  The
+// workspace's pad pixels past dstW are read (whatever they hold) and never stored: chroma sample i takes
+// columns 2 i and 2 i + 1 <= 2 cw - 1 < dstW.
+namespace {
+
+struct RgbYuvArgs {
+    RgbYuvDev d;
+    int nG, nP;         // pixel groups (one per thread) per row, row pairs per frame
+    unsigned items;     // frames x nP x nG
+    // Where R, G, B sit in a pixel, built from d.order by the launcher.
+    // C = 4: a pixel is a word, sel[c] = 8 order[c] is the bit offset of R, G, B in it.
+    // C = 3: 4 pixels are 3 words; pixel j's (R, G, B, 0) is v_perm(word min(j, 2), word max(j, 1) - 1, sel[j]).
+    uint32_t sel[4];
+};
+
+typedef u32x4 u32x4_a8 __attribute__((aligned(8)));  // C = 3: a thread's 24 bytes start at a multiple of 8
+
+// The 8 pixels a thread owns of one workspace row, p at the first of them
+template <int C>
+__device__ __forceinline__ void rgb_load(const uint8_t *p, const uint32_t (&sel)[4], int (&R)[8], int (&G)[8], int (&B)[8])
+{
+    if constexpr (C == 4) {
+        const u32x4 a = reinterpret_cast<const u32x4 *>(p)[0], b = reinterpret_cast<const u32x4 *>(p)[1];
+        const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            R[k] = static_cast<int>((w[k] >> sel[0]) & 0xffu);
+            G[k] = static_cast<int>((w[k] >> sel[1]) & 0xffu);
+            B[k] = static_cast<int>((w[k] >> sel[2]) & 0xffu);
+        }
+    } else {
+        const u32x4_a8 a = *reinterpret_cast<const u32x4_a8 *>(p);
+        const u32x2 b = *reinterpret_cast<const u32x2 *>(p + 16);
+        const uint32_t w[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t px = __builtin_amdgcn_perm(w[3 * q + (j < 2 ? j : 2)], w[3 * q + (j > 1 ? j - 1 : 0)], sel[j]);
+                R[4 * q + j] = static_cast<int>(byte_of(px, 0));
+                G[4 * q + j] = static_cast<int>(byte_of(px, 1));
+                B[4 * q + j] = static_cast<int>(byte_of(px, 2));
+            }
+    }
+}
+
+// (v[0] >> S, ..., v[3] >> S) as the bytes of a word, each saturated to 255 (v_ashr_pk_u8_i32; the
+// accumulators of colorspace.hpp's forward matrix are never negative)
+template <int S>
+__device__ __forceinline__ uint32_t pack4(int a, int b, int c, int e)
+{
+    return ashr_pk_hi<S>(ashr_pk_lo<S>(a, b), c, e);
+}
+
+// NB = 8 or 4 bytes (the words o[]) to p, of which the first `valid` are inside the row
+template <int NB>
+__device__ __forceinline__ void store_run(uint8_t *p, const uint32_t (&o)[NB / 4], int valid)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const bool full = valid == NB;
+    if (NB == 8 && full && !(a & 7)) {
+        *reinterpret_cast<u32x2 *>(p) = u32x2{o[0], o[NB / 4 - 1]};
+    } else if (full && !(a & 3)) {
+#pragma unroll
+        for (int i = 0; i < NB / 4; ++i)
+            reinterpret_cast<uint32_t *>(p)[i] = o[i];
+    } else {
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (b < valid)
+                p[b] = static_cast<uint8_t>(o[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+__device__ __forceinline__ void store_y(uint8_t *p, const RgbYuvCoef &k, const int (&R)[8], const int (&G)[8],
+                                        const int (&B)[8], int valid)
+{
+    int y[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        y[i] = rgb_y_sum(k, R[i], G[i], B[i]);
+    const uint32_t o[2] = {pack4<kRgbYuvShift>(y[0], y[1], y[2], y[3]), pack4<kRgbYuvShift>(y[4], y[5], y[6], y[7])};
+    store_run<8>(p, o, valid);
+}
+
+template <int C, bool UV2>
+__global__ __launch_bounds__(256) void rgb_yuv_kernel(RgbYuvArgs a)
+{
+    const RgbYuvDev &d = a.d;
+    const unsigned nG = static_cast<unsigned>(a.nG), nP = static_cast<unsigned>(a.nP);
+    const int cw = d.dstW >> 1;
+    for (unsigned it = blockIdx.x * 256u + threadIdx.x; it < a.items; it += gridDim.x * 256u) {
+        const unsigned t = it / nG;
+        const int g = static_cast<int>(it - t * nG), f = static_cast<int>(t / nP), rp = static_cast<int>(t - (t / nP) * nP);
+        const int row = 2 * rp, valid = min(8, d.dstW - 8 * g);
+        const uint8_t *sp = d.src + static_cast<int64_t>(f) * d.srcFrameSt + static_cast<int64_t>(row) * d.srcSt + 8 * C * g;
+        const int64_t fo = static_cast<int64_t>(f) * d.dstFrameSt;
+        uint8_t *yp = d.y + fo + static_cast<int64_t>(row) * d.ySt + 8 * g;
+        int R[8], G[8], B[8];
+        rgb_load<C>(sp, a.sel, R, G, B);
+        store_y(yp, d.k, R, G, B, valid);
+        if (row + 1 >= d.dstH)
+            continue;  // an odd dstH's last row: no second row, no chroma
+        int R1[8], G1[8], B1[8];
+        rgb_load<C>(sp + d.srcSt, a.sel, R1, G1, B1);
+        store_y(yp + d.ySt, d.k, R1, G1, B1, valid);
+        const int nc = min(4, cw - 4 * g);  // chroma samples of the run inside the plane
+        if (nc <= 0)
+            continue;
+        int u[4], v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int sr = R[2 * q] + R[2 * q + 1] + R1[2 * q] + R1[2 * q + 1];
+            const int sg = G[2 * q] + G[2 * q + 1] + G1[2 * q] + G1[2 * q + 1];
+            const int sb = B[2 * q] + B[2 * q + 1] + B1[2 * q] + B1[2 * q + 1];
+            u[q] = rgb_u_sum<kRgbYuvSumShift>(d.k, sr, sg, sb);
+            v[q] = rgb_v_sum<kRgbYuvSumShift>(d.k, sr, sg, sb);
+        }
+        const int64_t co = fo + static_cast<int64_t>(rp) * d.cSt;
+        if constexpr (UV2) {
+            const uint32_t o[2] = {pack4<kRgbYuvSumShift>(u[0], v[0], u[1], v[1]),
+                                   pack4<kRgbYuvSumShift>(u[2], v[2], u[3], v[3])};
+            store_run<8>(d.u + co + 8 * g, o, 2 * nc);
+        } else {
+            const uint32_t ou[1] = {pack4<kRgbYuvSumShift>(u[0], u[1], u[2], u[3])};
+            const uint32_t ov[1] = {pack4<kRgbYuvSumShift>(v[0], v[1], v[2], v[3])};
+            store_run<4>(d.u + co + 4 * g, ou, nc);
+            store_run<4>(d.v + co + 4 * g, ov, nc);
+        }
+    }
+}
+
+} // namespace
+
+hipError_t launch_rgb_yuv(const RgbYuvDev &d, int channels, bool interleavedUV, hipStream_t s)
+{
+    if (channels < 3 || channels > 4 || d.dstW < 2 || d.dstH < 2 || d.frames < 0 || !d.src || !d.y || !d.u ||
+        (!interleavedUV && !d.v))
+        return hipErrorInvalidValue;
+    for (int c = 0; c < 3; ++c)
+        if (d.order[c] < 0 || d.order[c] >= channels || d.order[c] == d.order[(c + 1) % 3])
+            return hipErrorInvalidValue;
+    const int nG = (d.dstW + 7) / 8, nP = (d.dstH + 1) / 2, cw = d.dstW / 2;
+    if (d.srcSt < 8 * channels * nG || (d.srcSt & 15) || (d.srcFrameSt & 15) || (reinterpret_cast<uintptr_t>(d.src) & 15) ||
+        d.ySt < d.dstW || d.cSt < (interleavedUV ? 2 : 1) * cw)
+        return hipErrorInvalidValue;
+    if (static_cast<uint64_t>(d.frames) * static_cast<uint64_t>(nP) * static_cast<uint64_t>(nG) >= (uint64_t(1) << 31))
+        return hipErrorInvalidValue;
+    if (d.frames == 0)
+        return hipSuccess;
+    RgbYuvArgs a{};
+    a.d = d;
+    a.nG = nG;
+    a.nP = nP;
+    a.items = static_cast<unsigned>(d.frames) * static_cast<unsigned>(nP) * static_cast<unsigned>(nG);
+    if (channels == 4) {
+        for (int c = 0; c < 3; ++c)
+            a.sel[c] = 8u * static_cast<uint32_t>(d.order[c]);
+    } else {
+        // pixel j of 4 starts at byte 3 j of the 3 words: byte `off` of the pair (lo, hi) v_perm selects from
+        // (selector bytes 0 .. 3 pick from lo, 4 .. 7 from hi, 0x0c is the constant 0)
+        const uint32_t off[4] = {0, 3, 2, 1};
+        for (int j = 0; j < 4; ++j)
+            a.sel[j] = (off[j] + static_cast<uint32_t>(d.order[0])) | ((off[j] + static_cast<uint32_t>(d.order[1])) << 8) |
+                       ((off[j] + static_cast<uint32_t>(d.order[2])) << 16) | (0x0cu << 24);
+    }
+    const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
+    const void *kern = channels == 4 ? (interleavedUV ? reinterpret_cast<const void *>(rgb_yuv_kernel<4, true>)
+                                                      : reinterpret_cast<const void *>(rgb_yuv_kernel<4, false>))
+                                     : (interleavedUV ? reinterpret_cast<const void *>(rgb_yuv_kernel<3, true>)
+                                                      : reinterpret_cast<const void *>(rgb_yuv_kernel<3, false>));
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(blocks), dim3(256), args, 0, s);
 }

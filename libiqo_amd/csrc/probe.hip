@@ -62,7 +62,7 @@ hipError_t launch(bool nt, const void *src, void *dst, size_t units, hipStream_t
 } // namespace
 
 // Reads R KiB and writes W KiB per unit, `units` units: srcBytes >= units R KiB, dstBytes >= units
-// W KiB (the caller sizes the buffers).  (R, W) in {(1, 8), (1, 4), (1, 1), (4, 1), (16, 1)}.  Returns 0, or
+// W KiB (the caller sizes the buffers).  (R, W) in {(1, 8), (1, 4), (1, 1), (4, 1), (16, 1), (2, 1), (8, 3)}.  Returns 0, or
 // -1 for an unsupported mix / bad arguments, -2 for a launch error.
 extern "C" int iqo_probe_stream(int R, int W, int nt, const void *src, size_t srcBytes, void *dst, size_t dstBytes,
                                 void *stream)
@@ -84,6 +84,10 @@ extern "C" int iqo_probe_stream(int R, int W, int nt, const void *src, size_t sr
         e = launch<4, 1>(nt != 0, src, dst, units, s);
     else if (R == 16 && W == 1)
         e = launch<16, 1>(nt != 0, src, dst, units, s);
+    else if (R == 2 && W == 1)  // packed RGB in, 4:2:0 planes out: 3 : 1.5 (benchmark/rgb_nv12.py)
+        e = launch<2, 1>(nt != 0, src, dst, units, s);
+    else if (R == 8 && W == 3)  // ... RGBA: 4 : 1.5
+        e = launch<8, 3>(nt != 0, src, dst, units, s);
     else
         return -1;
     return e == hipSuccess ? 0 : -2;
