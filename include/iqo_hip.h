@@ -166,7 +166,8 @@ int iqo_hip_resize_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size
  * (iqo_hip_plan_prepare beforehand for graph capture).  The option "force_general" applies.
  *
  * Plans with channels 2..4 only: a planar (1-channel) plan returns IQO_HIP_EUNSUP -- planar plans
- * dispatch to sixteen kernel families, none of which has the float epilogue.
+ * dispatch to sixteen kernel families, none of which has the float epilogue; planar sources go through
+ * iqo_hip_resize_planes_norm_device below.
  * IQO_HIP_EINVAL: a null plan, dSrc, dDst or norm; an unknown dtype; planes outside 1..4; an order[p]
  * outside 0..channels-1; a non-finite scale[p] or bias[p] (p < planes; entries from `planes` on are
  * ignored); dDst or a destination stride that is no multiple of elem; srcSt < srcW*channels;
@@ -184,6 +185,50 @@ typedef struct {
 int iqo_hip_resize_device_norm(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt,
                                const uint8_t *dSrc, const iqo_hip_norm *norm, size_t dstRowSt,
                                size_t dstPlaneSt, size_t dstFrameSt, void *dDst, void *stream);
+
+/* ---- Planar U8 frames straight to the same normalised planar float tensors: [F, P, H, W] bytes as an
+ * image decoder leaves them (P = 3 planar RGB, P = 1 grey), or the Y plane of a video frame.
+ *
+ * `plan` is a 1-channel plan: from iqo_hip_plan_lanczos / _area / _linear, from iqo_hip_plan_packed with
+ * channels == 1, or plane 0 of an NV12 / I420 plan (iqo_hip_nv12_plane(p, 0), iqo_hip_yuv_plane(p, 0):
+ * both are ordinary 1-channel plans built by the constructors above, so luma-only input to a model
+ * needs no chroma work).  Source plane c (0 <= c < srcPlanes, srcPlanes in 1..4) of frame f starts at
+ * dSrc + f*srcFrameSt + c*srcPlaneSt with rows srcSt bytes apart.  Sources are only read, so planes may
+ * alias or lie apart (a crop view, the Y plane inside an NV12 frame); srcPlaneSt is ignored when
+ * srcPlanes == 1.  With u8(f, c, y, x) exactly the byte iqo_hip_resize_device writes for the same plan
+ * with source plane (f, c) as its frame,
+ *
+ *   out(f, p, y, x) = cvt( fl32( fl32( (float)u8(f, norm->order[p], y, x) * scale[p] ) + bias[p] ) )
+ *
+ * which is iqo_hip_resize_device_norm's contract word for word (two separately rounded fp32 operations,
+ * nearest-even to fp16 / bf16, overflow to +-inf, the same destination addressing and alignment), with
+ * order[p] the SOURCE PLANE of output plane p: repeats (grey -> three planes), drops (RGBA planes -> RGB)
+ * and permutations (BGR -> RGB) are allowed.
+ *
+ * Two passes on `stream`, no allocation and no synchronisation in either (capturable after
+ * iqo_hip_plan_prepare): the plan's own resize of every source plane that `order` references, through
+ * the path of iqo_hip_resize_device (so whatever kernel family the layout gets), into `workspace`, then
+ * one memory-bound kernel from the workspace to dDst.  A plane that `order` does not reference is not
+ * resized.  When every plane is referenced and srcFrameSt == srcPlanes*srcPlaneSt (the contiguous
+ * tensor) the first pass is one batch of nFrames*srcPlanes frames; otherwise one batch per referenced
+ * plane.  `workspace` is device memory of at least
+ * iqo_hip_planes_norm_workspace_bytes(dstW, dstH, srcPlanes, nFrames) bytes, any alignment, contents
+ * unspecified afterwards; it may be reused by later calls on the same stream.  The query is host-only,
+ * saturates at SIZE_MAX instead of wrapping and returns SIZE_MAX for srcPlanes outside 1..4 (or
+ * dstW / dstH >= 2^31).
+ *
+ * IQO_HIP_EUNSUP: a plan whose channels are not 1 (packed plans have iqo_hip_resize_device_norm).
+ * IQO_HIP_EINVAL: a null plan, dSrc, dDst, norm or workspace; srcPlanes outside 1..4; everything
+ * iqo_hip_resize_device_norm rejects of a norm and its destination, with order[p] outside
+ * 0..srcPlanes-1; srcSt < srcW; srcSt >= 2^24; a source plane that reaches 2^31 bytes; workspaceBytes
+ * below the query's value.  nFrames == 0 returns IQO_HIP_OK after the checks.  Every check runs before
+ * the first launch: on any error nothing is launched and the destination is untouched. */
+size_t iqo_hip_planes_norm_workspace_bytes(size_t dstW, size_t dstH, int srcPlanes, size_t nFrames);
+int iqo_hip_resize_planes_norm_device(iqo_hip_plan *plan, size_t nFrames, int srcPlanes, size_t srcSt,
+                                      size_t srcPlaneSt, size_t srcFrameSt, const uint8_t *dSrc,
+                                      const iqo_hip_norm *norm, size_t dstRowSt, size_t dstPlaneSt,
+                                      size_t dstFrameSt, void *dDst, void *workspace, size_t workspaceBytes,
+                                      void *stream);
 
 /* Source rows [*srcRow0, *srcRow0 + *srcRows) that output rows [dstRow0, dstRow0 + dstRows)
  * read (the halo of a row band).  Host-only, no device work. */

@@ -100,6 +100,12 @@ def lib():
     L.iqo_hip_resize_device.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_sz, _vp, _vp]
     L.iqo_hip_resize_device_norm.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _vp, ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz,
                                              _vp, _vp]
+    L.iqo_hip_planes_norm_workspace_bytes.argtypes = [_c_sz, _c_sz, ctypes.c_int, _c_sz]
+    L.iqo_hip_planes_norm_workspace_bytes.restype = _c_sz
+    # plan, nFrames, srcPlanes, srcSt, srcPlaneSt, srcFrameSt, src, norm, the destination's strides and base,
+    # workspace, workspaceBytes, stream
+    L.iqo_hip_resize_planes_norm_device.argtypes = [_vp, _c_sz, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
+                                                    ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp]
     L.iqo_hip_band_src_rows.argtypes = [_vp, _c_sz, _c_sz, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]
     L.iqo_hip_resize_band.argtypes = [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_sz, _vp, _vp]
     L.iqo_hip_strerror.restype = ctypes.c_char_p
@@ -308,6 +314,12 @@ def rgb_yuv_workspace_bytes(dstW, dstH, channels, nFrames):
     return int(lib().iqo_hip_rgb_yuv_workspace_bytes(dstW, dstH, channels, nFrames))
 
 
+def planes_norm_workspace_bytes(dstW, dstH, srcPlanes, nFrames):
+    """Bytes of device workspace a resize_planes_normalized / resize_luma_normalized call with `srcPlanes`
+    (1..4) source planes per frame needs -- host only."""
+    return int(lib().iqo_hip_planes_norm_workspace_bytes(dstW, dstH, srcPlanes, nFrames))
+
+
 def host_rgb_to_yuv(standard, rgb):
     """The library's integer RGB -> YUV formula in its 4:4:4 form (include/iqo_hip.h, IQO_CS_*) on a numpy
     uint8 array [..., 3] (R, G, B), in plain C++ on the host -- no GPU.  Returns (y, u, v), uint8 [...]."""
@@ -353,6 +365,47 @@ def _stream_ptr(stream):
     if isinstance(stream, int):
         return stream
     return stream.cuda_stream  # torch.cuda.Stream on ROCm wraps a hipStream_t
+
+
+def _planes_norm(r, what, plan, src4, layout, scale, bias, dtype, order, squeeze, out, stream):
+    """resize_planes_normalized / resize_luma_normalized: iqo_hip_resize_planes_norm_device with the 1-channel
+    plan `plan` of resizer `r`.  layout: (frames, srcPlanes, srcSt, srcPlaneSt, srcFrameSt, address) of the
+    source `src4` lies on; order, scale, bias: one entry per output plane."""
+    import torch
+    if dtype is None:
+        dtype = torch.float32
+    codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+    if dtype not in codes:
+        raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    frames, P, src_st, plane_st, frame_st, addr = layout
+    order = tuple(int(c) for c in order)
+    scale, bias = tuple(float(v) for v in scale), tuple(float(v) for v in bias)
+    planes = len(order)
+    if not 1 <= planes <= 4 or len(scale) != planes or len(bias) != planes:
+        raise IqoError("order, scale and bias must have the same length, 1..4 (one entry per output plane)")
+    if any(not 0 <= c < P for c in order):
+        raise IqoError("order entries must be source planes, 0..%d" % (P - 1))
+    dev = src4.device
+    shape = (frames, planes, r.dstH, r.dstW)
+    if out is None:
+        out = torch.empty(shape[1:] if squeeze else shape, dtype=dtype, device=dev)
+    o = out.unsqueeze(0) if out.dim() == 3 else out
+    if (o.dtype != dtype or o.device != dev or tuple(o.shape) != shape or o.stride(3) != 1
+            or o.stride(2) < r.dstW or o.stride(1) < r.dstH * o.stride(2)
+            or (o.shape[0] > 1 and o.stride(0) < planes * o.stride(1))):
+        raise IqoError("out must be a %s tensor [%d, %d, %d, %d] on %s with unit column stride and "
+                       "non-overlapping rows, planes and frames" % ((dtype,) + shape + (dev,)))
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    n = Norm(codes[dtype], planes)
+    for i in range(planes):
+        n.order[i], n.scale[i], n.bias[i] = order[i], scale[i], bias[i]
+    e = o.element_size()
+    ws = _Resizer._yuv_workspace(r, planes_norm_workspace_bytes(r.dstW, r.dstH, P, frames), dev, stream)
+    _check(lib().iqo_hip_resize_planes_norm_device(plan, frames, P, src_st, plane_st, frame_st, addr, ctypes.byref(n),
+                                                   o.stride(2) * e, o.stride(1) * e, o.stride(0) * e, _ptr(o),
+                                                   _ptr(ws), ws.numel(), _stream_ptr(stream)), what)
+    return out
 
 
 class _Resizer:
@@ -507,6 +560,35 @@ class _Resizer:
                                                 ctypes.byref(n), o.stride(2) * e, o.stride(1) * e, o.stride(0) * e,
                                                 _ptr(o), _stream_ptr(stream)), "resize_normalized")
         return out
+
+    # -- planar plans straight to a model's input: CHW bytes in, planar float planes out
+    def resize_planes_normalized(self, src, scale, bias, dtype=None, order=None, out=None, stream=None):
+        """iqo_hip_resize_planes_norm_device on torch tensors, for 1-channel resizers.  src: [F, P, srcH, srcW]
+        (or [P, srcH, srcW]) uint8 on the plan's device, P in 1..4: planar RGB from an image decoder, grey
+        images, a crop or a channel slice of either.  A strided view is read where it lies, without a copy, as
+        long as its column stride is 1 and its row, plane and frame strides are positive (.contiguous() is
+        taken otherwise).  Returns / fills out [F, planes, dstH, dstW] (or [planes, dstH, dstW]) of `dtype`
+        (float32, float16 or bfloat16): plane p is float32(byte of source plane order[p]) * scale[p] + bias[p],
+        each operation rounded to float32, then rounded to `dtype` -- what resize_tensor on the planes followed
+        by those two torch operations gives, bit for bit.  planes = len(order), or P with the identity order;
+        order may repeat, drop and permute source planes, and a plane it does not name is not resized.  `out`
+        may be a strided view with unit column stride and non-overlapping rows, planes and frames; it is
+        returned."""
+        import torch
+        if self.channels > 1:
+            raise IqoError("resize_planes_normalized needs a 1-channel resizer; packed resizers have "
+                           "resize_normalized")
+        squeeze = src.dim() == 3
+        s = src.unsqueeze(0) if squeeze else src
+        if (s.dtype != torch.uint8 or not s.is_cuda or s.dim() != 4 or not 1 <= s.shape[1] <= 4
+                or tuple(s.shape[2:]) != (self.srcH, self.srcW)):
+            raise IqoError("expected uint8 device tensor [F, P, %d, %d] with P in 1..4" % (self.srcH, self.srcW))
+        if s.stride(3) != 1 or min(s.stride(0), s.stride(1), s.stride(2)) < 1:
+            s = s.contiguous()
+        P = s.shape[1]
+        layout = (s.shape[0], P, s.stride(2), s.stride(1), s.stride(0), s.data_ptr())
+        return _planes_norm(self, "resize_planes_normalized", self._plan, s, layout, scale, bias, dtype,
+                            tuple(range(P)) if order is None else order, squeeze, out, stream)
 
     # -- packed RGB(A) plans straight to an encoder's input: a Y plane and 4:2:0 chroma
     def _yuv_workspace(self, nbytes, device, stream):
@@ -740,6 +822,19 @@ class _YuvToRgb:
         ws, nbytes = self._workspace(s, stream)
         self._to_norm(s, cs, n, o.stride(2) * e, o.stride(1) * e, o.stride(0) * e, o, ws, nbytes, stream)
         return out
+
+
+    def resize_luma_normalized(self, src, scale, bias, dtype=None, out=None, stream=None):
+        """Luma only, for models that take no colour: the Y plane of each frame resized by plane 0's plan and
+        written as `planes` = len(scale) = len(bias) (1..4) normalised planes, all taken from Y
+        (iqo_hip_resize_planes_norm_device with srcPlanes 1 and order all zero).  src: the tight frame layout of
+        resize_frames.  Chroma is neither resized nor read, and the chroma mode has no effect.  Returns / fills
+        out [F, planes, dstH, dstW] of `dtype` as resize_normalized does."""
+        s = self._src_frames(src)
+        scale = tuple(scale)
+        layout = (s.shape[0], 1, self.srcW, 0, s.stride(0), s.data_ptr())
+        return _planes_norm(self, "resize_luma_normalized", self._plane(0), s, layout, scale, bias, dtype,
+                            (0,) * len(scale), False, out, stream)
 
 
 class Yuv420Resizer(_YuvToRgb):

@@ -2623,6 +2623,146 @@ int iqo_hip_resize_yuv420_norm_device(iqo_hip_yuv_plan *plan, size_t nFrames, si
                       stream, fused);
 }
 
+// ---- Planar U8 frames ([F, P, H, W] tensors, grey images, a video frame's Y plane) straight to normalised
+// planar floats.  Two passes on the stream: the 1-channel plan's own resize, unchanged (run_band over the
+// full frame, so whatever kernel family the layout gets), into the caller's workspace, then
+// planes_norm_kernel (kernels_norm.hip) from the workspace to the destination.  Every check runs on the
+// host before the first launch, so a rejected call launches nothing and leaves the destination untouched.
+
+// Workspace of one frame: srcPlanes planes of dstH rows, each row padded to the 8 pixels a thread of
+// planes_norm_kernel loads and to 16 bytes, so that every plan kernel finds its widest stores aligned.
+struct PlanesNormWs {
+    size_t st, plane, frame;
+};
+
+static PlanesNormWs planes_norm_ws(size_t dstW, size_t dstH, size_t srcPlanes)
+{
+    PlanesNormWs w;
+    w.st = ((dstW + 7) / 8 * 8 + 15) & ~static_cast<size_t>(15);
+    w.plane = w.st * dstH;
+    w.frame = w.plane * srcPlanes;
+    return w;
+}
+
+size_t iqo_hip_planes_norm_workspace_bytes(size_t dstW, size_t dstH, int srcPlanes, size_t nFrames)
+{
+    const size_t kMaxSize = std::numeric_limits<size_t>::max(), kLim = size_t(1) << 31;
+    if (dstW >= kLim || dstH >= kLim || srcPlanes < 1 || srcPlanes > 4)
+        return kMaxSize;  // (no plan has such a frame)
+    // (a plane is below 2^63: four of them can pass 2^64)
+    if (planes_norm_ws(dstW, dstH, 1).plane > (kMaxSize - 15) / static_cast<size_t>(srcPlanes))
+        return kMaxSize;
+    const size_t frame = planes_norm_ws(dstW, dstH, static_cast<size_t>(srcPlanes)).frame;
+    if (frame && nFrames > (kMaxSize - 15) / frame)
+        return kMaxSize;
+    return nFrames * frame + 15;  // + 15: the call rounds the base up to 16 bytes
+}
+
+int iqo_hip_resize_planes_norm_device(iqo_hip_plan *h, size_t nFrames, int srcPlanes, size_t srcSt, size_t srcPlaneSt,
+                                      size_t srcFrameSt, const uint8_t *dSrc, const iqo_hip_norm *norm, size_t dstRowSt,
+                                      size_t dstPlaneSt, size_t dstFrameSt, void *dDst, void *workspace,
+                                      size_t workspaceBytes, void *stream)
+{
+    if (!h || !dSrc || !dDst || !norm || !workspace)
+        return IQO_HIP_EINVAL;
+    if (h->channels != 1)  // packed plans: iqo_hip_resize_device_norm
+        return IQO_HIP_EUNSUP;
+    if (srcPlanes < 1 || srcPlanes > 4)
+        return IQO_HIP_EINVAL;
+    // the norm and its destination, as run_norm
+    if (norm->dtype != IQO_OUT_F32 && norm->dtype != IQO_OUT_F16 && norm->dtype != IQO_OUT_BF16)
+        return IQO_HIP_EINVAL;
+    if (norm->planes < 1 || norm->planes > 4)
+        return IQO_HIP_EINVAL;
+    unsigned used = 0;  // bit c: source plane c is referenced
+    for (int i = 0; i < norm->planes; ++i) {
+        if (norm->order[i] < 0 || norm->order[i] >= srcPlanes || !std::isfinite(norm->scale[i]) ||
+            !std::isfinite(norm->bias[i]))
+            return IQO_HIP_EINVAL;
+        used |= 1u << norm->order[i];
+    }
+    const Plan &p = h->p;
+    const size_t elem = norm->dtype == IQO_OUT_F32 ? 4 : 2;
+    const size_t dstW = static_cast<size_t>(p.dstW), dstH = static_cast<size_t>(p.dstH);
+    const size_t planes = static_cast<size_t>(norm->planes), P = static_cast<size_t>(srcPlanes);
+    if (reinterpret_cast<uintptr_t>(dDst) % elem || dstRowSt % elem || dstPlaneSt % elem || dstFrameSt % elem)
+        return IQO_HIP_EINVAL;
+    // (divisions: no product of caller-supplied strides can wrap)
+    if (dstRowSt < dstW * elem || dstPlaneSt / dstH < dstRowSt || (nFrames > 1 && dstFrameSt / planes < dstPlaneSt))
+        return IQO_HIP_EINVAL;
+    // the kernel addresses one float frame with 32-bit byte offsets
+    const size_t kLim = size_t(1) << 31;
+    if (dstRowSt >= kLim || dstPlaneSt >= kLim || (planes - 1) * dstPlaneSt + (dstH - 1) * dstRowSt + dstW * elem >= kLim)
+        return IQO_HIP_EINVAL;
+    if (!yuv_src_ok(p, 1, srcSt))
+        return IQO_HIP_EINVAL;
+    if (workspaceBytes < iqo_hip_planes_norm_workspace_bytes(dstW, dstH, srcPlanes, nFrames))
+        return IQO_HIP_EINVAL;
+    if (nFrames == 0)
+        return IQO_HIP_OK;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const PlanesNormWs w = planes_norm_ws(dstW, dstH, P);
+    uint8_t *ws = yuv_rgb_ws_base(workspace);
+    // First pass.  The contiguous [F, P, H, W] tensor with every plane referenced is one batch of
+    // nFrames * srcPlanes frames a plane stride apart, the workspace's planes likewise; otherwise one
+    // batch per referenced plane (an unused plane is not resized).
+    if (P == 1) {
+        const int rc = run_band(h, nFrames, 0, dstH, 0, srcSt, srcFrameSt, dSrc, w.st, w.frame, ws, s);
+        if (rc)
+            return rc;
+    } else if (used == (1u << srcPlanes) - 1u && srcFrameSt / P == srcPlaneSt && srcFrameSt % P == 0) {
+        const int rc = run_band(h, nFrames * P, 0, dstH, 0, srcSt, srcPlaneSt, dSrc, w.st, w.plane, ws, s);
+        if (rc)
+            return rc;
+    } else {
+        for (size_t c = 0; c < P; ++c) {
+            if (!(used >> c & 1u))
+                continue;
+            const int rc = run_band(h, nFrames, 0, dstH, 0, srcSt, srcFrameSt, dSrc + c * srcPlaneSt, w.st, w.frame,
+                                    ws + c * w.plane, s);
+            if (rc)
+                return rc;
+        }
+    }
+
+    // Second pass: planes_norm_kernel over the workspace planes.
+    DeviceGuard guard(h->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    iqo_amd::NormDev nd{};
+    nd.dtype = norm->dtype;
+    nd.planes = norm->planes;
+    nd.planeSt = static_cast<int>(dstPlaneSt);
+    for (int i = 0; i < norm->planes; ++i) {
+        nd.order[i] = norm->order[i];
+        nd.scale[i] = norm->scale[i];
+        nd.bias[i] = norm->bias[i];
+    }
+    iqo_amd::PlanesNormDev d{};
+    d.dstW = p.dstW;
+    d.dstH = p.dstH;
+    d.srcSt = static_cast<int>(w.st);
+    d.srcPlaneSt = static_cast<int64_t>(w.plane);
+    d.srcFrameSt = static_cast<int64_t>(w.frame);
+    d.dstSt = static_cast<int>(dstRowSt);
+    d.dstFrameSt = static_cast<int64_t>(dstFrameSt);
+    // frames per launch: the kernel counts (frame, row, pixel group) items in 31 bits, groups of 4 at the least
+    const size_t perFrame = dstH * ((dstW + 3) / 4);
+    const size_t chunk = std::max<size_t>(1, ((size_t(1) << 31) - 1) / perFrame);
+    for (size_t f0 = 0; f0 < nFrames; f0 += chunk) {
+        d.frames = static_cast<int>(std::min(chunk, nFrames - f0));
+        d.src = ws + f0 * w.frame;
+        d.dst = static_cast<uint8_t *>(dDst) + f0 * dstFrameSt;
+        const hipError_t e = iqo_amd::launch_planes_norm(d, nd, s);
+        if (e == hipErrorInvalidValue)
+            return IQO_HIP_EINVAL;
+        if (e != hipSuccess)
+            return IQO_HIP_EHIP;
+    }
+    return IQO_HIP_OK;
+}
+
 // ---- Packed RGB(A) straight to NV12 / I420, the opposite direction.  Two passes on the stream: the
 // packed plan's own resize, unchanged, into the caller's workspace, then rgb_yuv_kernel
 // (kernels_color.hip) from the workspace to the planes.  Every check runs on the host before the first

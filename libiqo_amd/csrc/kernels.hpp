@@ -127,6 +127,25 @@ struct RgbYuvDev {
 };
 hipError_t launch_rgb_yuv(const RgbYuvDev &d, int channels, bool interleavedUV, hipStream_t s);
 
+// --- resized U8 planes -> normalised planar floats (kernels_norm.hip): the second pass of
+// iqo_hip_resize_planes_norm_device.  Reads up to 4 resized planes (dstW x dstH each) per frame from a
+// workspace and writes NormDev's planar floats, NormDev::order[p] being the workspace plane of output
+// plane p: out = cvt(fl32(fl32((float)u8 * scale[p]) + bias[p])).
+// Workspace: src, srcSt, srcPlaneSt and srcFrameSt are multiples of 8 with srcSt >= 8 ceil(dstW / 8) --
+// a thread loads its 8 (fp32: 4) bytes of a plane whole; what it loads past dstW is never used.  No
+// alignment of dst beyond the element size.
+struct PlanesNormDev {
+    int dstW, dstH;
+    const uint8_t *src;                // plane 0 of frame 0 of the workspace
+    int srcSt;                         // row stride, bytes
+    int64_t srcPlaneSt, srcFrameSt;
+    uint8_t *dst;
+    int dstSt;                         // row stride, bytes (< 2^31; one frame's extent < 2^31)
+    int64_t dstFrameSt;
+    int frames;                        // frames x dstH x ceil(dstW / 4) < 2^31
+};
+hipError_t launch_planes_norm(const PlanesNormDev &d, const NormDev &n, hipStream_t s);
+
 // --- general-ratio wave walker: every wave walks a 256-column strip of one band of rows through
 // a private LDS ring of source rows widened to u16 (plan.hpp WalkTables; 4-byte aligned sources).
 struct WalkDev {
