@@ -527,6 +527,53 @@ int iqo_host_kernel_for_layout(int method, unsigned degree, size_t srcW, size_t 
 int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,
                                size_t dstH, size_t pxScale);
 
+/* The template instantiation a planar (1-channel) call runs, for the families that have more than one:
+ * IQO_KERNEL_TILE, _WALK, _LANCZOS_UP2, _LANCZOS_D32, _AREA_D32, _LANCZOS_U23, _LINEAR_U23, _LANCZOS_D31,
+ * _RYX and _RYG.  The fields are the kernels' template parameters by name; one a kernel does not have
+ * is 0.  For the other families (the integer-ratio streamers, the general and the packed kernels) only
+ * `family` is set.
+ *   tile_kernel          NP, LZ                            (LZ 1: Lanczos, 0: Area / Linear)
+ *   walk_kernel          NP, VY, NV, LZ
+ *   lanczos_up2_kernel   NT, F
+ *   lanczos_d32_kernel   PD, VARIANT                       (VARIANT 0: Lanczos-3 taps, 1: Lanczos-2 taps)
+ *   lanczos_d31_kernel   PD, VARIANT
+ *   lanczos_u23_kernel, linear_u23_kernel, area_d32_kernel   PD
+ *   ryx_kernel           LZ, P, Q, T, NP, PD, ADJ, CPT, UC
+ *   ryg_kernel           LZ, T, NP, PD, CPT, NL            (sub 0)
+ *   ryu_kernel           T, NP, PD, CPT, RUN, KM           (sub IQO_INSTANCE_SUB_RYU: IQO_KERNEL_RYG's upscale
+ *                                                           rows walked by window position) */
+enum { IQO_INSTANCE_SUB_NONE = 0, IQO_INSTANCE_SUB_RYU = 1 };
+typedef struct iqo_hip_instance {
+    int family;             /* IQO_KERNEL_* */
+    int sub;                /* IQO_INSTANCE_SUB_* */
+    int LZ, P, Q, T, NP, PD, ADJ, CPT, UC, NL, RUN, KM, VY, NV, NT, F, VARIANT;
+} iqo_hip_instance;
+
+/* The instantiation a full-frame call of `plan` runs with the plan's CURRENT options, when the source /
+ * destination base and strides are multiples of srcAlign / dstAlign bytes (powers of two, 1..16) and of
+ * nothing larger -- exactly the entry of the family's table that the launch function would run (one
+ * lookup serves both).  No launch, no device access.  IQO_HIP_EINVAL for a null plan or descriptor or
+ * another alignment value, IQO_HIP_EUNSUP for a packed plan, and IQO_HIP_EINVAL where the resize call
+ * itself would be rejected: a forced "ratio_prefetch" depth the kernel does not instantiate. */
+int iqo_hip_plan_instance(const iqo_hip_plan *plan, size_t srcAlign, size_t dstAlign, iqo_hip_instance *desc);
+
+/* Host-only twin (no GPU needed): the same for a shape and nOptions options, applied in order through
+ * iqo_hip_plan_set_option itself -- so an unknown key, an out-of-range value or (without IQO_HIP_TUNING=1)
+ * a tuning key is IQO_HIP_EINVAL here too, as is a shape the plan constructors reject. */
+typedef struct iqo_hip_option {
+    const char *key;
+    long value;
+} iqo_hip_option;
+int iqo_host_instance_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                          size_t pxScale, const iqo_hip_option *options, size_t nOptions, size_t srcAlign,
+                          size_t dstAlign, iqo_hip_instance *desc);
+
+/* Host-only: every instantiation of a family, in table order (IQO_KERNEL_RYG: ryg_kernel's, then
+ * ryu_kernel's).  The count is 0 for a family with a single kernel and for an unknown family;
+ * iqo_host_instance_at is IQO_HIP_EINVAL for a null descriptor or an index outside 0 .. count - 1. */
+int iqo_host_instance_count(int family);
+int iqo_host_instance_at(int family, int index, iqo_hip_instance *desc);
+
 /* Fused I420 instantiations: the kernel iqo_hip_resize_yuv420_device runs when it resizes the three
  * planes in one launch.  IQO_YUV420_NONE: plane by plane. */
 enum {

@@ -13,7 +13,7 @@ import ctypes
 import os
 
 __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420Resizer", "Nv12Resizer", "available",
-           "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_yuv420_fused", "host_band_src_rows", "copy_frames", "ipc_export", "ipc_open",
+           "lib", "host_tables", "host_kernel_for", "host_packed_kernel_for", "host_yuv420_fused", "host_band_src_rows", "host_instance_for", "host_instances", "Instance", "copy_frames", "ipc_export", "ipc_open",
            "ipc_close", "KERNELS", "YUV420_FUSED", "COPY_PATHS", "LIB_PATH", "Norm", "OUT_F32", "OUT_F16", "OUT_BF16",
            "CS_BT601_LIMITED", "CS_BT601_FULL", "CS_BT709_LIMITED", "CS_BT709_FULL", "COLOR_STANDARDS", "RGB_ORDERS",
            "host_yuv_to_rgb", "yuv_rgb_workspace_bytes", "CHROMA_REPLICATE", "CHROMA_FULL", "CHROMA_MODES",
@@ -44,6 +44,27 @@ class PlanDesc(ctypes.Structure):
                 ("dstW", _c_sz), ("dstH", _c_sz), ("tapsX", ctypes.c_int), ("tapsY", ctypes.c_int),
                 ("phasesX", ctypes.c_int), ("phasesY", ctypes.c_int), ("kernel", ctypes.c_int),
                 ("bandsPerFrame", ctypes.c_int), ("tileRows", ctypes.c_int)]
+
+
+INSTANCE_PARAMS = ("LZ", "P", "Q", "T", "NP", "PD", "ADJ", "CPT", "UC", "NL", "RUN", "KM", "VY", "NV", "NT", "F", "VARIANT")
+
+
+class Instance(ctypes.Structure):
+    """iqo_hip_instance: kernel family, sub-kernel tag and the template parameters by name (0: not a parameter
+    of that kernel)."""
+    _fields_ = [("family", ctypes.c_int), ("sub", ctypes.c_int)] + [(k, ctypes.c_int) for k in INSTANCE_PARAMS]
+
+
+class _Option(ctypes.Structure):
+    _fields_ = [("key", ctypes.c_char_p), ("value", ctypes.c_long)]
+
+
+def _instance_dict(d):
+    """{"kernel": the kernel's name (ryg / ryu within the ryg family), then its non-zero parameters}."""
+    name = "ryu" if d.family == 13 and d.sub == 1 else KERNELS.get(d.family, d.family)
+    out = {"kernel": name}
+    out.update({k: getattr(d, k) for k in INSTANCE_PARAMS if getattr(d, k)})
+    return out
 
 
 class Norm(ctypes.Structure):
@@ -116,6 +137,11 @@ def lib():
                                   ctypes.POINTER(ctypes.c_int32), _c_sz]
     L.iqo_host_kernel_for.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz]
     L.iqo_host_kernel_for_layout.argtypes = L.iqo_host_kernel_for.argtypes + [_c_sz, _c_sz]
+    L.iqo_hip_plan_instance.argtypes = [_vp, _c_sz, _c_sz, ctypes.POINTER(Instance)]
+    L.iqo_host_instance_for.argtypes = L.iqo_host_kernel_for.argtypes + [ctypes.POINTER(_Option), _c_sz, _c_sz, _c_sz,
+                                                                         ctypes.POINTER(Instance)]
+    L.iqo_host_instance_count.argtypes = [ctypes.c_int]
+    L.iqo_host_instance_at.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Instance)]
     L.iqo_host_band_src_rows.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz,
                                          ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]
     L.iqo_hip_plan_yuv420.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.c_int, pp]
@@ -242,6 +268,28 @@ def host_kernel_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1, src_align
     if k < 0:
         raise IqoError("invalid plan request")
     return KERNELS[k]
+
+
+def host_instance_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1, options=(), src_align=16, dst_align=16):
+    """The template instantiation a full-frame call of this shape runs after `options` ((key, value) pairs,
+    applied as set_option applies them) with the given alignments, as {"kernel": name, parameter: value, ...}
+    with the parameters that are not 0 -- host only, no GPU."""
+    opts = (_Option * max(1, len(options)))(*[_Option(k.encode(), int(v)) for k, v in options])
+    d = Instance()
+    _check(lib().iqo_host_instance_for(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale, opts, len(options),
+                                       src_align, dst_align, ctypes.byref(d)), "host_instance_for")
+    return _instance_dict(d)
+
+
+def host_instances(kernel):
+    """Every instantiation of a kernel family (a KERNELS name), in the library's table order -- host only."""
+    family = {v: k for k, v in KERNELS.items()}[kernel]
+    out = []
+    for i in range(lib().iqo_host_instance_count(family)):
+        d = Instance()
+        _check(lib().iqo_host_instance_at(family, i, ctypes.byref(d)), "host_instances")
+        out.append(_instance_dict(d))
+    return out
 
 
 def host_packed_kernel_for(method, degree, channels, srcW, srcH, dstW, dstH, pxScale=1):
@@ -456,6 +504,13 @@ class _Resizer:
     def set_option(self, key, value):
         _check(lib().iqo_hip_plan_set_option(self._plan, key.encode(), int(value)), "set_option")
 
+    def instance(self, src_align=16, dst_align=16):
+        """The template instantiation a full-frame call runs with the plan's current options (host_instance_for's
+        form)."""
+        d = Instance()
+        _check(lib().iqo_hip_plan_instance(self._plan, src_align, dst_align, ctypes.byref(d)), "instance")
+        return _instance_dict(d)
+
     def prepare(self):
         """Upload the device tables now (before graph capture / async-only use)."""
         _check(lib().iqo_hip_plan_prepare(self._plan), "prepare")
@@ -463,10 +518,13 @@ class _Resizer:
     def describe(self):
         d = PlanDesc()
         _check(lib().iqo_hip_plan_query(self._plan, ctypes.byref(d)), "query")
+        inst = Instance()  # (packed plans, and a forced prefetch depth the kernel has not: no instance)
+        rc = lib().iqo_hip_plan_instance(self._plan, 16, 16, ctypes.byref(inst))
         return {"method": d.method, "device": d.device, "tapsX": d.tapsX, "tapsY": d.tapsY,
                 "phasesX": d.phasesX, "phasesY": d.phasesY, "kernel": KERNELS.get(d.kernel, d.kernel),
                 "bands": d.bandsPerFrame, "tile_rows": d.tileRows,
-                "channels": int(lib().iqo_hip_plan_channels(self._plan))}
+                "channels": int(lib().iqo_hip_plan_channels(self._plan)),
+                "instance": _instance_dict(inst) if rc == 0 else None}
 
     # -- torch convenience: src [F, srcH, srcW] (or [srcH, srcW]) uint8 on the plan's device;
     #    packed plans: [F, srcH, srcW, C] (or [srcH, srcW, C])

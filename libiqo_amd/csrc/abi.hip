@@ -1384,6 +1384,8 @@ struct Layout {
     uintptr_t src, dst;
 };
 constexpr Layout kAlignedLayout{0, 0};
+// an alignment the iqo_host_* / instance queries take for a layout: a power of two, 1 .. 16
+bool valid_align(size_t a) { return a >= 1 && a <= 16 && !(a & (a - 1)); }
 
 Layout layout_of(const void *src, size_t srcSt, size_t srcFrameSt, const void *dst, size_t dstSt, size_t dstFrameSt)
 {
@@ -1484,6 +1486,97 @@ int kernel_for_layout(const iqo_hip_plan *h, const void *src, size_t srcSt, size
     return select_kernel(h, layout_of(src, srcSt, srcFrameSt, dst, dstSt, dstFrameSt));
 }
 
+iqo_hip_instance to_desc(const iqo_amd::Instance &k)
+{
+    iqo_hip_instance d{};
+    d.family = k.family;
+    d.sub = k.sub;
+    d.LZ = k.LZ;
+    d.P = k.P;
+    d.Q = k.Q;
+    d.T = k.T;
+    d.NP = k.NP;
+    d.PD = k.PD;
+    d.ADJ = k.ADJ;
+    d.CPT = k.CPT;
+    d.UC = k.UC;
+    d.NL = k.NL;
+    d.RUN = k.RUN;
+    d.KM = k.KM;
+    d.VY = k.VY;
+    d.NV = k.NV;
+    d.NT = k.NT;
+    d.F = k.F;
+    d.VARIANT = k.VARIANT;
+    return d;
+}
+
+// The exact-ratio kernels instantiate a few prefetch depths each; any other forced depth is an
+// error, not a silent fall-back to the default kernel.
+bool ratio_prefetch_ok(const iqo_hip_plan *h, int kernel)
+{
+    const int pd = h->ratioPrefetch;
+    if (pd <= 0)
+        return true;
+    if (kernel == IQO_KERNEL_LANCZOS_D32)
+        return h->dt.variant == 0 ? (pd == 1 || pd == 2 || pd == 4) : (pd == 1 || pd == 3);
+    if (kernel == IQO_KERNEL_LANCZOS_D31)
+        return h->t31.variant == 0 ? (pd == 1 || pd == 5) : (pd == 1 || pd == 2 || pd == 4);
+    if (kernel == IQO_KERNEL_LANCZOS_U23 || kernel == IQO_KERNEL_LINEAR_U23)
+        return pd == 1 || pd == 2;
+    if (kernel == IQO_KERNEL_AREA_D32)
+        return pd == 2 || pd == 4 || pd == 8;
+    return true;
+}
+
+// The instantiation a full-frame call with this layout runs (iqo_hip.h iqo_hip_instance): the family
+// of select_kernel, then the family's own lookup (kernels.hpp) on the *Dev the launch would get.  Host
+// data only, so it also serves a plan without device tables (iqo_host_instance_for): there the device
+// pointers of the *Dev are null, and the general rows' two decisions that launch_ryg reads off pointers
+// come from what ryg_dev itself decided -- rows by window position exactly when it set posRec
+// (nl == 1 && hasRyu && useRyu), the run mode exactly when it set d.run.
+int plan_instance(const iqo_hip_plan *h, Layout l, iqo_hip_instance *out)
+{
+    static_assert(iqo_amd::kFamTile == IQO_KERNEL_TILE && iqo_amd::kFamWalk == IQO_KERNEL_WALK &&
+                      iqo_amd::kFamUp2 == IQO_KERNEL_LANCZOS_UP2 && iqo_amd::kFamD32 == IQO_KERNEL_LANCZOS_D32 &&
+                      iqo_amd::kFamA32 == IQO_KERNEL_AREA_D32 && iqo_amd::kFamU23 == IQO_KERNEL_LANCZOS_U23 &&
+                      iqo_amd::kFamL23 == IQO_KERNEL_LINEAR_U23 && iqo_amd::kFamD31 == IQO_KERNEL_LANCZOS_D31 &&
+                      iqo_amd::kFamRyx == IQO_KERNEL_RYX && iqo_amd::kFamRyg == IQO_KERNEL_RYG &&
+                      iqo_amd::kSubRyu == IQO_INSTANCE_SUB_RYU,
+                  "kernels.hpp kFam* are iqo_hip.h IQO_KERNEL_*");
+    if (h->channels > 1)
+        return IQO_HIP_EUNSUP;
+    const int kernel = select_kernel(h, l);
+    if (!ratio_prefetch_ok(h, kernel))
+        return IQO_HIP_EINVAL;
+    const iqo_amd::Instance *k = nullptr;
+    switch (kernel) {
+    case IQO_KERNEL_TILE: k = iqo_amd::tile_instance(tile_dev(h)); break;
+    case IQO_KERNEL_WALK: k = iqo_amd::walk_instance(walk_dev(h)); break;
+    case IQO_KERNEL_LANCZOS_UP2: k = iqo_amd::up2_instance(up2_dev(h)); break;
+    case IQO_KERNEL_LANCZOS_D32: k = iqo_amd::d32_instance(d32_dev(h)); break;
+    case IQO_KERNEL_LANCZOS_D31: k = iqo_amd::d31_instance(d31_dev(h)); break;
+    case IQO_KERNEL_LANCZOS_U23: k = iqo_amd::u23_instance(u23_dev(h)); break;
+    case IQO_KERNEL_LINEAR_U23: k = iqo_amd::l23_instance(l23_dev(h)); break;
+    case IQO_KERNEL_AREA_D32: k = iqo_amd::a32_instance(a32_dev(h)); break;
+    case IQO_KERNEL_RYX: k = iqo_amd::ryx_instance(ryx_dev(h)); break;
+    case IQO_KERNEL_RYG: {
+        const iqo_amd::RygDev d = ryg_dev(h);
+        k = iqo_amd::ryg_instance(d, d.nl == 1 && h->hasRyu && h->useRyu, d.run);
+        break;
+    }
+    default: {  // a family with one kernel
+        *out = iqo_hip_instance{};
+        out->family = kernel;
+        return IQO_HIP_OK;
+    }
+    }
+    if (!k)
+        return IQO_HIP_EINVAL;  // (the launch function rejects the call the same way)
+    *out = to_desc(*k);
+    return IQO_HIP_OK;
+}
+
 iqo_amd::Io make_io(size_t frames, const uint8_t *src, size_t srcSt, size_t srcFrameSt, size_t srcRow0, int srcRowEnd,
                     uint8_t *dst, size_t dstSt, size_t dstFrameSt, int dstRow0)
 {
@@ -1542,22 +1635,8 @@ int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t src
         const size_t n = (nFrames + chunk - 1) / chunk;  // equal launches, not one straggler
         chunk = (nFrames + n - 1) / n;
     }
-    // the exact-ratio kernels instantiate a few prefetch depths each; any other forced depth is an
-    // error, not a silent fall-back to the default kernel
-    if (h->ratioPrefetch > 0) {
-        const int pd = h->ratioPrefetch;
-        bool ok = true;
-        if (kernel == IQO_KERNEL_LANCZOS_D32)
-            ok = h->dt.variant == 0 ? (pd == 1 || pd == 2 || pd == 4) : (pd == 1 || pd == 3);
-        else if (kernel == IQO_KERNEL_LANCZOS_D31)
-            ok = h->t31.variant == 0 ? (pd == 1 || pd == 5) : (pd == 1 || pd == 2 || pd == 4);
-        else if (kernel == IQO_KERNEL_LANCZOS_U23 || kernel == IQO_KERNEL_LINEAR_U23)
-            ok = pd == 1 || pd == 2;
-        else if (kernel == IQO_KERNEL_AREA_D32)
-            ok = pd == 2 || pd == 4 || pd == 8;
-        if (!ok)
-            return IQO_HIP_EINVAL;
-    }
+    if (!ratio_prefetch_ok(h, kernel))
+        return IQO_HIP_EINVAL;
     for (size_t f0 = 0; f0 < nFrames; f0 += chunk) {
         const iqo_amd::Io io = make_io(std::min(chunk, nFrames - f0), src + f0 * srcFrameSt, srcSt, srcFrameSt, srcRow0,
                                        s1, dst + f0 * dstFrameSt, dstSt, dstFrameSt, rb);
@@ -1748,6 +1827,13 @@ int iqo_hip_plan_query(const iqo_hip_plan *h, iqo_hip_plan_desc *d)
     d->bandsPerFrame = h->bands;
     d->tileRows = h->channels > 1 ? (h->pk.ok ? h->pk.TH : 0) : h->tt.ok ? h->tt.TH : 0;
     return IQO_HIP_OK;
+}
+
+int iqo_hip_plan_instance(const iqo_hip_plan *h, size_t srcAlign, size_t dstAlign, iqo_hip_instance *desc)
+{
+    if (!h || !desc || !valid_align(srcAlign) || !valid_align(dstAlign))
+        return IQO_HIP_EINVAL;
+    return plan_instance(h, Layout{srcAlign, dstAlign}, desc);
 }
 
 int iqo_hip_plan_prepare(iqo_hip_plan *h)
@@ -3249,8 +3335,7 @@ int iqo_host_band_src_rows(int method, unsigned degree, size_t srcW, size_t srcH
 int iqo_host_kernel_for_layout(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale,
                                size_t srcAlign, size_t dstAlign)
 {
-    auto valid = [](size_t a) { return a >= 1 && a <= 16 && !(a & (a - 1)); };
-    if (method < 0 || method > 2 || !valid(srcAlign) || !valid(dstAlign))
+    if (method < 0 || method > 2 || !valid_align(srcAlign) || !valid_align(dstAlign))
         return IQO_HIP_EINVAL;
     const Layout l{srcAlign, dstAlign};  // multiples of the alignment and of nothing larger
     iqo_hip_plan h;  // host half of a plan only: no device memory
@@ -3267,6 +3352,36 @@ int iqo_host_kernel_for_layout(int method, unsigned degree, size_t srcW, size_t 
 int iqo_host_kernel_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale)
 {
     return iqo_host_kernel_for_layout(method, degree, srcW, srcH, dstW, dstH, pxScale, 16, 16);
+}
+
+int iqo_host_instance_for(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale,
+                          const iqo_hip_option *options, size_t nOptions, size_t srcAlign, size_t dstAlign,
+                          iqo_hip_instance *desc)
+{
+    if (method < 0 || method > 2 || !desc || !valid_align(srcAlign) || !valid_align(dstAlign) || (nOptions && !options))
+        return IQO_HIP_EINVAL;
+    iqo_hip_plan h;  // host half of a plan only: no device memory
+    std::string err;
+    if (!iqo_amd::build_plan(static_cast<iqo_amd::Method>(method), degree, srcW, srcH, dstW, dstH, pxScale, &h.p, &err))
+        return IQO_HIP_EINVAL;
+    build_host_tables(&h);
+    for (size_t i = 0; i < nOptions; ++i) {
+        const int rc = iqo_hip_plan_set_option(&h, options[i].key, options[i].value);
+        if (rc)
+            return rc;
+    }
+    return plan_instance(&h, Layout{srcAlign, dstAlign}, desc);
+}
+
+int iqo_host_instance_count(int family) { return iqo_amd::instances(family).count; }
+
+int iqo_host_instance_at(int family, int index, iqo_hip_instance *desc)
+{
+    const iqo_amd::InstanceList l = iqo_amd::instances(family);
+    if (!desc || index < 0 || index >= l.count)
+        return IQO_HIP_EINVAL;
+    *desc = to_desc(l.first[index]);
+    return IQO_HIP_OK;
 }
 
 int iqo_host_packed_kernel_for(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,

@@ -2491,6 +2491,78 @@ hipError_t launch_general(const GeneralDev &g, const Io &io, int rowBegin, int r
     return hipGetLastError();
 }
 
+// tile_kernel<NP, LZ>: the column pair counts of plan.hpp kTileNP, Lanczos and Area / Linear
+static InstanceList tile_instances()
+{
+#define IQO_TILE(NP_) mk(NP_, true, reinterpret_cast<const void *>(tile_kernel<NP_, true>)),        \
+                      mk(NP_, false, reinterpret_cast<const void *>(tile_kernel<NP_, false>))
+    static const auto mk = [](int np, bool lz, const void *kern) {
+        Instance i{};
+        i.family = kFamTile;
+        i.NP = np;
+        i.LZ = lz;
+        i.kern = kern;
+        return i;
+    };
+    static const Instance kInst[] = {IQO_TILE(1), IQO_TILE(2), IQO_TILE(3), IQO_TILE(4),  IQO_TILE(5), IQO_TILE(6),
+                                     IQO_TILE(7), IQO_TILE(8), IQO_TILE(10), IQO_TILE(12), IQO_TILE(16)};
+#undef IQO_TILE
+    return {kInst, static_cast<int>(sizeof kInst / sizeof kInst[0])};
+}
+
+const Instance *tile_instance(const TileDev &t)
+{
+    const InstanceList l = tile_instances();
+    for (int i = 0; i < l.count; ++i)
+        if (l.first[i].NP == t.NP && (l.first[i].LZ != 0) == t.lanczos)
+            return l.first + i;
+    return nullptr;
+}
+
+// walk_kernel<NP, VY, NV, LZ>: VY = 2 NP or 2 NP - 2 row taps (NP 1: 2 only), NV 1 or 2 units per lane
+static InstanceList walk_instances()
+{
+#define IQO_WALK_NV(NP_, VY_, NV_) mk(NP_, VY_, NV_, true, reinterpret_cast<const void *>(walk_kernel<NP_, VY_, NV_, true>)), \
+                                   mk(NP_, VY_, NV_, false, reinterpret_cast<const void *>(walk_kernel<NP_, VY_, NV_, false>))
+#define IQO_WALK_VY(NP_, VY_) IQO_WALK_NV(NP_, VY_, 1), IQO_WALK_NV(NP_, VY_, 2)
+#define IQO_WALK(NP_) IQO_WALK_VY(NP_, 2 * NP_), IQO_WALK_VY(NP_, 2 * NP_ - 2)
+    static const auto mk = [](int np, int vy, int nv, bool lz, const void *kern) {
+        Instance i{};
+        i.family = kFamWalk;
+        i.NP = np;
+        i.VY = vy;
+        i.NV = nv;
+        i.LZ = lz;
+        i.kern = kern;
+        return i;
+    };
+    static const Instance kInst[] = {IQO_WALK_VY(1, 2), IQO_WALK(2), IQO_WALK(3), IQO_WALK(4),
+                                     IQO_WALK(5),       IQO_WALK(6), IQO_WALK(7), IQO_WALK(8)};
+#undef IQO_WALK
+#undef IQO_WALK_VY
+#undef IQO_WALK_NV
+    return {kInst, static_cast<int>(sizeof kInst / sizeof kInst[0])};
+}
+
+const Instance *walk_instance(const WalkDev &w)
+{
+    const TileDev &t = w.t;
+    const int e = 2 * t.NP - t.nYp;
+    if ((e != 0 && e != 2) || t.nYp < 2 || (w.NV != 1 && w.NV != 2))
+        return nullptr;
+    const InstanceList l = walk_instances();
+    for (int i = 0; i < l.count; ++i)
+        if (l.first[i].NP == t.NP && l.first[i].VY == t.nYp && l.first[i].NV == w.NV && (l.first[i].LZ != 0) == t.lanczos)
+            return l.first + i;
+    return nullptr;
+}
+
+// kernels.hpp instances(): the tile and walker tables live in this translation unit
+InstanceList tile_walk_instances(int family)
+{
+    return family == kFamTile ? tile_instances() : family == kFamWalk ? walk_instances() : InstanceList{nullptr, 0};
+}
+
 hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
@@ -2510,28 +2582,10 @@ hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd,
     const size_t lds = static_cast<size_t>(t.TH) * (static_cast<size_t>(t.pitchDw) * 4 + 16 + static_cast<size_t>(t.nYp) * 8) +
                        4u * static_cast<size_t>(t.CT) + static_cast<size_t>(t.srcRows) * t.spitch;
     dim3 grid(static_cast<unsigned>(nTiles));
-#define IQO_TILE(NP_)                                                                                \
-    case NP_:                                                                                        \
-        kern = t.lanczos ? reinterpret_cast<const void *>(tile_kernel<NP_, true>)                    \
-                         : reinterpret_cast<const void *>(tile_kernel<NP_, false>);                  \
-        break;
-    const void *kern = nullptr;
-    switch (t.NP) {
-        IQO_TILE(1)
-        IQO_TILE(2)
-        IQO_TILE(3)
-        IQO_TILE(4)
-        IQO_TILE(5)
-        IQO_TILE(6)
-        IQO_TILE(7)
-        IQO_TILE(8)
-        IQO_TILE(10)
-        IQO_TILE(12)
-        IQO_TILE(16)
-    default:
+    const Instance *inst = tile_instance(t);
+    if (!inst)
         return hipErrorInvalidValue;
-    }
-#undef IQO_TILE
+    const void *kern = inst->kern;
     void *args[] = {&a};
     return hipLaunchKernel(kern, grid, dim3(256), args, lds, s);
 }
@@ -2553,45 +2607,10 @@ hipError_t launch_walk(const WalkDev &w, const Io &io, int rowBegin, int rowEnd,
     const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + t.dstW;  // stores are relative to dstRow0
     if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31) || io.srcSt >= (int64_t(1) << 24))
         return hipErrorInvalidValue;
-    const void *kern = nullptr;
-    // (NP, VY = 2NP or 2NP - 2, NV) instantiations
-    const int e = 2 * t.NP - t.nYp;
-    if ((e != 0 && e != 2) || t.nYp < 2 || (w.NV != 1 && w.NV != 2))
+    const Instance *inst = walk_instance(w);
+    if (!inst)
         return hipErrorInvalidValue;
-#define IQO_WALK_NV(NP_, VY_, NV_)                                                                   \
-    kern = t.lanczos ? reinterpret_cast<const void *>(walk_kernel<NP_, VY_, NV_, true>)              \
-                     : reinterpret_cast<const void *>(walk_kernel<NP_, VY_, NV_, false>);
-#define IQO_WALK_VY(NP_, VY_)                                                                        \
-    if (w.NV == 1) {                                                                                 \
-        IQO_WALK_NV(NP_, VY_, 1)                                                                     \
-    } else {                                                                                         \
-        IQO_WALK_NV(NP_, VY_, 2)                                                                     \
-    }
-#define IQO_WALK(NP_)                                                                                \
-    case NP_:                                                                                        \
-        if (e == 0) {                                                                                \
-            IQO_WALK_VY(NP_, 2 * NP_)                                                                \
-        } else {                                                                                     \
-            IQO_WALK_VY(NP_, 2 * NP_ - 2)                                                            \
-        }                                                                                            \
-        break;
-    switch (t.NP) {
-    case 1:
-        IQO_WALK_VY(1, 2)
-        break;
-        IQO_WALK(2)
-        IQO_WALK(3)
-        IQO_WALK(4)
-        IQO_WALK(5)
-        IQO_WALK(6)
-        IQO_WALK(7)
-        IQO_WALK(8)
-    default:
-        return hipErrorInvalidValue;
-    }
-#undef IQO_WALK
-#undef IQO_WALK_VY
-#undef IQO_WALK_NV
+    const void *kern = inst->kern;
     const int lds = 4 * w.waveBytes;
     // bands per frame: about 2.5 rounds of resident waves (more waves than slots hide the tail and
     // the latency of each wave's serial walk; MI355X G1/G2/G3 sweeps), bands of >= 16 rows

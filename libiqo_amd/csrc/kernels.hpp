@@ -22,6 +22,28 @@ struct Io {
     int frames;
 };
 
+// --- the template instantiation a launch runs, by name.  Every family with more than one
+// instantiation keeps ONE table of them (kernels.hip: tile, walk; kernels_ratio.hip: the ratio
+// kernels) and one lookup over it, `<family>_instance(dev)`: the launch function runs the entry the
+// lookup returns, and the C ABI reports that entry (iqo_hip.h iqo_hip_instance) -- a pure host
+// function of the *Dev, no device query and no launch.  Parameters a family does not have are 0.
+constexpr int kFamTile = 4, kFamWalk = 5, kFamUp2 = 6, kFamD32 = 7, kFamA32 = 8, kFamU23 = 9, kFamL23 = 10,
+              kFamD31 = 11, kFamRyx = 12, kFamRyg = 13;  // iqo_hip.h IQO_KERNEL_* (abi.hip asserts it)
+constexpr int kSubRyu = 1;       // Instance::sub within kFamRyg: ryu_kernel (0: ryg_kernel)
+struct Instance {
+    int family, sub;
+    int LZ, P, Q, T, NP, PD, ADJ, CPT, UC, NL, RUN, KM, VY, NV, NT, F, VARIANT;
+    const void *kern;
+};
+struct InstanceList {
+    const Instance *first;
+    int count;
+};
+// Every instantiation of a family, in table order (ryg: ryg_kernel's, then ryu_kernel's); {nullptr, 0}
+// for a family with a single kernel.
+InstanceList instances(int family);
+InstanceList tile_walk_instances(int family);  // (its tile / walk part, kernels.hip; the rest and the whole: kernels_ratio.hip)
+
 // --- general kernel: one workgroup per output row; LDS work row built chunk by chunk.
 struct GeneralDev {
     int method, srcW, srcH, dstW, nX, nY;
@@ -47,6 +69,7 @@ struct TileDev {
     const int4 *spans;           // {lo8, groups, any border column, 0} per column tile
 };
 hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s);
+const Instance *tile_instance(const TileDev &t);      // null: no instantiation (launch_tile rejects it)
 
 
 // --- packed (interleaved) pixels, C = 2 .. 4 bytes per pixel, every channel resized on its own
@@ -163,6 +186,7 @@ struct WalkDev {
 // strips stripLo + i * stripStride (i < strips; strips < 0: all of them)
 hipError_t launch_walk(const WalkDev &w, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s,
                        int stripLo = 0, int strips = -1, int stripStride = 1);
+const Instance *walk_instance(const WalkDev &w);
 
 // --- exact 2x Lanczos-2/3 upscale, main rows x middle columns (plan.hpp Up2Tables).
 struct Up2Dev {
@@ -181,6 +205,7 @@ struct Up2Dev {
     int yS[2][16];
 };
 hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *up2_instance(const Up2Dev &u);
 
 // Exact 3:2 Lanczos-3 downscale (plan.hpp D32Tables): main rows x all columns.
 struct D32Dev {
@@ -197,6 +222,7 @@ struct D32Dev {
     int yS[2][8];
 };
 hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *d32_instance(const D32Dev &d);
 
 // Exact 3:1 Lanczos-2/3 downscale (plan.hpp D31Tables): every row and column.
 struct D31Dev {
@@ -213,6 +239,7 @@ struct D31Dev {
     int yS[2][8];
 };
 hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *d31_instance(const D31Dev &d);
 
 // Exact vertical ratio, tabled columns (plan.hpp RyxTables): every row and column.
 constexpr int kRyxPadK = 24;     // work-row padding (u16 entries) left of column 0: plan.hpp kRyxPad
@@ -241,6 +268,7 @@ struct RyxDev {
     int uc = 0;
 };
 hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *ryx_instance(const RyxDev &d);
 
 // General-row variant (plan.hpp build_ryg; kernels.hip ryg_kernel): ryx's tabled columns and column
 // parts, rows from a per-row record table instead of an exact P:Q.
@@ -277,6 +305,9 @@ struct RygDev {
     int run = 0;
 };
 hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+// byPos: rows by window position (ryu_kernel) -- launch_ryg: d.nl == 1 && d.posRec; a host-only plan has no
+// device tables and passes what ryg_dev decided (abi.hip plan_instance).  run: the run mode in use (0: none).
+const Instance *ryg_instance(const RygDev &d, bool byPos, int run);
 
 // Exact 2:3 Lanczos-3 upscale (plan.hpp U23Tables).
 struct U23Dev {
@@ -292,6 +323,7 @@ struct U23Dev {
     int yS[2][8];
 };
 hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *u23_instance(const U23Dev &d);
 
 // Exact 2:3 Linear upscale (plan.hpp L23Tables).
 struct L23Dev {
@@ -302,6 +334,7 @@ struct L23Dev {
     uint32_t cx[3];              // phase j's (c_0, c_1) u16 pair
 };
 hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *l23_instance(const L23Dev &d);
 
 // Exact 3:2 Area downscale (plan.hpp A32Tables).
 struct A32Dev {
@@ -312,6 +345,7 @@ struct A32Dev {
     uint32_t cx[2];              // phase p's (c_0, c_1) u16 pair
 };
 hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+const Instance *a32_instance(const A32Dev &d);
 
 // --- Lanczos row-band streamer (integer ratio, single phase).
 struct LanczosDev {

@@ -2252,6 +2252,290 @@ __global__ __launch_bounds__(256) void area_d32_kernel(A32Args a)
 
 } // namespace
 
+// ================================================================ instantiations
+//
+// One table and one lookup per family (kernels.hpp Instance): what the launchers below run and what
+// the C ABI reports.  A lookup is a pure function of the *Dev.
+
+namespace {
+
+#define IQO_KERN(...) reinterpret_cast<const void *>(__VA_ARGS__)
+
+Instance inst_of(int family, const void *kern)
+{
+    Instance i{};
+    i.family = family;
+    i.kern = kern;
+    return i;
+}
+
+Instance pd_inst(int family, int pd, int variant, const void *kern)
+{
+    Instance i = inst_of(family, kern);
+    i.PD = pd;
+    i.VARIANT = variant;
+    return i;
+}
+
+InstanceList up2_instances()
+{
+    static const auto mk = [](int nt, int f, const void *kern) {
+        Instance i = inst_of(kFamUp2, kern);
+        i.NT = nt;
+        i.F = f;
+        return i;
+    };
+    static const Instance k[] = {mk(4, 2, IQO_KERN(lanczos_up2_kernel<4, 2>)), mk(6, 2, IQO_KERN(lanczos_up2_kernel<6, 2>)),
+                                 mk(4, 3, IQO_KERN(lanczos_up2_kernel<4, 3>)), mk(6, 3, IQO_KERN(lanczos_up2_kernel<6, 3>))};
+    return {k, static_cast<int>(sizeof k / sizeof k[0])};
+}
+
+// variant 0: Lanczos-3 (10 taps), 1: Lanczos-2 (6 taps); the first depth of a variant is its default
+InstanceList d32_instances()
+{
+    static const Instance k[] = {pd_inst(kFamD32, 1, 0, IQO_KERN(lanczos_d32_kernel<1, -4, 10, 8, 2, 5, -4>)),
+                                 pd_inst(kFamD32, 2, 0, IQO_KERN(lanczos_d32_kernel<2, -4, 10, 8, 2, 5, -4>)),
+                                 pd_inst(kFamD32, 4, 0, IQO_KERN(lanczos_d32_kernel<4, -4, 10, 8, 2, 5, -4>)),
+                                 pd_inst(kFamD32, 1, 1, IQO_KERN(lanczos_d32_kernel<1, -2, 7, 5, 2, 3, -2>)),
+                                 pd_inst(kFamD32, 3, 1, IQO_KERN(lanczos_d32_kernel<3, -2, 7, 5, 2, 3, -2>))};
+    return {k, static_cast<int>(sizeof k / sizeof k[0])};
+}
+
+// variant 0: Lanczos-3 (18 taps), 1: Lanczos-2 (12 taps)
+InstanceList d31_instances()
+{
+    static const Instance k[] = {pd_inst(kFamD31, 1, 0, IQO_KERN(lanczos_d31_kernel<1, 0>)),
+                                 pd_inst(kFamD31, 5, 0, IQO_KERN(lanczos_d31_kernel<5, 0>)),
+                                 pd_inst(kFamD31, 1, 1, IQO_KERN(lanczos_d31_kernel<1, 1>)),
+                                 pd_inst(kFamD31, 2, 1, IQO_KERN(lanczos_d31_kernel<2, 1>)),
+                                 pd_inst(kFamD31, 4, 1, IQO_KERN(lanczos_d31_kernel<4, 1>))};
+    return {k, static_cast<int>(sizeof k / sizeof k[0])};
+}
+
+InstanceList u23_instances()
+{
+    static const Instance k[] = {pd_inst(kFamU23, 1, 0, IQO_KERN(lanczos_u23_kernel<1>)),
+                                 pd_inst(kFamU23, 2, 0, IQO_KERN(lanczos_u23_kernel<2>))};
+    return {k, 2};
+}
+
+InstanceList l23_instances()
+{
+    static const Instance k[] = {pd_inst(kFamL23, 2, 0, IQO_KERN(linear_u23_kernel<2>)),
+                                 pd_inst(kFamL23, 1, 0, IQO_KERN(linear_u23_kernel<1>))};
+    return {k, 2};
+}
+
+InstanceList a32_instances()
+{
+    static const Instance k[] = {pd_inst(kFamA32, 4, 0, IQO_KERN(area_d32_kernel<4>)),
+                                 pd_inst(kFamA32, 2, 0, IQO_KERN(area_d32_kernel<2>)),
+                                 pd_inst(kFamA32, 8, 0, IQO_KERN(area_d32_kernel<8>))};
+    return {k, 3};
+}
+
+// The entry of depth `pd` and tap structure `variant`; a depth the variant does not instantiate (0
+// included) takes the variant's first entry, its default -- abi.hip run_band rejects a forced depth
+// that is not instantiated before it gets here.
+const Instance *pd_lookup(InstanceList l, int pd, int variant)
+{
+    const Instance *def = nullptr;
+    for (int i = 0; i < l.count; ++i)
+        if (l.first[i].VARIANT == variant) {
+            if (l.first[i].PD == pd)
+                return l.first + i;
+            if (!def)
+                def = l.first + i;
+        }
+    return def;
+}
+
+// ryx_kernel (plan.cpp build_ryx kShapes): method, P, Q, taps (the reference's taps less the zero outer
+// taps of every phase), column pairs
+// PD: groups of P source rows loaded ahead (ubench: with one group in flight the source loads
+// cost G5 19 % and Lanczos-4 2:1 27 % of the kernel time -- latency, not bandwidth)
+// ADJ: adjacent column pairs per thread (9:4 rows with columns >= 2:1, ryx_dev d.adj)
+// CPT: output columns per thread (upscales, ryx_dev d.cpt)
+// UC: uniform column coefficients (scalars)
+InstanceList ryx_instances()
+{
+    static const auto mk = [](bool lz, int P, int Q, int T, int NP, int PD, bool adj, int cpt, bool uc, const void *kern) {
+        Instance i = inst_of(kFamRyx, kern);
+        i.LZ = lz;
+        i.P = P;
+        i.Q = Q;
+        i.T = T;
+        i.NP = NP;
+        i.PD = PD;
+        i.ADJ = adj;
+        i.CPT = cpt;
+        i.UC = uc;
+        return i;
+    };
+#define IQO_RYX_C(LZ_, P_, Q_, T_, NP_, PD_, ADJ_, CPT_)                                                        \
+    mk(LZ_, P_, Q_, T_, NP_, PD_, ADJ_, CPT_, false, IQO_KERN(ryx_kernel<LZ_, P_, Q_, T_, NP_, PD_, ADJ_, CPT_>))
+#define IQO_RYX_UA(P_, Q_, T_, NP_, PD_, ADJ_)                                                                \
+    mk(true, P_, Q_, T_, NP_, PD_, ADJ_, 2, true, IQO_KERN(ryx_kernel<true, P_, Q_, T_, NP_, PD_, ADJ_, 2, true>))
+#define IQO_RYX_U(P_, Q_, T_, NP_, PD_) IQO_RYX_UA(P_, Q_, T_, NP_, PD_, false), IQO_RYX_UA(P_, Q_, T_, NP_, PD_, true)
+#define IQO_RYX_A(LZ_, P_, Q_, T_, NP_, PD_, ADJ_) IQO_RYX_C(LZ_, P_, Q_, T_, NP_, PD_, ADJ_, 2)
+#define IQO_RYX(LZ_, P_, Q_, T_, NP_, PD_) IQO_RYX_A(LZ_, P_, Q_, T_, NP_, PD_, false)
+#define IQO_RYX2(LZ_, P_, Q_, T_, NP_, PD_) IQO_RYX(LZ_, P_, Q_, T_, NP_, PD_), IQO_RYX_A(LZ_, P_, Q_, T_, NP_, PD_, true)
+    static const Instance kInst[] = {
+        IQO_RYX2(true, 9, 4, 12, 8, 2), IQO_RYX2(true, 9, 4, 12, 10, 2),  // Lanczos-3 9:4 (1080p -> 480p, -> 640x480)
+        IQO_RYX2(true, 9, 4, 8, 6, 2), IQO_RYX2(true, 9, 4, 8, 7, 2),     // Lanczos-2 9:4
+        IQO_RYX2(false, 9, 4, 4, 3, 2),                                   // Area 9:4
+        IQO_RYX(true, 4, 1, 14, 13, 4), IQO_RYX(true, 4, 1, 14, 9, 4),  // Lanczos-3 / -2 4:1 (4K -> 960x540)
+        IQO_RYX(true, 4, 1, 22, 17, 3),  // Lanczos-4 4:1 (round 6: 22 of 32 row taps; had run the general kernel)
+        IQO_RYX(true, 2, 1, 4, 3, 2),                                   // Lanczos-1 2:1
+        IQO_RYX(true, 2, 1, 12, 9, 3), IQO_RYX(true, 2, 1, 16, 11, 4),  // Lanczos-4 / -5 2:1
+        IQO_RYX(true, 2, 1, 18, 13, 5), IQO_RYX(true, 2, 1, 20, 15, 5), // Lanczos-6 / -7 2:1
+        IQO_RYX(true, 2, 1, 22, 17, 2), IQO_RYX(true, 2, 1, 24, 19, 2), // Lanczos-8 / -9 2:1
+        IQO_RYX(true, 4, 9, 6, 4, 2), IQO_RYX(true, 4, 9, 4, 3, 2),     // Lanczos-3 / -2 4:9 up (480 -> 1080 rows)
+        IQO_RYX_C(true, 4, 9, 6, 4, 2, false, 4),
+        // Lanczos 2:1 columns (uniform coefficients): no per-lane coefficient registers; adjacent
+        // column pairs (ryx_dev d.uc, d.adj)
+        IQO_RYX_U(2, 1, 4, 3, 2), IQO_RYX_U(2, 1, 12, 9, 3), IQO_RYX_U(2, 1, 16, 11, 4), IQO_RYX_U(2, 1, 18, 13, 5), IQO_RYX_U(2, 1, 20, 15, 5),
+        IQO_RYX_U(2, 1, 22, 17, IQO_RYX_UC_PD), IQO_RYX_U(2, 1, 24, 19, IQO_RYX_UC_PD),
+    };
+#undef IQO_RYX_U
+#undef IQO_RYX_UA
+#undef IQO_RYX2
+#undef IQO_RYX
+#undef IQO_RYX_A
+#undef IQO_RYX_C
+    return {kInst, static_cast<int>(sizeof kInst / sizeof kInst[0])};
+}
+
+// ryg_kernel (plan.cpp build_ryg kShapes: taps, column pairs; PD = kRygPD output rows ahead), then
+// ryu_kernel (upscale rows by window position: PD positions ahead, a trip of lcm(T, PD, 2);
+// RUN: run mode, work-row dwords per 4 adjacent columns, 0 off; KM: output rows per window position at most)
+InstanceList ryg_instances()
+{
+    static const auto mk = [](bool lz, int T, int NP, int cpt, int nl, const void *kern) {
+        Instance i = inst_of(kFamRyg, kern);
+        i.LZ = lz;
+        i.T = T;
+        i.NP = NP;
+        i.PD = kRygPD;
+        i.CPT = cpt;
+        i.NL = nl;
+        return i;
+    };
+    static const auto up = [](int T, int NP, int PD, int cpt, int run, int km, const void *kern) {
+        Instance i = inst_of(kFamRyg, kern);
+        i.sub = kSubRyu;
+        i.T = T;
+        i.NP = NP;
+        i.PD = PD;
+        i.CPT = cpt;
+        i.RUN = run;
+        i.KM = km;
+        return i;
+    };
+#define IQO_RYG_1(LZ_, T_, NP_, CPT_, NL_) mk(LZ_, T_, NP_, CPT_, NL_, IQO_KERN(ryg_kernel<LZ_, T_, NP_, kRygPD, CPT_, NL_>))
+#define IQO_RYG_N(LZ_, T_, NP_, NL_) IQO_RYG_1(LZ_, T_, NP_, 2, NL_), IQO_RYG_1(LZ_, T_, NP_, 3, NL_), IQO_RYG_1(LZ_, T_, NP_, 4, NL_)
+#define IQO_RYG(LZ_, T_, NP_) IQO_RYG_N(LZ_, T_, NP_, 2)
+#define IQO_RYU_1(T_, NP_, PD_, CPT_, RUN_, KM_) up(T_, NP_, PD_, CPT_, RUN_, KM_, IQO_KERN(ryu_kernel<T_, NP_, PD_, CPT_, RUN_, KM_>))
+#define IQO_RYU_K(T_, NP_, PD_, KM_)                                                                   \
+    IQO_RYU_1(T_, NP_, PD_, 2, 0, KM_), IQO_RYU_1(T_, NP_, PD_, 3, 0, KM_), IQO_RYU_1(T_, NP_, PD_, 4, 0, KM_), \
+    IQO_RYU_1(T_, NP_, PD_, 4, NP_ + 1, KM_), IQO_RYU_1(T_, NP_, PD_, 4, NP_ + 2, KM_)
+#define IQO_RYU(T_, NP_, PD_) IQO_RYU_K(T_, NP_, PD_, 2), IQO_RYU_K(T_, NP_, PD_, 3)
+    static const Instance kInst[] = {
+        IQO_RYG(true, 4, 3), IQO_RYG(true, 6, 4), IQO_RYG(true, 8, 5), IQO_RYG(true, 10, 5), IQO_RYG(true, 10, 6),
+        IQO_RYG(true, 12, 7),
+        IQO_RYG(true, 12, 8),  // (round 6: Lanczos-5 rows of 1 .. 2 : 1, 8 column pairs)
+        IQO_RYG(true, 16, 10), IQO_RYG(true, 16, 12),  // (round 6: Lanczos-5 / -6 rows of 1 .. 2 : 1)
+        // upscales (windows 0 or 1 rows apart: one new row per output row)
+        IQO_RYG_N(true, 4, 3, 1), IQO_RYG_N(true, 6, 4, 1), IQO_RYG_N(true, 8, 5, 1),
+        // Area downscales of 1 .. 2 : 1 (round 5: after the ring and the columns-per-thread rule)
+        IQO_RYG(false, 3, 2), IQO_RYG(false, 3, 3),
+        // Lanczos downscales of 2 .. 3 : 1 (windows 2 or 3 rows apart; 2 columns per thread)
+        IQO_RYG_1(true, 10, 6, 2, 3), IQO_RYG_1(true, 12, 7, 2, 3), IQO_RYG_1(true, 14, 8, 2, 3), IQO_RYG_1(true, 16, 9, 2, 3),
+        IQO_RYG_1(true, 18, 10, 2, 3),
+        // (round 6: Lanczos-4 rows of 2 .. 3 : 1, 12 column pairs: 4K -> 1366x768 had run the tile kernel)
+        IQO_RYG_1(true, 18, 12, 2, 3),
+        // (round 6: Lanczos-5 rows of 2 .. 3 : 1, 22 taps, 16 column pairs, one workgroup per CU)
+        IQO_RYG_1(true, 22, 16, 2, 3),
+        // Area downscales of 2 .. 3 : 1
+        IQO_RYG_1(false, 4, 3, 2, 3), IQO_RYG_1(false, 4, 4, 2, 3),
+        // downscales of 3 .. 4 : 1 (windows 3 or 4 rows apart)
+        IQO_RYG_1(true, 14, 8, 2, 4), IQO_RYG_1(true, 16, 9, 2, 4), IQO_RYG_1(true, 18, 10, 2, 4), IQO_RYG_1(true, 20, 11, 2, 4),
+        IQO_RYG_1(true, 22, 12, 2, 4), IQO_RYG_1(true, 24, 13, 2, 4),
+        // (round 6: Lanczos-4 rows of 3 .. 4 : 1, 16 column pairs, one workgroup per CU)
+        IQO_RYG_1(true, 22, 16, 2, 4), IQO_RYG_1(false, 5, 3, 2, 4), IQO_RYG_1(false, 5, 4, 2, 4),
+        // ryu_kernel
+        IQO_RYU(4, 3, 4), IQO_RYU(6, 4, 3), IQO_RYU(8, 5, 4)};
+#undef IQO_RYU
+#undef IQO_RYU_K
+#undef IQO_RYU_1
+#undef IQO_RYG
+#undef IQO_RYG_N
+#undef IQO_RYG_1
+    return {kInst, static_cast<int>(sizeof kInst / sizeof kInst[0])};
+}
+
+#undef IQO_KERN
+
+} // namespace
+
+InstanceList instances(int family)
+{
+    switch (family) {
+    case kFamUp2: return up2_instances();
+    case kFamD32: return d32_instances();
+    case kFamD31: return d31_instances();
+    case kFamU23: return u23_instances();
+    case kFamL23: return l23_instances();
+    case kFamA32: return a32_instances();
+    case kFamRyx: return ryx_instances();
+    case kFamRyg: return ryg_instances();
+    default: return tile_walk_instances(family);
+    }
+}
+
+const Instance *up2_instance(const Up2Dev &u)
+{
+    const InstanceList l = up2_instances();
+    for (int i = 0; i < l.count; ++i)  // (launch_up2 has checked NT 4 / 6 and F 2 / 3)
+        if (l.first[i].NT == (u.NT == 6 ? 6 : 4) && l.first[i].F == (u.F == 3 ? 3 : 2))
+            return l.first + i;
+    return nullptr;
+}
+
+const Instance *d32_instance(const D32Dev &d) { return pd_lookup(d32_instances(), d.pd, d.variant); }
+const Instance *d31_instance(const D31Dev &d) { return pd_lookup(d31_instances(), d.pd, d.variant); }
+const Instance *u23_instance(const U23Dev &d) { return pd_lookup(u23_instances(), d.pd, 0); }
+const Instance *l23_instance(const L23Dev &d) { return pd_lookup(l23_instances(), d.pd, 0); }
+const Instance *a32_instance(const A32Dev &d) { return pd_lookup(a32_instances(), d.pd, 0); }
+
+const Instance *ryx_instance(const RyxDev &d)
+{
+    const InstanceList l = ryx_instances();
+    const Instance *hit = nullptr;
+    for (int i = 0; i < l.count; ++i) {
+        const Instance &k = l.first[i];
+        if ((k.LZ != 0) == d.lanczos && k.P == d.P && k.Q == d.Q && k.T == d.taps && k.NP == d.NP && (k.ADJ != 0) == (d.adj != 0) &&
+            k.CPT == d.cpt && (!k.UC || d.uc) && (!hit || (k.UC && !hit->UC)))  // (the uniform-column one first)
+            hit = &k;
+    }
+    return hit;
+}
+
+const Instance *ryg_instance(const RygDev &d, bool byPos, int run)
+{
+    const InstanceList l = ryg_instances();
+    const Instance *hit = nullptr;
+    for (int i = 0; i < l.count; ++i) {
+        const Instance &k = l.first[i];
+        if (k.sub == 0 && !byPos && (k.LZ != 0) == d.lanczos && k.T == d.taps && k.NP == d.NP && k.CPT == d.cpt && k.NL == d.nl)
+            hit = &k;
+        if (k.sub == kSubRyu && byPos && d.lanczos && k.T == d.taps && k.NP == d.NP && k.CPT == d.cpt && k.RUN == run &&
+            k.KM == std::max(2, d.posRows))
+            hit = &k;
+    }
+    return hit;
+}
+
 // ================================================================ launchers
 
 hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
@@ -2264,10 +2548,10 @@ hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, i
         (u.NT != 4 && u.NT != 6) || (u.F != 2 && u.F != 3) || u.dstW % (8 * u.F) || u.dstW != u.F * u.srcW ||
         u.dstW < 16 * u.F || u.dstH != u.F * u.srcH)
         return hipErrorInvalidValue;
-    const void *kern = u.F == 3 ? (u.NT == 6 ? reinterpret_cast<const void *>(lanczos_up2_kernel<6, 3>)
-                                             : reinterpret_cast<const void *>(lanczos_up2_kernel<4, 3>))
-                                : (u.NT == 6 ? reinterpret_cast<const void *>(lanczos_up2_kernel<6, 2>)
-                                             : reinterpret_cast<const void *>(lanczos_up2_kernel<4, 2>));
+    const Instance *inst = up2_instance(u);
+    if (!inst)
+        return hipErrorInvalidValue;
+    const void *kern = inst->kern;
     // producing lanes per wave: the fewest waves per row, then the fewest lanes that tile the width
     const int lanes = u.dstW / (8 * u.F);
     int wpr = (lanes + 61) / 62;
@@ -2315,16 +2599,10 @@ hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, i
     int np = d.np > 0 ? min(d.np, min(62, lanes)) : (lanes + wpr - 1) / wpr;
     wpr = (lanes + np - 1) / np;
     // one group of rows loaded ahead by default (G1, fresh data: 2.5 % faster than 2, 8 % than 4)
-    const void *kern = nullptr;
-    if (d.variant == 0)
-        kern = d.pd == 2   ? reinterpret_cast<const void *>(lanczos_d32_kernel<2, -4, 10, 8, 2, 5, -4>)
-               : d.pd == 4 ? reinterpret_cast<const void *>(lanczos_d32_kernel<4, -4, 10, 8, 2, 5, -4>)
-                           : reinterpret_cast<const void *>(lanczos_d32_kernel<1, -4, 10, 8, 2, 5, -4>);
-    else if (d.variant == 1)
-        kern = d.pd == 3 ? reinterpret_cast<const void *>(lanczos_d32_kernel<3, -2, 7, 5, 2, 3, -2>)
-                         : reinterpret_cast<const void *>(lanczos_d32_kernel<1, -2, 7, 5, 2, 3, -2>);
-    else
+    const Instance *inst = d32_instance(d);
+    if (!inst)
         return hipErrorInvalidValue;
+    const void *kern = inst->kern;
     const int evenBegin = rowBegin & ~1;
     const int rows = rowEnd - evenBegin;
     // bands: ~2.5 rounds of resident waves, whole trips (8 rows) per band, >= 16 rows
@@ -2362,16 +2640,10 @@ hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, i
     int wpr = (lanes + 61) / 62;
     int np = d.np > 0 ? min(d.np, min(62, lanes)) : (lanes + wpr - 1) / wpr;
     wpr = (lanes + np - 1) / np;
-    const void *kern = nullptr;
-    if (d.variant == 0)
-        kern = d.pd == 5 ? reinterpret_cast<const void *>(lanczos_d31_kernel<5, 0>)
-                         : reinterpret_cast<const void *>(lanczos_d31_kernel<1, 0>);
-    else if (d.variant == 1)
-        kern = d.pd == 2   ? reinterpret_cast<const void *>(lanczos_d31_kernel<2, 1>)
-               : d.pd == 4 ? reinterpret_cast<const void *>(lanczos_d31_kernel<4, 1>)
-                           : reinterpret_cast<const void *>(lanczos_d31_kernel<1, 1>);
-    else
+    const Instance *inst = d31_instance(d);
+    if (!inst)
         return hipErrorInvalidValue;
+    const void *kern = inst->kern;
     const int rows = rowEnd - rowBegin;
     const int trip = d.variant == 0 ? 5 : 4;  // output rows per unrolled trip (U)
     // bands of two trips (round 6, steady clock: 4K -> 720p x128: 72 bands of 10 rows 0.235 ms vs
@@ -2401,65 +2673,13 @@ hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, i
     const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
     if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
         return hipErrorInvalidValue;
-    // instantiations (plan.cpp build_ryx kShapes): method, P, Q, taps (the reference's taps less the
-    // zero outer taps of every phase), column pairs
-    // PD: groups of P source rows loaded ahead (ubench: with one group in flight the source loads
-    // cost G5 19 % and Lanczos-4 2:1 27 % of the kernel time -- latency, not bandwidth)
-    // ADJ: adjacent column pairs per thread (9:4 rows with columns >= 2:1, ryx_dev d.adj)
-    // CPT: output columns per thread (upscales, ryx_dev d.cpt)
-    struct Inst {
-        bool lz;
-        int P, Q, T, NP;
-        bool adj;
-        int cpt;
-        bool uc;  // uniform column coefficients (scalars)
-        const void *kern;
-    };
-#define IQO_RYX_C(LZ_, P_, Q_, T_, NP_, PD_, ADJ_, CPT_)                                                        \
-    {LZ_, P_, Q_, T_, NP_, ADJ_, CPT_, false, reinterpret_cast<const void *>(ryx_kernel<LZ_, P_, Q_, T_, NP_, PD_, ADJ_, CPT_>)}
-#define IQO_RYX_UA(P_, Q_, T_, NP_, PD_, ADJ_)                                                                \
-    {true, P_, Q_, T_, NP_, ADJ_, 2, true, reinterpret_cast<const void *>(ryx_kernel<true, P_, Q_, T_, NP_, PD_, ADJ_, 2, true>)}
-#define IQO_RYX_U(P_, Q_, T_, NP_, PD_) IQO_RYX_UA(P_, Q_, T_, NP_, PD_, false), IQO_RYX_UA(P_, Q_, T_, NP_, PD_, true)
-#define IQO_RYX_A(LZ_, P_, Q_, T_, NP_, PD_, ADJ_) IQO_RYX_C(LZ_, P_, Q_, T_, NP_, PD_, ADJ_, 2)
-#define IQO_RYX(LZ_, P_, Q_, T_, NP_, PD_) IQO_RYX_A(LZ_, P_, Q_, T_, NP_, PD_, false)
-#define IQO_RYX2(LZ_, P_, Q_, T_, NP_, PD_) IQO_RYX(LZ_, P_, Q_, T_, NP_, PD_), IQO_RYX_A(LZ_, P_, Q_, T_, NP_, PD_, true)
-    static const Inst kInst[] = {
-        IQO_RYX2(true, 9, 4, 12, 8, 2), IQO_RYX2(true, 9, 4, 12, 10, 2),  // Lanczos-3 9:4 (1080p -> 480p, -> 640x480)
-        IQO_RYX2(true, 9, 4, 8, 6, 2), IQO_RYX2(true, 9, 4, 8, 7, 2),     // Lanczos-2 9:4
-        IQO_RYX2(false, 9, 4, 4, 3, 2),                                   // Area 9:4
-        IQO_RYX(true, 4, 1, 14, 13, 4), IQO_RYX(true, 4, 1, 14, 9, 4),  // Lanczos-3 / -2 4:1 (4K -> 960x540)
-        IQO_RYX(true, 4, 1, 22, 17, 3),  // Lanczos-4 4:1 (round 6: 22 of 32 row taps; had run the general kernel)
-        IQO_RYX(true, 2, 1, 4, 3, 2),                                   // Lanczos-1 2:1
-        IQO_RYX(true, 2, 1, 12, 9, 3), IQO_RYX(true, 2, 1, 16, 11, 4),  // Lanczos-4 / -5 2:1
-        IQO_RYX(true, 2, 1, 18, 13, 5), IQO_RYX(true, 2, 1, 20, 15, 5), // Lanczos-6 / -7 2:1
-        IQO_RYX(true, 2, 1, 22, 17, 2), IQO_RYX(true, 2, 1, 24, 19, 2), // Lanczos-8 / -9 2:1
-        IQO_RYX(true, 4, 9, 6, 4, 2), IQO_RYX(true, 4, 9, 4, 3, 2),     // Lanczos-3 / -2 4:9 up (480 -> 1080 rows)
-        IQO_RYX_C(true, 4, 9, 6, 4, 2, false, 4),
-        // Lanczos 2:1 columns (uniform coefficients): no per-lane coefficient registers; adjacent
-        // column pairs (ryx_dev d.uc, d.adj)
-        IQO_RYX_U(2, 1, 4, 3, 2), IQO_RYX_U(2, 1, 12, 9, 3), IQO_RYX_U(2, 1, 16, 11, 4), IQO_RYX_U(2, 1, 18, 13, 5), IQO_RYX_U(2, 1, 20, 15, 5),
-        IQO_RYX_U(2, 1, 22, 17, IQO_RYX_UC_PD), IQO_RYX_U(2, 1, 24, 19, IQO_RYX_UC_PD),
-    };
-#undef IQO_RYX_U
-#undef IQO_RYX_UA
-#undef IQO_RYX2
-#undef IQO_RYX
-#undef IQO_RYX_A
-#undef IQO_RYX_C
-    const void *kern = nullptr;
-    int trip = 0;
-    bool kernUc = false;
-    for (const Inst &k : kInst)
-        if (k.lz == d.lanczos && k.P == d.P && k.Q == d.Q && k.T == d.taps && k.NP == d.NP && k.adj == (d.adj != 0) &&
-            k.cpt == d.cpt && (!k.uc || d.uc) && (!kern || (k.uc && !kernUc))) {  // (the uniform-column one first)
-            kernUc = k.uc;
-            kern = k.kern;
-            const int span = (k.P * (k.Q - 1)) / k.Q + k.T, nw0 = (span + k.P - 1) / k.P * k.P;
-            const int nw = ((nw0 / k.P) * k.Q) % 2 ? nw0 + k.P : nw0;
-            trip = nw / k.P * k.Q * 2;  // (as the kernel: output rows per trip) x 2
-        }
-    if (!kern)
+    const Instance *inst = ryx_instance(d);
+    if (!inst)
         return hipErrorInvalidValue;
+    const void *kern = inst->kern;
+    const int span = (inst->P * (inst->Q - 1)) / inst->Q + inst->T, nw0 = (span + inst->P - 1) / inst->P * inst->P;
+    const int nw = ((nw0 / inst->P) * inst->Q) % 2 ? nw0 + inst->P : nw0;
+    const int trip = nw / inst->P * inst->Q * 2;  // (as the kernel: output rows per trip) x 2
     if (d.parts < 1 || d.parts > 16)
         return hipErrorInvalidValue;
     const int threads = d.threads > 0 ? d.threads : 512;
@@ -2521,73 +2741,9 @@ hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, i
     const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;
     if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
         return iqo_ryg_einval(2);
-    // instantiations (plan.cpp build_ryg kShapes): taps, column pairs; PD = 4 output rows ahead
-    struct Inst {
-        bool lz;
-        int T, NP, cpt, nl;
-        const void *kern;
-        int run;  // ryu_kernel run mode: work-row dwords per 4 adjacent columns (0: off)
-        int km;   // ryu_kernel: output rows per window position (at most)
-    };
-#define IQO_RYG_N(LZ_, T_, NP_, NL_)                                                                   \
-    {LZ_, T_, NP_, 2, NL_, reinterpret_cast<const void *>(ryg_kernel<LZ_, T_, NP_, kRygPD, 2, NL_>), 0, 0},    \
-    {LZ_, T_, NP_, 3, NL_, reinterpret_cast<const void *>(ryg_kernel<LZ_, T_, NP_, kRygPD, 3, NL_>), 0, 0},    \
-    {LZ_, T_, NP_, 4, NL_, reinterpret_cast<const void *>(ryg_kernel<LZ_, T_, NP_, kRygPD, 4, NL_>), 0, 0}
-#define IQO_RYG(LZ_, T_, NP_) IQO_RYG_N(LZ_, T_, NP_, 2)
-    static const Inst kInst[] = {IQO_RYG(true, 4, 3),  IQO_RYG(true, 6, 4),  IQO_RYG(true, 8, 5),  IQO_RYG(true, 10, 5),
-                                 IQO_RYG(true, 10, 6), IQO_RYG(true, 12, 7),
-                                 IQO_RYG(true, 12, 8),  // (round 6: Lanczos-5 rows of 1 .. 2 : 1, 8 column pairs)
-                                 IQO_RYG(true, 16, 10), IQO_RYG(true, 16, 12),  // (round 6: Lanczos-5 / -6 rows of 1 .. 2 : 1)
-                                 // upscales (windows 0 or 1 rows apart: one new row per output row)
-                                 IQO_RYG_N(true, 4, 3, 1), IQO_RYG_N(true, 6, 4, 1), IQO_RYG_N(true, 8, 5, 1),
-                                 // Area downscales of 1 .. 2 : 1 (round 5: after the ring and the columns-per-thread rule)
-                                 IQO_RYG(false, 3, 2), IQO_RYG(false, 3, 3),
-                                 // Lanczos downscales of 2 .. 3 : 1 (windows 2 or 3 rows apart; 2 columns per thread)
-                                 {true, 10, 6, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 10, 6, kRygPD, 2, 3>), 0, 0},
-                                 {true, 12, 7, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 12, 7, kRygPD, 2, 3>), 0, 0},
-                                 {true, 14, 8, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 14, 8, kRygPD, 2, 3>), 0, 0},
-                                 {true, 16, 9, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 16, 9, kRygPD, 2, 3>), 0, 0},
-                                 {true, 18, 10, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 18, 10, kRygPD, 2, 3>), 0, 0},
-                                 // (round 6: Lanczos-4 rows of 2 .. 3 : 1, 12 column pairs: 4K -> 1366x768 had run the tile kernel)
-                                 {true, 18, 12, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 18, 12, kRygPD, 2, 3>), 0, 0},
-                                 // (round 6: Lanczos-5 rows of 2 .. 3 : 1, 22 taps, 16 column pairs, one workgroup per CU)
-                                 {true, 22, 16, 2, 3, reinterpret_cast<const void *>(ryg_kernel<true, 22, 16, kRygPD, 2, 3>), 0, 0},
-                                 // Area downscales of 2 .. 3 : 1
-                                 {false, 4, 3, 2, 3, reinterpret_cast<const void *>(ryg_kernel<false, 4, 3, kRygPD, 2, 3>), 0, 0},
-                                 {false, 4, 4, 2, 3, reinterpret_cast<const void *>(ryg_kernel<false, 4, 4, kRygPD, 2, 3>), 0, 0},
-                                 // downscales of 3 .. 4 : 1 (windows 3 or 4 rows apart)
-                                 {true, 14, 8, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 14, 8, kRygPD, 2, 4>), 0, 0},
-                                 {true, 16, 9, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 16, 9, kRygPD, 2, 4>), 0, 0},
-                                 {true, 18, 10, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 18, 10, kRygPD, 2, 4>), 0, 0},
-                                 {true, 20, 11, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 20, 11, kRygPD, 2, 4>), 0, 0},
-                                 {true, 22, 12, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 22, 12, kRygPD, 2, 4>), 0, 0},
-                                 {true, 24, 13, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 24, 13, kRygPD, 2, 4>), 0, 0},
-                                 // (round 6: Lanczos-4 rows of 3 .. 4 : 1, 16 column pairs, one workgroup per CU)
-                                 {true, 22, 16, 2, 4, reinterpret_cast<const void *>(ryg_kernel<true, 22, 16, kRygPD, 2, 4>), 0, 0},
-                                 {false, 5, 3, 2, 4, reinterpret_cast<const void *>(ryg_kernel<false, 5, 3, kRygPD, 2, 4>), 0, 0},
-                                 {false, 5, 4, 2, 4, reinterpret_cast<const void *>(ryg_kernel<false, 5, 4, kRygPD, 2, 4>), 0, 0}};
-#undef IQO_RYG_N
-#undef IQO_RYG
-    // upscale rows by window position (ryu_kernel): PD positions ahead (a trip of lcm(T, PD, 2))
-#define IQO_RYU_K(T_, NP_, PD_, KM_)                                                                   \
-    {true, T_, NP_, 2, 1, reinterpret_cast<const void *>(ryu_kernel<T_, NP_, PD_, 2, 0, KM_>), 0, KM_},  \
-    {true, T_, NP_, 3, 1, reinterpret_cast<const void *>(ryu_kernel<T_, NP_, PD_, 3, 0, KM_>), 0, KM_},  \
-    {true, T_, NP_, 4, 1, reinterpret_cast<const void *>(ryu_kernel<T_, NP_, PD_, 4, 0, KM_>), 0, KM_},  \
-    {true, T_, NP_, 4, 1, reinterpret_cast<const void *>(ryu_kernel<T_, NP_, PD_, 4, NP_ + 1, KM_>), NP_ + 1, KM_}, \
-    {true, T_, NP_, 4, 1, reinterpret_cast<const void *>(ryu_kernel<T_, NP_, PD_, 4, NP_ + 2, KM_>), NP_ + 2, KM_}
-#define IQO_RYU(T_, NP_, PD_) IQO_RYU_K(T_, NP_, PD_, 2), IQO_RYU_K(T_, NP_, PD_, 3)
-    static const Inst kUp[] = {IQO_RYU(4, 3, 4), IQO_RYU(6, 4, 3), IQO_RYU(8, 5, 4)};
-#undef IQO_RYU
-#undef IQO_RYU_K
-    const void *kern = nullptr;
     const bool byPos = d.nl == 1 && d.posRec;
-    for (const Inst &k : kInst)
-        if (!byPos && k.lz == d.lanczos && k.T == d.taps && k.NP == d.NP && k.cpt == d.cpt && k.nl == d.nl)
-            kern = k.kern;
-    for (const Inst &k : kUp)
-        if (byPos && d.lanczos && k.T == d.taps && k.NP == d.NP && k.cpt == d.cpt && k.run == (d.colRun ? d.run : 0) &&
-            k.km == std::max(2, d.posRows))
-            kern = k.kern;
+    const Instance *inst = ryg_instance(d, byPos, d.colRun ? d.run : 0);
+    const void *kern = inst ? inst->kern : nullptr;
     if (!kern || d.parts < 1 || d.parts > 16)
         return iqo_ryg_einval(3);
     const int threads = d.threads > 0 ? d.threads : 512;
@@ -2650,8 +2806,7 @@ hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, i
     int wpr = (lanes + 61) / 62;
     int np = d.np > 0 ? min(d.np, min(62, lanes)) : (lanes + wpr - 1) / wpr;
     wpr = (lanes + np - 1) / np;
-    const void *kern = d.pd == 2 ? reinterpret_cast<const void *>(lanczos_u23_kernel<2>)
-                                 : reinterpret_cast<const void *>(lanczos_u23_kernel<1>);
+    const void *kern = u23_instance(d)->kern;
     const int row3Begin = rowBegin - rowBegin % 3;
     const int rows = rowEnd - row3Begin;
     constexpr int trip = 12;  // output rows per unrolled trip
@@ -2688,8 +2843,7 @@ hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, i
     int wpr = (lanes + 61) / 62;
     int np = d.np > 0 ? min(d.np, min(62, lanes)) : (lanes + wpr - 1) / wpr;
     wpr = (lanes + np - 1) / np;
-    const void *kern = d.pd == 1 ? reinterpret_cast<const void *>(linear_u23_kernel<1>)
-                                 : reinterpret_cast<const void *>(linear_u23_kernel<2>);
+    const void *kern = l23_instance(d)->kern;
     const int row3Begin = rowBegin - rowBegin % 3;
     const int rows = rowEnd - row3Begin;
     constexpr int trip = 6;  // output rows per unrolled trip
@@ -2726,9 +2880,7 @@ hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, i
     int wpr = (lanes + 63) / 64;
     int np = d.np > 0 ? min(d.np, min(64, lanes)) : (lanes + wpr - 1) / wpr;
     wpr = (lanes + np - 1) / np;
-    const void *kern = d.pd == 2   ? reinterpret_cast<const void *>(area_d32_kernel<2>)
-                       : d.pd == 8 ? reinterpret_cast<const void *>(area_d32_kernel<8>)
-                                   : reinterpret_cast<const void *>(area_d32_kernel<4>);
+    const void *kern = a32_instance(d)->kern;
     const int evenBegin = rowBegin & ~1;
     const int rows = rowEnd - evenBegin;
     // bands: ~6 rounds of resident waves, whole trips (8 rows) per band (fresh data, G3: 90 bands
