@@ -574,6 +574,14 @@ int iqo_host_instance_for(int method, unsigned degree, size_t srcW, size_t srcH,
 int iqo_host_instance_count(int family);
 int iqo_host_instance_at(int family, int index, iqo_hip_instance *desc);
 
+/* Host-only: 1 when a default-option call of this shape runs the block-shared Lanczos 2:1 streamer with
+ * the folded vertical pass -- its own quantised Y table has an outer tap that is twice its neighbour
+ * (as u16 values: c2 == 2 c1 in the 10-tap window of Lanczos-3, c1 == 2 c0 in the 12-tap window of
+ * Lanczos-4), so the two pair sums enter one multiply-add as P + 2 P'.  0 for every other table and
+ * every other kernel; < 0 for a shape the plan constructors reject. */
+int iqo_host_lanczos_yfold(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                           size_t pxScale);
+
 /* Fused I420 instantiations: the kernel iqo_hip_resize_yuv420_device runs when it resizes the three
  * planes in one launch.  IQO_YUV420_NONE: plane by plane. */
 enum {

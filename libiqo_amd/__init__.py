@@ -292,6 +292,17 @@ def host_instances(kernel):
     return out
 
 
+def host_lanczos_yfold(method, degree, srcW, srcH, dstW, dstH, pxScale=1):
+    """True when a call of this shape runs the block-shared Lanczos 2:1 streamer with the folded vertical
+    pass (its own Y table has an outer tap twice its neighbour) -- host only, no GPU."""
+    f = lib().iqo_host_lanczos_yfold  # (bound here: an A/B build of an older commit loads without it)
+    f.argtypes = lib().iqo_host_kernel_for.argtypes
+    k = f(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale)
+    if k < 0:
+        raise IqoError("invalid plan request")
+    return bool(k)
+
+
 def host_packed_kernel_for(method, degree, channels, srcW, srcH, dstW, dstH, pxScale=1):
     """Kernel family of a packed plan with `channels` bytes per pixel -- host only, no GPU."""
     k = lib().iqo_host_packed_kernel_for(_METHODS[method], degree, channels, srcW, srcH, dstW, dstH, pxScale)

@@ -3373,6 +3373,19 @@ int iqo_host_instance_for(int method, unsigned degree, size_t srcW, size_t srcH,
     return plan_instance(&h, Layout{srcAlign, dstAlign}, desc);
 }
 
+int iqo_host_lanczos_yfold(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale)
+{
+    if (method < 0 || method > 2)
+        return IQO_HIP_EINVAL;
+    iqo_hip_plan h;  // host half of a plan only: no device memory
+    std::string err;
+    if (!iqo_amd::build_plan(static_cast<iqo_amd::Method>(method), degree, srcW, srcH, dstW, dstH, pxScale, &h.p, &err))
+        return IQO_HIP_EINVAL;
+    if (h.p.kernel != IQO_KERNEL_LANCZOS_STREAM)
+        return 0;
+    return iqo_amd::symb_yfold(lanczos_dev(&h)) ? 1 : 0;
+}
+
 int iqo_host_instance_count(int family) { return iqo_amd::instances(family).count; }
 
 int iqo_host_instance_at(int family, int index, iqo_hip_instance *desc)

@@ -699,6 +699,18 @@ constexpr int symb_edge_bytes(int NY, int NX)
 #else
 #define IQO_SYMB_LDPOL_S "nt"
 #endif
+// Instruction-stream levers of the block-shared streamer (round 8; a variant build with one of them
+// set to 0 times it alone, scripts/build_variant.sh; profiles/r08/steady_ab_levers.txt):
+//   IQO_SYMB_DMA1   one exec-masked DMA form per cache policy (dma_pair_masked) in place of the
+//                   {default, nt} x {whole, partial chunk} ladder of four copies per row
+//   IQO_SYMB_FOLD   the host picks the folded vertical pass where the Y table allows it (symb_yfold)
+#ifndef IQO_SYMB_DMA1
+#define IQO_SYMB_DMA1 1
+#endif
+#ifndef IQO_SYMB_FOLD
+#define IQO_SYMB_FOLD 1
+#endif
+#if !IQO_SYMB_DMA1  // (the ladder's two nontemporal forms)
 __device__ __forceinline__ void dma_row_nt(uint32_t lds, int voff, __amdgpu_buffer_rsrc_t rsrc, int soff)
 {
     uint32_t keep;
@@ -719,6 +731,34 @@ __device__ __forceinline__ void dma_row_masked_nt(uint32_t lds, int voff, __amdg
                  : "=&s"(keep), "=&s"(save)
                  : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff), "s"(mask)
                  : "memory");
+}
+#endif
+
+// The two ring rows of one iteration in one statement, for the lanes of `mask` (all ones except in
+// the wave that owns the row's last, partial chunk): one form serves whole and partial chunks, and
+// exec and M0 are saved and restored once for the pair.  NT: the cache policy of dma_row_nt.
+template <bool NT>
+__device__ __forceinline__ void dma_pair_masked(uint32_t lds0, uint32_t lds1, int voff, __amdgpu_buffer_rsrc_t rsrc,
+                                                int soff0, int soff1, uint64_t mask)
+{
+    uint32_t keep;
+    uint64_t save;
+    if constexpr (NT)
+        asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %8\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %4, %5, %6 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %4, %5, %7 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %0\n\t"
+                     "s_mov_b64 exec, %1"
+                     : "=&s"(keep), "=&s"(save)
+                     : "s"(lds0), "s"(lds1), "v"(voff), "s"(rsrc), "s"(soff0), "s"(soff1), "s"(mask)
+                     : "memory");
+    else
+        asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %8\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %4, %5, %6 offen lds\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %4, %5, %7 offen lds\n\ts_mov_b32 m0, %0\n\t"
+                     "s_mov_b64 exec, %1"
+                     : "=&s"(keep), "=&s"(save)
+                     : "s"(lds0), "s"(lds1), "v"(voff), "s"(rsrc), "s"(soff0), "s"(soff1), "s"(mask)
+                     : "memory");
 }
 
 // X coefficient pair p of the symmetric streamers (pairs 8, 9 of Lanczos-5 live in cy[8], cy[9]:
@@ -971,13 +1011,14 @@ __global__ __launch_bounds__(256, 4) void lanczos_sym_kernel(LanczosArgs a)
 #define IQO_SYMB_EXP 0  // timing experiments in variant builds (wrong output): 1 no vertical MACs,
                         // 2 half the horizontal dots, 3 / 4 dot2 / dot4 in place of the MACs
 #endif
-template <int NY, int NX, int OFFX, int K, int CPW, bool C0ONE, bool LINE>
+template <int NY, int NX, int OFFX, int K, int CPW, bool C0ONE, bool LINE, bool FOLD = false>
 __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, const unsigned bx, const unsigned by,
                                                          const int rpb)
 {
     constexpr int H = NY / 2;                   // symmetric pairs = iterations per window cycle
     static_assert(NY % 2 == 0 && NX % 2 == 0 && (OFFX & 1), "even taps, odd first X column");
     static_assert(K >= 3 && CPW >= 1, "ring depth (the LDS look-ahead needs K >= 3)");
+    static_assert(!FOLD || NY == 10 || NY == 12, "folded Y taps: the 10- and 12-row windows (symb_yfold)");
     // LDS look-ahead: iteration i reads the ring slot of iteration i+1 (its latency hides behind
     // iteration i's arithmetic), so it waits for DMA(i+1): after this wave's DMA(i+1) come the
     // store of iteration i-K+2 and the 2*CPW DMAs + 1 store of each of iterations i+2 .. i+K-2
@@ -1103,6 +1144,15 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
             const int v = (real && col < L.srcW && !(dbg & 2)) ? col : 0x7ff00000;
             const uint32_t d0 = real ? s + 16 + 1024 * c : ldsBase + sinkLds;
             const uint32_t d1 = real ? d0 + rowPitch : d0;
+#if IQO_SYMB_DMA1
+            // one form: the wave's mask is all ones unless this is the row's last, partial chunk
+            // (uniform and the same in every row, so the compiler hoists it out of the row loop)
+            const uint64_t m = (real && c == a.chunks - 1) ? lastMask : ~0ull;
+            if (nt)
+                dma_pair_masked<true>(d0, d1, v, srcR, so0, so1, m);
+            else
+                dma_pair_masked<false>(d0, d1, v, srcR, so0, so1, m);
+#else
             if (real && c == a.chunks - 1 && lastLanes < 64) {  // uniform
                 if (nt) {
                     dma_row_masked_nt(d0, v, srcR, so0, lastMask);
@@ -1118,6 +1168,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
                 dma_row(d0, v, srcR, so0);
                 dma_row(d1, v, srcR, so1);
             }
+#endif
         }
     };
     auto read_iter = [&](int slot, uint4 &r0, uint4 &r1) {
@@ -1234,6 +1285,8 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         *reinterpret_cast<uint4 *>(ring + r * rowPitch) = make_uint4(0u, 0u, 0u, 0u);
     // ring prologue: DMA(0) .. DMA(K-2), each followed by a dropped store, so that from the first
     // iteration on the vm counter sees the steady-state order DMA(j), S(j-K+1)
+    // (issuing these DMAs before or between the window loads and their unpack, one round trip
+    // instead of two, measured no gain: profiles/r08/steady_ab_levers.txt)
 #pragma unroll
     for (int j = 0; j < K - 1; ++j) {
         dma_iter(j, j);
@@ -1270,12 +1323,30 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
 
         // vertical: pair p = slots (2v + p, 2v + NY - 1 - p) mod NY
         uint32_t acc[8];
+        // Folded Y taps (FOLD, chosen by the host from the plan's own table, symb_yfold): where one
+        // outer tap is twice its neighbour, c_{q+1} = 2 c_q, the two pair sums enter as
+        // X = P_q + 2 P_{q+1} -- v_add_lshl_u32 and v_add3_u32 on the packed halves, which stay
+        // below 2^16 (P <= 510, X <= 1530), so nothing carries between them -- and c_q X replaces
+        // c_q P_q + c_{q+1} P_{q+1}: the same sum modulo 2^16 per half, one VALU instruction less per
+        // register.  q = 1 for the 10-row window (1 -2 -4 9 28), q = 0 for the 12-row one (1 2 -3 -5 9 28).
+        constexpr int FQ = NY == 10 ? 1 : 0;      // first pair of the fold
+        constexpr int PREST = FOLD ? FQ + 2 : 1;  // first pair of the plain multiply-add loop
+        auto fold_sum = [&](int c) {
+            const uint32_t twice = (win[(2 * v + FQ + 1) % NY][c] + win[(2 * v + NY - 2 - FQ) % NY][c]) << 1;
+            return win[(2 * v + FQ) % NY][c] + win[(2 * v + NY - 1 - FQ) % NY][c] + twice;
+        };
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const uint32_t p0 = win[(2 * v) % NY][c] + win[(2 * v + NY - 1) % NY][c];
-            acc[c] = C0ONE ? p0 : pk_mul(p0, L.cy[0]);
+            if constexpr (FOLD && FQ == 0) {
+                acc[c] = pk_mul(fold_sum(c), L.cy[0]);
+            } else {
+                const uint32_t p0 = win[(2 * v) % NY][c] + win[(2 * v + NY - 1) % NY][c];
+                acc[c] = C0ONE ? p0 : pk_mul(p0, L.cy[0]);
+                if constexpr (FOLD)
+                    acc[c] = pk_mad(fold_sum(c), L.cy[FQ], acc[c]);
+            }
         }
-#if IQO_SYMB_EXP == 1  // timing experiment (variant build, wrong output): pair sums only, no MACs
+#if IQO_SYMB_EXP == 1 // timing experiment (variant build, wrong output): pair sums only, no MACs
 #pragma unroll
         for (int p = 1; p < H; ++p)
 #pragma unroll
@@ -1299,7 +1370,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
             }
 #else
 #pragma unroll
-        for (int p = 1; p < H; ++p)
+        for (int p = PREST; p < H; ++p)
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const uint32_t pp = win[(2 * v + p) % NY][c] + win[(2 * v + NY - 1 - p) % NY][c];
@@ -1402,7 +1473,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
 
     wait_vmcnt<0>();  // no LDS-DMA may still be writing when the wave (and its LDS) retires
 }
-template <int NY, int NX, int OFFX, int K, int CPW, bool C0ONE, bool LINE>
+template <int NY, int NX, int OFFX, int K, int CPW, bool C0ONE, bool LINE, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NY > 12 ? 2 : NY > 10 ? 3 : 4))) void lanczos_symb_kernel(LanczosArgs a)
 {
     unsigned bx = blockIdx.x, by = blockIdx.y;
@@ -1448,7 +1519,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NY > 12 ? 2
     if (a.l.trace && threadIdx.x < 64)
         t0 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
 #endif
-    lanczos_symb_kernel_body<NY, NX, OFFX, K, CPW, C0ONE, LINE>(a, bx, by, rpb);
+    lanczos_symb_kernel_body<NY, NX, OFFX, K, CPW, C0ONE, LINE, FOLD>(a, bx, by, rpb);
 #ifdef IQO_VARIANT_DEBUG
     if (a.l.trace && threadIdx.x == 0) {
         const uint32_t t1 = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
@@ -2734,24 +2805,34 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
                 ldsBytes = std::max(ldsBytes, 163840 / atoi(ev) - 256);
 #endif
         block = 64 * wpr;
-#define IQO_SYMB_L(NY_, NX_, OX_, K_, CPW_, ONE_)                                                       \
-    (line ? reinterpret_cast<const void *>(lanczos_symb_kernel<NY_, NX_, OX_, K_, CPW_, ONE_, true>)             \
-          : reinterpret_cast<const void *>(lanczos_symb_kernel<NY_, NX_, OX_, K_, CPW_, ONE_, false>))
-#define IQO_SYMB_K(NY_, NX_, OX_, K_, ONE_)                                                             \
-    (cpw == 1 ? IQO_SYMB_L(NY_, NX_, OX_, K_, 1, ONE_) : IQO_SYMB_L(NY_, NX_, OX_, K_, 2, ONE_))
-#define IQO_SYMB(NY_, NX_, OX_, ONE_)                                                                   \
-    (K == 3 ? IQO_SYMB_K(NY_, NX_, OX_, 3, ONE_) : K == 4 ? IQO_SYMB_K(NY_, NX_, OX_, 4, ONE_)          \
-            : IQO_SYMB_K(NY_, NX_, OX_, 5, ONE_))
+#define IQO_SYMB_L(NY_, NX_, OX_, K_, CPW_, ONE_, FOLD_)                                                \
+    (line ? reinterpret_cast<const void *>(lanczos_symb_kernel<NY_, NX_, OX_, K_, CPW_, ONE_, true, FOLD_>)      \
+          : reinterpret_cast<const void *>(lanczos_symb_kernel<NY_, NX_, OX_, K_, CPW_, ONE_, false, FOLD_>))
+#define IQO_SYMB_K(NY_, NX_, OX_, K_, ONE_, FOLD_)                                                      \
+    (cpw == 1 ? IQO_SYMB_L(NY_, NX_, OX_, K_, 1, ONE_, FOLD_) : IQO_SYMB_L(NY_, NX_, OX_, K_, 2, ONE_, FOLD_))
+#define IQO_SYMB_F(NY_, NX_, OX_, ONE_, FOLD_)                                                          \
+    (K == 3 ? IQO_SYMB_K(NY_, NX_, OX_, 3, ONE_, FOLD_) : K == 4 ? IQO_SYMB_K(NY_, NX_, OX_, 4, ONE_, FOLD_) \
+            : IQO_SYMB_K(NY_, NX_, OX_, 5, ONE_, FOLD_))
+#define IQO_SYMB(NY_, NX_, OX_, ONE_) IQO_SYMB_F(NY_, NX_, OX_, ONE_, false)
+#if IQO_SYMB_FOLD
+        // the folded vertical pass where this plan's own Y table has the doubling relation
+        const bool fold = symb_yfold(l);
+#define IQO_SYMB_Y(NY_, NX_, OX_, ONE_) (fold ? IQO_SYMB_F(NY_, NX_, OX_, ONE_, true) : IQO_SYMB(NY_, NX_, OX_, ONE_))
+#else
+#define IQO_SYMB_Y(NY_, NX_, OX_, ONE_) IQO_SYMB(NY_, NX_, OX_, ONE_)
+#endif
         if (l.NY == 10 && one)
-            kern = IQO_SYMB(10, 12, -5, true);
+            kern = IQO_SYMB_Y(10, 12, -5, true);
         else if (l.NY == 10)
-            kern = IQO_SYMB(10, 12, -5, false);
+            kern = IQO_SYMB_Y(10, 12, -5, false);
         else if (l.NY == 12)
-            kern = IQO_SYMB(12, 16, -7, false);  // Lanczos-4 2:1 (3 waves per SIMD: the 12-row window)
+            kern = IQO_SYMB_Y(12, 16, -7, false);  // Lanczos-4 2:1 (3 waves per SIMD: the 12-row window)
         else if (l.NY == 16)
             kern = IQO_SYMB(16, 20, -9, false);  // Lanczos-5 2:1 (2 waves per SIMD: the 16-row window)
         else
             kern = IQO_SYMB(8, 8, -3, false);
+#undef IQO_SYMB_Y
+#undef IQO_SYMB_F
 #undef IQO_SYMB
 #undef IQO_SYMB_K
 #undef IQO_SYMB_L

@@ -384,6 +384,18 @@ struct LanczosDev {
     uint64_t trace;
 #endif
 };
+// Block-shared symmetric streamer: whether the plan's own Y table lets two outer pair sums fold into
+// one multiply-add (kernels.hip lanczos_symb_kernel_body, FOLD): a tap that is twice its neighbour,
+// compared as the u16 values the kernel multiplies by -- cy[2] == 2 cy[1] in the 10-row window
+// (Lanczos-3: 1 -2 -4 9 28), cy[1] == 2 cy[0] in the 12-row one (Lanczos-4: 1 2 -3 -5 9 28).
+// Nothing is taken from the degree; a table without the relation runs the unfolded pass.
+inline bool symb_yfold(const LanczosDev &l)
+{
+    if (l.sym != 1 || (l.NY != 10 && l.NY != 12))
+        return false;
+    const int q = l.NY == 10 ? 1 : 0;
+    return (l.cy[q + 1] & 0xffffu) == ((2u * (l.cy[q] & 0xffffu)) & 0xffffu);
+}
 bool lanczos_stream_supported(int KY, int KX, int NY, int NXP, int offX);
 hipError_t launch_lanczos_stream(const LanczosDev &l, const Io &io, int rowBegin, int rowEnd, int bands,
                                  hipStream_t s);

@@ -11,16 +11,16 @@ mkdir -p variants
 F="-O3 -std=c++17 -fPIC -fno-strict-aliasing -I../include -Icsrc --offload-arch=gfx950 -munsafe-fp-atomics $2"
 OBJS="variants/$1_kernels.o"
 if [ -n "$KERNELS_ONLY" ]; then
-    make -s build/kernels_ratio.o build/kernels_packed.o build/kernels_color.o build/abi.o
+    make -s build/kernels_ratio.o build/kernels_packed.o build/kernels_color.o build/kernels_norm.o build/abi.o
     /opt/rocm/bin/hipcc $F -c csrc/kernels.hip -o variants/$1_kernels.o
-    REST="build/kernels_ratio.o build/kernels_packed.o build/kernels_color.o build/abi.o"
+    REST="build/kernels_ratio.o build/kernels_packed.o build/kernels_color.o build/kernels_norm.o build/abi.o"
 else
-    for k in kernels kernels_ratio kernels_packed kernels_color; do
+    for k in kernels kernels_ratio kernels_packed kernels_color kernels_norm; do
         /opt/rocm/bin/hipcc $F -c csrc/$k.hip -o variants/$1_$k.o &
     done
     /opt/rocm/bin/hipcc $F -ffp-contract=off -c csrc/abi.hip -o variants/$1_abi.o
     wait
-    OBJS="variants/$1_kernels.o variants/$1_kernels_ratio.o variants/$1_kernels_packed.o variants/$1_kernels_color.o variants/$1_abi.o"
+    OBJS="variants/$1_kernels.o variants/$1_kernels_ratio.o variants/$1_kernels_packed.o variants/$1_kernels_color.o variants/$1_kernels_norm.o variants/$1_abi.o"
     REST=""
 fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$1.so build/plan.o build/cpu_generic.o build/resizers.o \
