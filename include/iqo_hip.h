@@ -607,6 +607,88 @@ enum {
  * iqo_hip_plan_yuv420).  < 0 for a request iqo_hip_plan_yuv420 rejects. */
 int iqo_host_yuv420_fused(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH);
 
+/* ---- Crop-and-resize a batch of boxes to ONE output size in one launch (RandomResizedCrop, detector
+ * boxes for a second stage, thumbnails of regions).
+ *
+ * A roi plan fixes method, degree, channels (1, 3 or 4 interleaved bytes per pixel) and dstW x dstH; the
+ * source sizes come with each call.  Box i of a call names frame `frame` of nFrames frames of
+ * frameW x frameH pixels (frame f at dSrc + f*srcFrameSt, rows srcSt bytes apart) and the rectangle
+ * [x, x + w) x [y, y + h) in it.  Output i is, bit for bit, what iqo::{Lanczos,Area,Linear}Resizer
+ * (w, h -> dstW, dstH), pixel scale 1, gives on the cropped image, per channel: the box is the whole image
+ * for border purposes, pixels outside it never contribute, and the kernel never reads a byte outside the
+ * rows of the frames it was given.  With flags bit 0 set, column x of that result is stored at column
+ * dstW - 1 - x (a horizontal flip of the output; the resize itself is unchanged).
+ *
+ *   iqo_hip_resize_rois_device       output i: dstW x dstH pixels of `channels` bytes at dDst + i*dstRoiSt,
+ *                                    rows dstSt bytes apart
+ *   iqo_hip_resize_rois_norm_device  output i: iqo_hip_resize_device_norm's planar float planes (iqo_hip_norm,
+ *                                    order[p] < channels, the same two separately rounded fp32 operations,
+ *                                    fp32 / fp16 / bf16) of those bytes; element (i, p, y, x) at
+ *                                    dDst + i*dstRoiSt + p*dstPlaneSt + y*dstSt + x*elem.  channels == 1
+ *                                    works too (grey -> 3 planes: order {0, 0, 0}).
+ *
+ * Validity follows the plan constructors, box by box.  IQO_HIP_EINVAL: an empty box, a box outside
+ * frameW x frameH, a frame index >= nFrames, an unknown flag bit, a Lanczos box whose top border band is
+ * taller than the output (what iqo_hip_plan_lanczos rejects, e.g. Lanczos-3 with h = 1, dstH = 24); Linear
+ * up-scales above 2x are accepted as everywhere in this library.  IQO_HIP_EUNSUP: a box whose reference
+ * table has more than IQO_HIP_ROI_MAX_TAPS taps on either axis (Lanczos-3 reaches 21:1, Area 128:1); a box
+ * whose one work row -- channels x (w + the tap windows' overhang) 16-bit values plus 8 bytes per Y tap --
+ * exceeds IQO_HIP_ROI_LDS_BYTES (w up to 8000 at 4 channels); more workgroups than one grid addresses
+ * (2^31); frameH*srcSt >= 2^31.  *badRoi (may be null) receives the first offending box, or -1 when an
+ * argument of the call itself is at fault: null pointers, srcSt < frameW*channels, dstSt too small for a
+ * row, dstRoiSt (or dstPlaneSt) too small for an output, and for the norm form everything
+ * iqo_hip_resize_device_norm rejects of a norm and its strides.  On any error nothing is launched and the
+ * destination is untouched.  nRois == 0 returns IQO_HIP_OK after the checks
+ * (dSrc and dDst may then be null).
+ *
+ * Asynchronous on `stream`, no allocation in steady state.  The per-call tables (one X table per distinct
+ * w, one Y table per distinct h, and a record per box) travel in the call: the plan owns two pinned host
+ * arenas with a device arena each, grown when a batch needs more, and a call fills one, copies it with
+ * hipMemcpyAsync on `stream`, launches and records an event; arenas alternate, and before one is refilled
+ * its event is synchronised, so the host blocks only when it is two calls ahead of the device.  The plan
+ * keeps a host cache of axis tables by (axis, length), least recently used dropped beyond a byte cap:
+ * repeated lengths cost a memcpy.  Because the tables are per call, a CAPTURING stream gets
+ * IQO_HIP_EUNSUP.  A roi plan is NOT thread-safe: one call at a time per plan. */
+#define IQO_HIP_ROI_MAX_TAPS 128
+#define IQO_HIP_ROI_LDS_BYTES 65536
+typedef struct { int frame, x, y, w, h, flags; } iqo_hip_roi;   /* flags bit 0: mirror the output columns */
+enum { IQO_ROI_FLIP = 1 };
+typedef struct iqo_hip_roi_plan iqo_hip_roi_plan;
+int iqo_hip_plan_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, int device,
+                      iqo_hip_roi_plan **out);
+void iqo_hip_roi_plan_destroy(iqo_hip_roi_plan *plan);
+int iqo_hip_resize_rois_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                               size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt,
+                               const uint8_t *dSrc, size_t dstSt, size_t dstRoiSt, uint8_t *dDst, void *stream,
+                               int *badRoi);
+int iqo_hip_resize_rois_norm_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                    size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt,
+                                    const uint8_t *dSrc, const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt,
+                                    size_t dstRoiSt, void *dDst, void *stream, int *badRoi);
+
+/* Host-only CPU twins of the two calls above (host pointers, no stream, no device): they assemble the same
+ * arena and walk it in plain C++ with the kernel's integer formulas, so the device calls must equal them
+ * byte for byte.  Same status codes and *badRoi. */
+int iqo_host_resize_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                         const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                         size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstRoiSt, uint8_t *dst,
+                         int *badRoi);
+int iqo_host_resize_rois_norm(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                              const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                              size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, size_t dstSt,
+                              size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi);
+/* Host-only: what the arena of such a call holds (tightly packed frames: srcSt = frameW*channels). */
+typedef struct {
+    size_t arenaBytes;    /* header + one record per box + every distinct table once */
+    int xTables, yTables; /* distinct X tables (box widths) and Y tables (box heights) */
+    unsigned workgroups;  /* the launch's grid */
+    size_t ldsBytes;      /* its dynamic LDS: the largest workgroup's */
+    size_t recordBytes;   /* bytes of one box record */
+} iqo_hip_roi_arena_stats;
+int iqo_host_roi_arena_stats(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                             const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                             iqo_hip_roi_arena_stats *stats, int *badRoi);
+
 /* Drop-in classes (iqo::LanczosResizer, AreaResizer, LinearResizer): how many objects this process constructed on the
  * HIP backend, and on the CPU backend (no gfx950 device) plus the resize() calls of HIP objects that fell back to the
  * CPU (a device failure, or a call the HIP path rejected).  IQO_REQUIRE_HIP=1 makes any CPU use abort;

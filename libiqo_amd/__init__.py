@@ -18,7 +18,8 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "CS_BT601_LIMITED", "CS_BT601_FULL", "CS_BT709_LIMITED", "CS_BT709_FULL", "COLOR_STANDARDS", "RGB_ORDERS",
            "host_yuv_to_rgb", "yuv_rgb_workspace_bytes", "CHROMA_REPLICATE", "CHROMA_FULL", "CHROMA_MODES",
            "host_chroma_full_kernel", "host_rgb_to_yuv", "host_rgb_to_yuv420", "rgb_yuv_workspace_bytes",
-           "SOURCE_ORDERS"]
+           "SOURCE_ORDERS", "RoiResizer", "Roi", "RoiArenaStats", "host_resize_rois", "host_roi_arena_stats",
+           "ROI_MAX_TAPS", "ROI_LDS_BYTES"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -84,6 +85,21 @@ SOURCE_ORDERS = {"rgb": (0, 1, 2), "bgr": (2, 1, 0)}
 # IQO_CHROMA_*: chroma resized to half the output and replicated 2 x 2, or filtered to the full output grid
 CHROMA_REPLICATE, CHROMA_FULL = 0, 1
 CHROMA_MODES = {"replicate": CHROMA_REPLICATE, "full": CHROMA_FULL}
+
+
+class Roi(ctypes.Structure):
+    """iqo_hip_roi: a rectangle of one frame; flags bit 0 mirrors the output columns."""
+    _fields_ = [("frame", ctypes.c_int), ("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_int),
+                ("h", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+class RoiArenaStats(ctypes.Structure):
+    """iqo_hip_roi_arena_stats"""
+    _fields_ = [("arenaBytes", _c_sz), ("xTables", ctypes.c_int), ("yTables", ctypes.c_int),
+                ("workgroups", ctypes.c_uint), ("ldsBytes", _c_sz), ("recordBytes", _c_sz)]
+
+
+ROI_MAX_TAPS, ROI_LDS_BYTES = 128, 65536  # IQO_HIP_ROI_MAX_TAPS, IQO_HIP_ROI_LDS_BYTES
 
 
 class IpcHandle(ctypes.Structure):
@@ -187,6 +203,19 @@ def lib():
     L.iqo_hip_resize_rgb_yuv420_device.argtypes = to_yuv + [_vp, _vp, _vp, _vp, _c_sz, _vp]
     L.iqo_host_rgb_to_yuv.argtypes = [ctypes.c_int, _c_sz, _vp, _vp, _vp, _vp]
     L.iqo_host_rgb_to_yuv420.argtypes = [ctypes.c_int, _c_sz, _c_sz, _vp, _vp, _vp, _vp]
+    pi = ctypes.POINTER(ctypes.c_int)
+    roi_src = [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _vp]
+    roi_host = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz]
+    L.iqo_hip_plan_rois.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz, ctypes.c_int, pp]
+    L.iqo_hip_roi_plan_destroy.argtypes = [_vp]
+    L.iqo_hip_roi_plan_destroy.restype = None
+    L.iqo_hip_resize_rois_device.argtypes = [_vp] + roi_src + [_c_sz, _c_sz, _vp, _vp, pi]
+    L.iqo_hip_resize_rois_norm_device.argtypes = [_vp] + roi_src + [ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz, _vp,
+                                                                    _vp, pi]
+    L.iqo_host_resize_rois.argtypes = roi_host + roi_src + [_c_sz, _c_sz, _vp, pi]
+    L.iqo_host_resize_rois_norm.argtypes = roi_host + roi_src + [ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz, _vp, pi]
+    L.iqo_host_roi_arena_stats.argtypes = roi_host + [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz,
+                                                      ctypes.POINTER(RoiArenaStats), pi]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -405,6 +434,95 @@ def host_rgb_to_yuv420(standard, rgb):
     _check(lib().iqo_host_rgb_to_yuv420(_standard(standard), w, h, _ptr(rgb), _ptr(y), _ptr(u), _ptr(v)),
            "host_rgb_to_yuv420")
     return y, u, v
+
+
+def _roi_array(boxes):
+    """(frame, x, y, w, h[, flip]) tuples -> a ctypes array of iqo_hip_roi."""
+    arr = (Roi * max(1, len(boxes)))()
+    for i, b in enumerate(boxes):
+        if len(b) not in (5, 6):
+            raise IqoError("box %d: expected (frame, x, y, w, h) or (frame, x, y, w, h, flip)" % i)
+        arr[i] = Roi(int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(b[4]), int(b[5]) if len(b) == 6 else 0)
+    return arr
+
+
+def _check_rois(rc, bad, boxes, what):
+    if rc != 0:
+        where = " (box %d: %s)" % (bad.value, tuple(boxes[bad.value])) if 0 <= bad.value < len(boxes) else ""
+        err = IqoError("%s: %s (%d)%s" % (what, lib().iqo_hip_strerror(rc).decode(), rc, where))
+        err.status, err.bad_roi = rc, bad.value  # IQO_HIP_E*, the first offending box (-1: the call itself)
+        raise err
+
+
+def _norm_of(C, scale, bias, order, code):
+    order = tuple(range(C)) if order is None else tuple(int(c) for c in order)
+    scale, bias = tuple(float(v) for v in scale), tuple(float(v) for v in bias)
+    planes = len(order)
+    if not 1 <= planes <= 4 or len(scale) != planes or len(bias) != planes:
+        raise IqoError("order, scale and bias must have the same length, 1..4 (one entry per output plane)")
+    n = Norm(code, planes)
+    for i in range(planes):
+        n.order[i], n.scale[i], n.bias[i] = order[i], scale[i], bias[i]
+    return n, planes
+
+
+def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=None, dtype=None, order=None, out=None):
+    """iqo_host_resize_rois / iqo_host_resize_rois_norm on numpy arrays (no GPU): the CPU twin of
+    RoiResizer.resize_rois and, with scale / bias, of resize_rois_normalized.  src: uint8 [F, H, W] or
+    [F, H, W, C] (row and frame strides free, pixel bytes contiguous).  Returns uint8 [N, dstH, dstW(, C)], or
+    [N, planes, dstH, dstW] of dtype "float32", "float16" (numpy arrays of that type) or "bfloat16" (uint16 bit
+    patterns)."""
+    import numpy as np
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    if src.dtype != np.uint8 or src.ndim not in (3, 4):
+        raise IqoError("expected a uint8 array [F, H, W] or [F, H, W, C]")
+    C = 1 if src.ndim == 3 else src.shape[3]
+    if src.strides[2] != C or (src.ndim == 4 and src.strides[3] != 1) or min(src.strides[0], src.strides[1]) < 1:
+        src = np.ascontiguousarray(src)
+    F, H, W = src.shape[:3]
+    boxes = [tuple(b) for b in boxes]
+    arr, bad, N = _roi_array(boxes), ctypes.c_int(-1), len(boxes)
+    head = (m, degree, C, dstW, dstH, N, arr, F, W, H, src.strides[1], src.strides[0], src.ctypes.data)
+    if scale is None:
+        shape = (N, dstH, dstW) if src.ndim == 3 else (N, dstH, dstW, C)
+        if out is None:
+            out = np.zeros(shape, np.uint8)
+        if out.dtype != np.uint8 or out.shape != shape or (N and (out.strides[2] != C or
+                                                                  (src.ndim == 4 and out.strides[3] != 1))):
+            raise IqoError("out must be a uint8 array %s with contiguous pixels" % (shape,))
+        if N == 0:  # (numpy gives an empty array no usable strides)
+            return out
+        rc = lib().iqo_host_resize_rois(*head, out.strides[1], out.strides[0], out.ctypes.data, ctypes.byref(bad))
+        _check_rois(rc, bad, boxes, "host_resize_rois")
+        return out
+    dtype = dtype or "float32"
+    codes = {"float32": (OUT_F32, np.float32), "float16": (OUT_F16, np.float16), "bfloat16": (OUT_BF16, np.uint16)}
+    n, planes = _norm_of(C, scale, bias, order, codes[dtype][0])
+    shape = (N, planes, dstH, dstW)
+    if out is None:
+        out = np.zeros(shape, codes[dtype][1])
+    e = out.itemsize
+    if out.dtype != codes[dtype][1] or out.shape != shape or (N and out.strides[3] != e):
+        raise IqoError("out must be a %s array %s with unit column stride" % (codes[dtype][1].__name__, shape))
+    if N == 0:
+        return out
+    rc = lib().iqo_host_resize_rois_norm(*head, ctypes.byref(n), out.strides[2], out.strides[1], out.strides[0],
+                                         out.ctypes.data, ctypes.byref(bad))
+    _check_rois(rc, bad, boxes, "host_resize_rois")
+    return out
+
+
+def host_roi_arena_stats(method, degree, dstW, dstH, channels, boxes, nFrames, frameW, frameH):
+    """iqo_host_roi_arena_stats: {"arena_bytes", "x_tables", "y_tables", "workgroups", "lds_bytes", "record_bytes"}
+    of the call's arena, without a GPU."""
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    boxes = [tuple(b) for b in boxes]
+    st, bad = RoiArenaStats(), ctypes.c_int(-1)
+    rc = lib().iqo_host_roi_arena_stats(m, degree, channels, dstW, dstH, len(boxes), _roi_array(boxes), nFrames, frameW,
+                                        frameH, ctypes.byref(st), ctypes.byref(bad))
+    _check_rois(rc, bad, boxes, "host_roi_arena_stats")
+    return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
+            "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
 
 
 def _ptr(obj):
@@ -765,6 +883,99 @@ def make_resizer(method, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None,
     if method == "linear":
         return LinearResizer(srcW, srcH, dstW, dstH, device, channels)
     raise ValueError(method)
+
+
+class RoiResizer:
+    """Crop-and-resize a batch of boxes of device-resident frames to one dstW x dstH in one launch
+    (iqo_hip_plan_rois).  method: "lanczos" / "area" / "linear" (or 0 / 1 / 2); channels 1, 3 or 4.  Every output is
+    bit for bit the {Lanczos,Area,Linear}Resizer result on the cropped image.  Calls are asynchronous on the stream;
+    one call at a time per object (not thread-safe); not capturable into a graph."""
+
+    def __init__(self, method, degree, dstW, dstH, channels=1, device=None):
+        self.method = _METHODS[method] if isinstance(method, str) else int(method)
+        self.degree, self.dstW, self.dstH, self.channels = int(degree), int(dstW), int(dstH), int(channels)
+        self.device = 0 if device is None else int(device)
+        self._plan = _vp()
+        _check(lib().iqo_hip_plan_rois(self.method, self.degree, self.channels, self.dstW, self.dstH, self.device,
+                                       ctypes.byref(self._plan)), "RoiResizer")
+
+    def __del__(self):
+        p = getattr(self, "_plan", None)
+        if p and _lib is not None:
+            _lib.iqo_hip_roi_plan_destroy(p)
+            self._plan = _vp()
+
+    def _source(self, src):
+        """src [F, H, W] (channels 1) or [F, H, W, C] uint8 on the device, read where it lies when the pixel bytes
+        are contiguous and the row and frame strides are positive (.contiguous() otherwise)."""
+        import torch
+        C = self.channels
+        ok = src.dtype == torch.uint8 and src.is_cuda and (src.dim() == 4 and src.shape[3] == C
+                                                           or src.dim() == 3 and C == 1)
+        if not ok:
+            raise IqoError("expected a uint8 device tensor [F, H, W, %d]%s" % (C, " or [F, H, W]" if C == 1 else ""))
+        if src.stride(2) != C or (src.dim() == 4 and src.stride(3) != 1) or min(src.stride(0), src.stride(1)) < 1:
+            src = src.contiguous()
+        return src
+
+    def resize_rois(self, src, boxes, out=None, stream=None):
+        """boxes: a sequence of (frame, x, y, w, h) or (frame, x, y, w, h, flip).  Returns / fills out
+        [N, dstH, dstW] (3-dimensional src) or [N, dstH, dstW, C]: a uint8 tensor on src's device with contiguous
+        pixels and non-overlapping rows and outputs."""
+        import torch
+        s = self._source(src)
+        C, boxes = self.channels, [tuple(b) for b in boxes]
+        N = len(boxes)
+        shape = (N, self.dstH, self.dstW) if s.dim() == 3 else (N, self.dstH, self.dstW, C)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=s.device)
+        if (out.dtype != torch.uint8 or out.device != s.device or tuple(out.shape) != shape or out.stride(2) != C
+                or (out.dim() == 4 and out.stride(3) != 1) or out.stride(1) < self.dstW * C
+                or (N > 1 and out.stride(0) < self.dstH * out.stride(1))):
+            raise IqoError("out must be a uint8 tensor %s on %s with contiguous pixels and non-overlapping rows and "
+                           "outputs" % (shape, s.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        bad = ctypes.c_int(-1)
+        rc = lib().iqo_hip_resize_rois_device(self._plan, N, _roi_array(boxes), s.shape[0], s.shape[2], s.shape[1],
+                                              s.stride(1), s.stride(0), _ptr(s), out.stride(1), out.stride(0),
+                                              _ptr(out), _stream_ptr(stream), ctypes.byref(bad))
+        _check_rois(rc, bad, boxes, "resize_rois")
+        return out
+
+    def resize_rois_normalized(self, src, boxes, scale, bias, dtype=None, order=None, out=None, stream=None):
+        """As resize_rois, stored as the normalised planar tensor a model takes: [N, planes, dstH, dstW] of `dtype`
+        (float32, float16 or bfloat16), plane p = float32(byte of channel order[p]) * scale[p] + bias[p], each
+        operation rounded to float32, then rounded to `dtype`.  planes = len(order), or C with the identity order
+        (channels 1: order (0, 0, 0) gives grey -> 3 planes).  `out` may be a strided view with unit column stride
+        and non-overlapping rows, planes and outputs."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32
+        codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+        if dtype not in codes:
+            raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        s = self._source(src)
+        boxes = [tuple(b) for b in boxes]
+        N = len(boxes)
+        n, planes = _norm_of(self.channels, scale, bias, order, codes[dtype])
+        shape = (N, planes, self.dstH, self.dstW)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=s.device)
+        if (out.dtype != dtype or out.device != s.device or tuple(out.shape) != shape or out.stride(3) != 1
+                or out.stride(2) < self.dstW or out.stride(1) < self.dstH * out.stride(2)
+                or (N > 1 and out.stride(0) < planes * out.stride(1))):
+            raise IqoError("out must be a %s tensor %s on %s with unit column stride and non-overlapping rows, planes "
+                           "and outputs" % (dtype, shape, s.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        e, bad = out.element_size(), ctypes.c_int(-1)
+        rc = lib().iqo_hip_resize_rois_norm_device(self._plan, N, _roi_array(boxes), s.shape[0], s.shape[2], s.shape[1],
+                                                   s.stride(1), s.stride(0), _ptr(s), ctypes.byref(n),
+                                                   out.stride(2) * e, out.stride(1) * e, out.stride(0) * e, _ptr(out),
+                                                   _stream_ptr(stream), ctypes.byref(bad))
+        _check_rois(rc, bad, boxes, "resize_rois_normalized")
+        return out
 
 
 class _YuvToRgb:

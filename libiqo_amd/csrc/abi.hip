@@ -24,6 +24,7 @@
 
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "roi.hpp"
 
 using iqo_amd::AxisPlan;
 using iqo_amd::CoordInfo;
@@ -3456,6 +3457,306 @@ int iqo_host_yuv420_fused(int method, unsigned degree, size_t srcW, size_t srcH,
     if (k == IQO_KERNEL_LINEAR_UP2)
         return iqo_amd::yuv420_fused(linear_dev(&hy), linear_dev(&hc)).label;
     return IQO_YUV420_NONE;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- batched crop-and-resize (roi.hpp)
+
+// Two arenas per plan, used alternately: pinned host words, their device copy and the event recorded
+// after the launch that reads the device copy.
+struct iqo_hip_roi_plan {
+    iqo_hip_roi_plan(iqo_amd::Method m, unsigned degree, int channels_, int dstW, int dstH, int device_)
+        : cache(m, degree, dstW, dstH), channels(channels_), device(device_)
+    {
+    }
+    iqo_amd::RoiTableCache cache;
+    iqo_amd::RoiLayout layout;
+    int channels, device;
+    struct Arena {
+        uint32_t *h = nullptr, *d = nullptr;
+        size_t capWords = 0;
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } arena[2];
+    int next = 0;
+};
+
+namespace {
+
+static_assert(sizeof(iqo_hip_roi) == sizeof(iqo_amd::RoiBox), "iqo_hip_roi is roi.hpp RoiBox");
+static_assert(IQO_HIP_ROI_MAX_TAPS == iqo_amd::kRoiMaxTaps && IQO_HIP_ROI_LDS_BYTES == iqo_amd::kRoiLdsMax,
+              "iqo_hip.h roi limits are roi.hpp's");
+
+int roi_status(int st) { return st == iqo_amd::kRoiOk ? IQO_HIP_OK : st == iqo_amd::kRoiInvalid ? IQO_HIP_EINVAL : IQO_HIP_EUNSUP; }
+
+// The destination checks of both forms (norm == nullptr: interleaved bytes); fills *rn for the twin.
+int roi_check_dst(int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_norm *norm, bool isNorm,
+                  size_t dstSt, size_t planeSt, size_t dstRoiSt, const void *dst, iqo_amd::RoiNorm *rn)
+{
+    *rn = iqo_amd::RoiNorm();
+    if ((!dst && nRois) || !dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20))
+        return IQO_HIP_EINVAL;
+    if (!isNorm) {
+        if (dstSt < dstW * static_cast<size_t>(channels) || (nRois > 1 && dstRoiSt / dstH < dstSt))
+            return IQO_HIP_EINVAL;
+        return IQO_HIP_OK;
+    }
+    if (!norm || (norm->dtype != IQO_OUT_F32 && norm->dtype != IQO_OUT_F16 && norm->dtype != IQO_OUT_BF16) ||
+        norm->planes < 1 || norm->planes > 4)
+        return IQO_HIP_EINVAL;
+    for (int i = 0; i < norm->planes; ++i)
+        if (norm->order[i] < 0 || norm->order[i] >= channels || !std::isfinite(norm->scale[i]) ||
+            !std::isfinite(norm->bias[i]))
+            return IQO_HIP_EINVAL;
+    const size_t elem = norm->dtype == IQO_OUT_F32 ? 4 : 2, planes = static_cast<size_t>(norm->planes);
+    if (reinterpret_cast<uintptr_t>(dst) % elem || dstSt % elem || planeSt % elem || dstRoiSt % elem)
+        return IQO_HIP_EINVAL;
+    if (dstSt < dstW * elem || planeSt / dstH < dstSt || (nRois > 1 && dstRoiSt / planes < planeSt) ||
+        planeSt >= (size_t(1) << 31))
+        return IQO_HIP_EINVAL;
+    rn->dtype = norm->dtype;
+    rn->planes = norm->planes;
+    for (int i = 0; i < norm->planes; ++i) {
+        rn->order[i] = norm->order[i];
+        rn->scale[i] = norm->scale[i];
+        rn->bias[i] = norm->bias[i];
+    }
+    return IQO_HIP_OK;
+}
+
+int host_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_roi *rois,
+              size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
+              const iqo_hip_norm *norm, bool isNorm, size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst,
+              iqo_hip_roi_arena_stats *stats, int *badRoi)
+{
+    int bad = -1;
+    if (badRoi)
+        *badRoi = -1;
+    if (method < 0 || method > 2)
+        return IQO_HIP_EINVAL;
+    if (channels != 1 && channels != 3 && channels != 4)
+        return IQO_HIP_EUNSUP;
+    iqo_amd::RoiNorm rn;
+    if (!stats) {
+        if (!src && nRois)
+            return IQO_HIP_EINVAL;
+        const int rc = roi_check_dst(channels, dstW, dstH, nRois, norm, isNorm, dstSt, planeSt, dstRoiSt, dst, &rn);
+        if (rc)
+            return rc;
+    } else if (!dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20)) {
+        return IQO_HIP_EINVAL;
+    }
+    iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
+    iqo_amd::RoiLayout l;
+    const int st = iqo_amd::roi_layout(&cache, channels, nRois, reinterpret_cast<const iqo_amd::RoiBox *>(rois), nFrames,
+                                       frameW, frameH, srcSt, srcFrameSt, &l, &bad);
+    if (st != iqo_amd::kRoiOk) {
+        if (badRoi)
+            *badRoi = bad;
+        return roi_status(st);
+    }
+    if (stats) {
+        stats->arenaBytes = l.words * 4;
+        stats->xTables = l.nXTables;
+        stats->yTables = l.nYTables;
+        stats->workgroups = l.groups;
+        stats->ldsBytes = l.ldsBytes;
+        stats->recordBytes = iqo_amd::kRoiRecWords * 4;
+        return IQO_HIP_OK;
+    }
+    std::vector<uint32_t> arena(l.words);
+    iqo_amd::roi_fill(cache, l, frameW, arena.data());
+    iqo_amd::roi_walk(arena.data(), src, srcSt, dstSt, planeSt, dstRoiSt, dst, rn);
+    return IQO_HIP_OK;
+}
+
+void roi_arena_free(iqo_hip_roi_plan::Arena *a)
+{
+    if (a->h)
+        (void)hipHostFree(a->h);
+    if (a->d)
+        (void)hipFree(a->d);
+    a->h = a->d = nullptr;
+    a->capWords = 0;
+}
+
+int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+             size_t srcSt, size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, bool isNorm, size_t dstSt,
+             size_t planeSt, size_t dstRoiSt, void *dst, hipStream_t s, int *badRoi)
+{
+    if (badRoi)
+        *badRoi = -1;
+    if (!h || (!src && nRois))
+        return IQO_HIP_EINVAL;
+    iqo_amd::RoiNorm rn;
+    const int rc = roi_check_dst(h->channels, static_cast<size_t>(h->cache.dstW()), static_cast<size_t>(h->cache.dstH()),
+                                 nRois, norm, isNorm, dstSt, planeSt, dstRoiSt, dst, &rn);
+    if (rc)
+        return rc;
+    int bad = -1;
+    const int st = iqo_amd::roi_layout(&h->cache, h->channels, nRois, reinterpret_cast<const iqo_amd::RoiBox *>(rois),
+                                       nFrames, frameW, frameH, srcSt, srcFrameSt, &h->layout, &bad);
+    if (st != iqo_amd::kRoiOk) {
+        if (badRoi)
+            *badRoi = bad;
+        return roi_status(st);
+    }
+    const iqo_amd::RoiLayout &l = h->layout;
+    if (nRois == 0)
+        return IQO_HIP_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess)
+        return IQO_HIP_EHIP;
+    if (cap != hipStreamCaptureStatusNone)
+        return IQO_HIP_EUNSUP;  // the tables are per call: nothing to replay
+    iqo_hip_roi_plan::Arena &a = h->arena[h->next];
+    if (a.pending) {  // the launch that last read this arena
+        if (hipEventSynchronize(a.ev) != hipSuccess)
+            return IQO_HIP_EHIP;
+        a.pending = false;
+    }
+    if (a.capWords < l.words) {
+        roi_arena_free(&a);
+        const size_t cap2 = std::max(l.words + l.words / 2, size_t(1) << 16);
+        if (hipHostMalloc(reinterpret_cast<void **>(&a.h), cap2 * 4, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&a.d), cap2 * 4) != hipSuccess) {
+            roi_arena_free(&a);
+            return IQO_HIP_ENOMEM;
+        }
+        a.capWords = cap2;
+    }
+    iqo_amd::roi_fill(h->cache, l, frameW, a.h);
+    if (hipMemcpyAsync(a.d, a.h, l.words * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return IQO_HIP_EHIP;
+    a.pending = true;  // from here on the arena is in flight, whatever follows
+    iqo_amd::RoiDev d;
+    d.arena = a.d;
+    d.src = src;
+    d.dst = static_cast<uint8_t *>(dst);
+    d.srcSt = static_cast<int64_t>(srcSt);
+    d.dstSt = static_cast<int64_t>(dstSt);
+    d.dstRoiSt = static_cast<int64_t>(dstRoiSt);
+    d.lanczos = h->cache.method() == iqo_amd::kLanczos;
+    d.channels = h->channels;
+    d.groups = l.groups;
+    d.ldsBytes = l.ldsBytes;
+    iqo_amd::NormDev n;
+    if (isNorm) {
+        n.dtype = rn.dtype;
+        n.planes = rn.planes;
+        n.planeSt = static_cast<int>(planeSt);
+        for (int i = 0; i < 4; ++i) {
+            n.order[i] = rn.order[i];
+            n.scale[i] = rn.scale[i];
+            n.bias[i] = rn.bias[i];
+        }
+    }
+    const hipError_t e = iqo_amd::launch_roi(d, isNorm ? &n : nullptr, s);
+    const hipError_t e2 = hipEventRecord(a.ev, s);
+    h->next ^= 1;
+    if (e == hipErrorInvalidValue)
+        return IQO_HIP_EINVAL;
+    return e == hipSuccess && e2 == hipSuccess ? IQO_HIP_OK : IQO_HIP_EHIP;
+}
+
+} // namespace
+
+extern "C" {
+
+int iqo_hip_plan_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, int device,
+                      iqo_hip_roi_plan **out)
+{
+    if (!out)
+        return IQO_HIP_EINVAL;
+    *out = nullptr;
+    if (method < 0 || method > 2 || (method == IQO_METHOD_LANCZOS && degree < 1) || !dstW || !dstH ||
+        dstW > (1u << 20) || dstH > (1u << 20))
+        return IQO_HIP_EINVAL;
+    if (channels != 1 && channels != 3 && channels != 4)
+        return IQO_HIP_EUNSUP;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || !is_gfx950(device))
+        return IQO_HIP_ENODEV;
+    DeviceGuard guard(device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    iqo_hip_roi_plan *h = new (std::nothrow) iqo_hip_roi_plan(static_cast<iqo_amd::Method>(method), degree, channels,
+                                                              static_cast<int>(dstW), static_cast<int>(dstH), device);
+    if (!h)
+        return IQO_HIP_ENOMEM;
+    for (auto &a : h->arena)
+        if (hipEventCreateWithFlags(&a.ev, hipEventDisableTiming) != hipSuccess) {
+            iqo_hip_roi_plan_destroy(h);
+            return IQO_HIP_EHIP;
+        }
+    *out = h;
+    return IQO_HIP_OK;
+}
+
+void iqo_hip_roi_plan_destroy(iqo_hip_roi_plan *h)
+{
+    if (!h)
+        return;
+    {
+        DeviceGuard guard(h->device);
+        for (auto &a : h->arena) {
+            if (a.pending)
+                (void)hipEventSynchronize(a.ev);
+            if (a.ev)
+                (void)hipEventDestroy(a.ev);
+            roi_arena_free(&a);
+        }
+    }
+    delete h;
+}
+
+int iqo_hip_resize_rois_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                               size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrc,
+                               size_t dstSt, size_t dstRoiSt, uint8_t *dDst, void *stream, int *badRoi)
+{
+    return run_rois(plan, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, dSrc, nullptr, false, dstSt, 0,
+                    dstRoiSt, dDst, static_cast<hipStream_t>(stream), badRoi);
+}
+
+int iqo_hip_resize_rois_norm_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                    size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrc,
+                                    const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt,
+                                    void *dDst, void *stream, int *badRoi)
+{
+    return run_rois(plan, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, dSrc, norm, true, dstSt, dstPlaneSt,
+                    dstRoiSt, dDst, static_cast<hipStream_t>(stream), badRoi);
+}
+
+int iqo_host_resize_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                         const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                         size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstRoiSt, uint8_t *dst, int *badRoi)
+{
+    return host_rois(method, degree, channels, dstW, dstH, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, src,
+                     nullptr, false, dstSt, 0, dstRoiSt, dst, nullptr, badRoi);
+}
+
+int iqo_host_resize_rois_norm(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                              const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                              size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, size_t dstSt,
+                              size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi)
+{
+    return host_rois(method, degree, channels, dstW, dstH, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, src,
+                     norm, true, dstSt, dstPlaneSt, dstRoiSt, dst, nullptr, badRoi);
+}
+
+int iqo_host_roi_arena_stats(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                             const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                             iqo_hip_roi_arena_stats *stats, int *badRoi)
+{
+    if (!stats)
+        return IQO_HIP_EINVAL;
+    const size_t C = channels > 0 ? static_cast<size_t>(channels) : 1;
+    return host_rois(method, degree, channels, dstW, dstH, nRois, rois, nFrames, frameW, frameH, frameW * C,
+                     frameW * C * frameH, nullptr, nullptr, false, 0, 0, 0, nullptr, stats, badRoi);
 }
 
 } // extern "C"

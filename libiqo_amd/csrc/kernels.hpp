@@ -100,6 +100,22 @@ hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const I
 hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io, const NormDev &n, int rowBegin,
                                    int rowEnd, hipStream_t s);
 
+// --- batched crop-and-resize (kernels_roi.hip roi_kernel): one launch over the workgroups of a call's
+// arena (roi.hpp), which lies in device memory at `arena` and names every box, its tables and its
+// workgroups.  dst: interleaved bytes, rows dstSt and outputs dstRoiSt bytes apart; with `norm` the float
+// planes of NormDev (rows dstSt, planes norm->planeSt, outputs dstRoiSt bytes apart).
+struct RoiDev {
+    const uint32_t *arena;
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t srcSt, dstSt, dstRoiSt;
+    bool lanczos;
+    int channels;                // 1, 3 or 4
+    unsigned groups;             // the arena's workgroup count
+    size_t ldsBytes;             // the largest workgroup's LDS (roi.hpp RoiLayout)
+};
+hipError_t launch_roi(const RoiDev &d, const NormDev *norm, hipStream_t s);
+
 // --- YUV 4:2:0 planes -> RGB (kernels_color.hip): the second pass of the NV12 / I420 "resize to RGB"
 // entries.  Reads resized planes from a workspace (Y dstW x dstH; chroma cw x ch, replicated to the
 // output grid: pixel (y, x) takes sample (min(y >> 1, ch - 1), min(x >> 1, cw - 1))), applies the

@@ -759,23 +759,23 @@ struct Window {
     bool border = false;
 };
 
-Window axis_window(const Plan &p, const AxisPlan &ax, int i, bool isX)
+Window axis_window(Method method, const AxisPlan &ax, int i, bool isX)
 {
     const CoordInfo &ci = ax.coord[static_cast<size_t>(i)];
     const int len = ax.srcLen;
     Window w;
     w.start = ci.srcO;
     if (ci.kind == kIdentity) {
-        w.c.assign(1, p.method == kLanczos ? (isX ? 1 << 14 : 64) : (isX ? 1 << 15 : 256));
+        w.c.assign(1, method == kLanczos ? (isX ? 1 << 14 : 64) : (isX ? 1 << 15 : 256));
         return w;
     }
-    if (p.method == kLinear && ci.kind != kMain) {  // replicate the first / last source pixel
+    if (method == kLinear && ci.kind != kMain) {  // replicate the first / last source pixel
         w.start = ci.kind == kBorderLo ? 0 : len - 1;
         w.c.assign(1, isX ? 1 << 15 : 256);
         return w;
     }
     w.c.assign(ax.table.begin() + ci.tabOff, ax.table.begin() + ci.tabOff + ax.taps);
-    if (p.method == kLanczos && ci.kind != kMain) {
+    if (method == kLanczos && ci.kind != kMain) {
         for (int k = 0; k < ax.taps; ++k)
             if (w.start + k < 0 || w.start + k >= len)
                 w.c[static_cast<size_t>(k)] = 0;
@@ -785,7 +785,64 @@ Window axis_window(const Plan &p, const AxisPlan &ax, int i, bool isX)
     return w;
 }
 
+Window axis_window(const Plan &p, const AxisPlan &ax, int i, bool isX) { return axis_window(p.method, ax, i, isX); }
+
 } // namespace
+
+bool build_axis(Method m, unsigned degree, size_t srcLen, size_t dstLen, bool isX, AxisPlan *a, std::string *err)
+{
+    *a = AxisPlan();
+    auto fail = [&](const char *what) {
+        if (err)
+            *err = what;
+        return false;
+    };
+    if (!srcLen || !dstLen)
+        return fail("zero-sized image");
+    if (srcLen > (1u << 30) || dstLen > (1u << 30))
+        return fail("image dimension too large");
+    a->srcLen = static_cast<int>(srcLen);
+    a->dstLen = static_cast<int>(dstLen);
+    switch (m) {  // the biases of build_tables, the coordinate maps of build_plan
+    case kLanczos:
+        if (degree < 1)
+            return fail("lanczos degree must be >= 1");
+        tables_lanczos(degree, srcLen, dstLen, 1, isX ? 1 << 14 : 1 << 6, a);
+        if (isX)
+            coords_lanczos_x(a);
+        else if (!coords_lanczos_y(a))
+            return fail("lanczos window taller than the source: the top border rows exceed dstH (no defined result)");
+        return true;
+    case kArea:
+        tables_area(srcLen, dstLen, isX ? 1 << 15 : 1 << 8, a);
+        coords_area(a);
+        return true;
+    case kLinear:
+        tables_linear(srcLen, dstLen, isX ? 1 << 15 : 1 << 8, a);
+        coords_linear(a);
+        return true;
+    }
+    return fail("unknown method");
+}
+
+void axis_windows(Method m, const AxisPlan &a, bool isX, std::vector<AxisWindow> *out)
+{
+    out->resize(static_cast<size_t>(a.dstLen));
+    for (int i = 0; i < a.dstLen; ++i) {
+        const Window w = axis_window(m, a, i, isX);
+        AxisWindow &o = (*out)[static_cast<size_t>(i)];
+        const int n = static_cast<int>(w.c.size());
+        const int shift = isX ? (w.start & 1) : 0;
+        o.start = w.start - shift;
+        o.lo = std::max(0, std::min(w.start, a.srcLen - 1));
+        o.hi = std::max(o.lo, std::min(w.start + n - 1, a.srcLen - 1));
+        // a masked border divisor of 0 traps in the reference; exact_div(n, INT_MAX) = 0, as in build_tile_tables
+        o.div = w.border ? (w.div ? w.div : 0x7fffffff) : 0;
+        o.c.assign(static_cast<size_t>(n + shift), 0);
+        for (int k = 0; k < n; ++k)
+            o.c[static_cast<size_t>(k + shift)] = static_cast<uint16_t>(w.c[static_cast<size_t>(k)] & 0xffff);
+    }
+}
 
 void build_tile_tables(const Plan &p, TileTables *t)
 {

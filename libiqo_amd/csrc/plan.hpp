@@ -375,6 +375,23 @@ bool build_plan(Method m, unsigned degree, size_t srcW, size_t srcH, size_t dstW
 bool build_tables(Method m, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
                   size_t pxScale, AxisPlan *x, AxisPlan *y, std::string *err);
 
+// One axis alone, as build_plan builds it (pixel scale 1): the quantised table and the coordinate map of
+// (method, degree, srcLen -> dstLen) for the X or the Y axis.  False (with *err) for a zero or oversized
+// length, a bad degree, and the Lanczos Y shapes build_plan rejects (top border band taller than dstLen).
+bool build_axis(Method m, unsigned degree, size_t srcLen, size_t dstLen, bool isX, AxisPlan *a, std::string *err);
+
+// Every output coordinate of an axis as ONE contiguous tap window, the form build_tile_tables restates
+// for the tile kernels (identity, replicated Linear borders and masked Lanczos border taps folded in):
+//   value = sum_k px(clamp(start + k, lo, hi)) * c[k], then the border division when div != 0.
+// Y: start is the reference's first tap row; div the wrapped int16 valid-tap sum.  X: start is even (one
+// leading zero coefficient when the reference's start is odd); div is 64 * the valid-tap sum.
+struct AxisWindow {
+    int32_t start = 0, lo = 0, hi = 0;  // first tap, clamp bounds of the taps with data (0 <= lo <= hi < srcLen)
+    int32_t div = 0;                    // Lanczos border divisor (0: main formula)
+    std::vector<uint16_t> c;            // coefficients as the 16-bit patterns the kernels multiply by
+};
+void axis_windows(Method m, const AxisPlan &a, bool isX, std::vector<AxisWindow> *out);
+
 // Source rows read by output rows [r0, r1) (global indices; clamped to [0, srcH)).
 void band_src_rows(const Plan &p, int r0, int r1, int *s0, int *s1);
 

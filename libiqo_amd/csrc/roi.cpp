@@ -1,0 +1,350 @@
+// roi.cpp -- host side of the batched crop-and-resize (roi.hpp): axis tables in arena form and their
+// cache, validation and layout of a call's arena, and the CPU twin of roi_kernel.
+#include "roi.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+namespace iqo_amd {
+
+namespace {
+
+// One axis table in arena form (roi.hpp); empty when the axis has no defined result (*why = 0) or its
+// reference table has more than kRoiMaxTaps taps (*why = 1).
+std::vector<uint32_t> build_roi_table(Method m, unsigned degree, int srcLen, int dstLen, bool isX, int *why)
+{
+    std::vector<uint32_t> t;
+    AxisPlan a;
+    std::string err;
+    *why = 0;
+    if (!build_axis(m, degree, static_cast<size_t>(srcLen), static_cast<size_t>(dstLen), isX, &a, &err))
+        return t;
+    *why = 1;
+    if (a.taps > kRoiMaxTaps)
+        return t;
+    std::vector<AxisWindow> w;
+    axis_windows(m, a, isX, &w);
+    size_t n = 1;
+    for (const AxisWindow &v : w)
+        n = std::max(n, v.c.size());
+    if (isX) {
+        const int NP = static_cast<int>((n + 1) / 2);
+        int minA = 0, maxEnd = srcLen;
+        for (const AxisWindow &v : w) {
+            minA = std::min(minA, v.start);
+            maxEnd = std::max(maxEnd, v.start + 2 * NP);
+        }
+        const int padL = (-minA + 1) & ~1;
+        const int pitchDw = ((padL + maxEnd + 1) / 2) | 1;
+        t.assign(4 + static_cast<size_t>(dstLen) * (2 + NP), 0u);
+        t[0] = static_cast<uint32_t>(NP);
+        t[1] = static_cast<uint32_t>(padL);
+        t[2] = static_cast<uint32_t>(pitchDw);
+        t[3] = static_cast<uint32_t>(a.taps);
+        uint32_t *col = t.data() + 4, *coef = col + 2 * static_cast<size_t>(dstLen);
+        for (int x = 0; x < dstLen; ++x) {
+            const AxisWindow &v = w[static_cast<size_t>(x)];
+            col[2 * x] = static_cast<uint32_t>(v.start);
+            col[2 * x + 1] = static_cast<uint32_t>(v.div);
+            for (size_t k = 0; k < v.c.size(); ++k)
+                coef[(k / 2) * static_cast<size_t>(dstLen) + x] |= static_cast<uint32_t>(v.c[k]) << (16 * (k & 1));
+        }
+    } else {
+        const int nYp = static_cast<int>((n + 1) & ~size_t(1));
+        t.assign(4 + static_cast<size_t>(dstLen) * (4 + nYp / 2), 0u);
+        t[0] = static_cast<uint32_t>(nYp);
+        t[1] = static_cast<uint32_t>(a.taps);
+        uint32_t *row = t.data() + 4, *coef = row + 4 * static_cast<size_t>(dstLen);
+        for (int y = 0; y < dstLen; ++y) {
+            const AxisWindow &v = w[static_cast<size_t>(y)];
+            row[4 * y] = static_cast<uint32_t>(v.start);
+            row[4 * y + 1] = static_cast<uint32_t>(v.lo);
+            row[4 * y + 2] = static_cast<uint32_t>(v.hi);
+            row[4 * y + 3] = static_cast<uint32_t>(v.div);
+            for (size_t k = 0; k < v.c.size(); ++k)
+                coef[static_cast<size_t>(y) * (nYp / 2) + k / 2] |= static_cast<uint32_t>(v.c[k]) << (16 * (k & 1));
+        }
+    }
+    return t;
+}
+
+} // namespace
+
+RoiTableCache::Table RoiTableCache::get(bool isX, int srcLen, int *why)
+{
+    const uint64_t key = (static_cast<uint64_t>(isX) << 32) | static_cast<uint32_t>(srcLen);
+    auto it = map_.find(key);
+    if (it != map_.end()) {
+        lru_.splice(lru_.begin(), lru_, it->second);
+        return it->second->t;
+    }
+    std::vector<uint32_t> t = build_roi_table(m_, degree_, srcLen, isX ? dstW_ : dstH_, isX, why);
+    if (t.empty())
+        return nullptr;
+    ++misses_;
+    Table tab = std::make_shared<const std::vector<uint32_t>>(std::move(t));
+    lru_.push_front(Entry{key, tab});
+    map_[key] = lru_.begin();
+    bytes_ += tab->size() * 4;
+    while (bytes_ > cap_ && lru_.size() > 1) {
+        const Entry &e = lru_.back();
+        bytes_ -= e.t->size() * 4;
+        map_.erase(e.key);
+        lru_.pop_back();
+    }
+    return tab;
+}
+
+void RoiTableCache::clear()
+{
+    lru_.clear();
+    map_.clear();
+    bytes_ = 0;
+}
+
+int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, size_t nFrames, size_t frameW,
+               size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad)
+{
+    // (cleared member by member: a plan's layout keeps its capacity from call to call)
+    out->nRois = out->channels = out->nXTables = out->nYTables = 0;
+    out->words = out->ldsBytes = 0;
+    out->groups = 0;
+    out->tables.clear();
+    out->rec.clear();
+    out->xIdx.clear();
+    out->yIdx.clear();
+    *bad = -1;
+    if (channels != 1 && channels != 3 && channels != 4)
+        return kRoiUnsupported;
+    const size_t C = static_cast<size_t>(channels);
+    if (!frameW || !frameH || frameW > (1u << 24) || frameH > (1u << 24) || srcSt < frameW * C ||
+        (nRois && !rois) || cache->dstW() < 1 || cache->dstH() < 1)
+        return kRoiInvalid;
+    // the kernel keeps byte offsets within a frame's rows in 32 bits
+    if (srcSt >= (size_t(1) << 31) / frameH)
+        return kRoiUnsupported;
+    if (nRois >= (size_t(1) << 24))
+        return kRoiUnsupported;
+    out->nRois = static_cast<int>(nRois);
+    out->channels = channels;
+    out->rec.assign(nRois * kRoiRecWords, 0u);
+    size_t words = kRoiHdrWords + nRois * kRoiRecWords;
+    uint64_t groups = 0;
+    const int dstH = cache->dstH();
+    for (size_t i = 0; i < nRois; ++i) {
+        const RoiBox &b = rois[i];
+        *bad = static_cast<int>(i);
+        if (b.w <= 0 || b.h <= 0 || b.x < 0 || b.y < 0 || static_cast<size_t>(b.x) + static_cast<size_t>(b.w) > frameW ||
+            static_cast<size_t>(b.y) + static_cast<size_t>(b.h) > frameH || b.frame < 0 ||
+            static_cast<size_t>(b.frame) >= nFrames || (b.flags & ~1))
+            return kRoiInvalid;
+        uint32_t tabOff[2];
+        const uint32_t *tab[2];
+        for (int ax = 0; ax < 2; ++ax) {
+            const bool isX = ax == 0;
+            std::vector<std::pair<int, int>> &idx = isX ? out->xIdx : out->yIdx;
+            const int len = isX ? b.w : b.h;
+            auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(len, 0));
+            if (it == idx.end() || it->first != len) {
+                int why = 0;
+                RoiTableCache::Table t = cache->get(isX, len, &why);
+                if (!t)
+                    return why ? kRoiUnsupported : kRoiInvalid;
+                it = idx.insert(it, std::make_pair(len, static_cast<int>(out->tables.size())));
+                out->tables.emplace_back(t, static_cast<uint32_t>(words));
+                words += t->size();
+                ++(isX ? out->nXTables : out->nYTables);
+            }
+            tabOff[ax] = out->tables[static_cast<size_t>(it->second)].second;
+            tab[ax] = out->tables[static_cast<size_t>(it->second)].first->data();
+        }
+        // rows per workgroup: the band's tap records and its work rows over the box's width and channels
+        const size_t pitchDw = tab[0][2], nYp = tab[1][0];
+        const size_t rowBytes = C * pitchDw * 4 + nYp * 8;
+        if (rowBytes > static_cast<size_t>(kRoiLdsMax))
+            return kRoiUnsupported;
+        const int rows = std::max(1, std::min(std::min(dstH, kRoiMaxRows), static_cast<int>(kRoiLdsTarget / rowBytes)));
+        const uint32_t g = static_cast<uint32_t>((dstH + rows - 1) / rows);
+        out->ldsBytes = std::max(out->ldsBytes, rows * rowBytes);
+        const uint64_t off = static_cast<uint64_t>(b.frame) * frameSt + static_cast<uint64_t>(b.y) * srcSt +
+                             static_cast<uint64_t>(b.x) * C;
+        uint32_t *r = out->rec.data() + i * kRoiRecWords;
+        r[kRFrame] = static_cast<uint32_t>(b.frame);
+        r[kROffLo] = static_cast<uint32_t>(off);
+        r[kROffHi] = static_cast<uint32_t>(off >> 32);
+        r[kRX] = static_cast<uint32_t>(b.x);
+        r[kRY] = static_cast<uint32_t>(b.y);
+        r[kRW] = static_cast<uint32_t>(b.w);
+        r[kRH] = static_cast<uint32_t>(b.h);
+        r[kRFlags] = static_cast<uint32_t>(b.flags);
+        r[kRXTab] = tabOff[0];
+        r[kRYTab] = tabOff[1];
+        r[kRRows] = static_cast<uint32_t>(rows);
+        r[kRFirst] = static_cast<uint32_t>(groups);
+        r[kRGroups] = g;
+        r[kRPitch] = static_cast<uint32_t>(pitchDw);
+        groups += g;
+        if (groups >= (uint64_t(1) << 31) || words >= (size_t(1) << 30))
+            return kRoiUnsupported;  // more boxes than one grid (or one arena) can address
+    }
+    *bad = -1;
+    out->words = words;
+    out->groups = static_cast<uint32_t>(groups);
+    return kRoiOk;
+}
+
+void roi_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena)
+{
+    std::memset(arena, 0, kRoiHdrWords * 4);
+    arena[kHMagic] = kRoiMagic;
+    arena[kHRois] = static_cast<uint32_t>(l.nRois);
+    arena[kHGroups] = l.groups;
+    arena[kHDstW] = static_cast<uint32_t>(cache.dstW());
+    arena[kHDstH] = static_cast<uint32_t>(cache.dstH());
+    arena[kHChannels] = static_cast<uint32_t>(l.channels);
+    arena[kHLanczos] = cache.method() == kLanczos ? 1u : 0u;
+    arena[kHRowBytes] = static_cast<uint32_t>(frameW * static_cast<size_t>(l.channels));
+    arena[kHRecOff] = kRoiHdrWords;
+    arena[kHWords] = static_cast<uint32_t>(l.words);
+    if (!l.rec.empty())
+        std::memcpy(arena + kRoiHdrWords, l.rec.data(), l.rec.size() * 4);
+    for (const auto &t : l.tables)
+        std::memcpy(arena + t.second, t.first->data(), t.first->size() * 4);
+}
+
+// ---------------------------------------------------------------- CPU twin
+
+namespace {
+
+// round-to-nearest-even float -> fp16 / bf16 bit patterns (overflow to +-inf), as the kernel's conversions
+uint16_t f16_bits_host(float f)
+{
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    u &= 0x7fffffffu;
+    if (u >= 0x7f800000u)
+        return static_cast<uint16_t>(sign | (u > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (u >= 0x477ff000u)  // rounds to >= 2^16
+        return static_cast<uint16_t>(sign | 0x7c00u);
+    if (u < 0x38800000u) {  // subnormal half (or zero): value * 2^24 rounded to an integer
+        if (u < 0x33000000u)
+            return static_cast<uint16_t>(sign);  // < 2^-25: rounds to zero (2^-25 itself ties to even: zero)
+        const int e = static_cast<int>(u >> 23);                // biased exponent, 102 .. 112
+        const uint32_t man = (u & 0x7fffffu) | 0x800000u;       // 24-bit significand
+        const int shift = 126 - e;                              // 14 .. 24
+        const uint32_t q = man >> shift, rem = man & ((1u << shift) - 1u), half = 1u << (shift - 1);
+        return static_cast<uint16_t>(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+    }
+    const uint32_t v = u - 0x38000000u;  // rebias 127 -> 15
+    const uint32_t q = v >> 13, rem = v & 0x1fffu;
+    return static_cast<uint16_t>(sign | (q + ((rem > 0x1000u || (rem == 0x1000u && (q & 1u))) ? 1u : 0u)));
+}
+
+uint16_t bf16_bits_host(float f)
+{
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u)
+        return static_cast<uint16_t>((u >> 16) | 0x40u);
+    return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+} // namespace
+
+void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+              void *dstV, const RoiNorm &n)
+{
+    const int nRois = static_cast<int>(arena[kHRois]);
+    const int dstW = static_cast<int>(arena[kHDstW]), dstH = static_cast<int>(arena[kHDstH]);
+    const int C = static_cast<int>(arena[kHChannels]);
+    const bool LZ = arena[kHLanczos] != 0;
+    uint8_t *dst = static_cast<uint8_t *>(dstV);
+    std::vector<uint16_t> work;
+    for (int i = 0; i < nRois; ++i) {
+        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * kRoiRecWords;
+        const uint8_t *box = src + ((static_cast<uint64_t>(r[kROffHi]) << 32) | r[kROffLo]);
+        const int w = static_cast<int>(r[kRW]);
+        const bool flip = r[kRFlags] & 1u;
+        const uint32_t *xt = arena + r[kRXTab], *yt = arena + r[kRYTab];
+        const int NP = static_cast<int>(xt[0]), padL = static_cast<int>(xt[1]), pitch = 2 * static_cast<int>(xt[2]);
+        const int32_t *col = reinterpret_cast<const int32_t *>(xt + 4);
+        const uint32_t *cx = xt + 4 + 2 * static_cast<size_t>(dstW);
+        const int nYp = static_cast<int>(yt[0]);
+        const int32_t *row = reinterpret_cast<const int32_t *>(yt + 4);
+        const uint32_t *cy = yt + 4 + 4 * static_cast<size_t>(dstH);
+        work.assign(static_cast<size_t>(C) * pitch, 0);
+        for (int y = 0; y < dstH; ++y) {
+            const int32_t start = row[4 * y], lo = row[4 * y + 1], hi = row[4 * y + 2], deno = row[4 * y + 3];
+            // vertical: 16-bit wrapping sums over the row window, rows clamped to the box
+            for (int q = 0; q < w * C; ++q) {
+                uint16_t acc = 0;
+                for (int k = 0; k < nYp; ++k) {
+                    const int rr = std::max(lo, std::min(start + k, hi));
+                    const uint16_t c = static_cast<uint16_t>(cy[static_cast<size_t>(y) * (nYp / 2) + k / 2] >> (16 * (k & 1)));
+                    acc = static_cast<uint16_t>(acc + box[static_cast<size_t>(rr) * srcSt + q] * c);
+                }
+                if (LZ && deno != 0)
+                    acc = static_cast<uint16_t>(static_cast<int16_t>(static_cast<int>(static_cast<int16_t>(acc)) * 64 / deno));
+                work[static_cast<size_t>(q % C) * pitch + padL + q / C] = acc;
+            }
+            for (int c = 0; c < C; ++c) {  // columns outside the box: the clamped edge column
+                uint16_t *wr = work.data() + static_cast<size_t>(c) * pitch;
+                for (int k = 0; k < padL; ++k)
+                    wr[k] = wr[padL];
+                for (int k = padL + w; k < pitch; ++k)
+                    wr[k] = wr[padL + w - 1];
+            }
+            // horizontal
+            for (int x = 0; x < dstW; ++x) {
+                const int32_t a = col[2 * x], D = col[2 * x + 1];
+                uint32_t bt[4] = {0, 0, 0, 0};
+                for (int c = 0; c < C; ++c) {
+                    const uint16_t *wr = work.data() + static_cast<size_t>(c) * pitch + padL + a;
+                    if (LZ) {
+                        int32_t s = 1 << 19;
+                        for (int p = 0; p < NP; ++p) {
+                            const uint32_t cf = cx[static_cast<size_t>(p) * dstW + x];
+                            s += static_cast<int16_t>(wr[2 * p]) * static_cast<int16_t>(cf & 0xffffu) +
+                                 static_cast<int16_t>(wr[2 * p + 1]) * static_cast<int16_t>(cf >> 16);
+                        }
+                        int v = s >> 20;
+                        if (D != 0)
+                            v = static_cast<int16_t>(s / D);
+                        bt[c] = static_cast<uint32_t>(std::min(std::max(v, 0), 255));
+                    } else {
+                        uint32_t s = 1u << 22;
+                        for (int p = 0; p < NP; ++p) {
+                            const uint32_t cf = cx[static_cast<size_t>(p) * dstW + x];
+                            s += static_cast<uint32_t>(wr[2 * p]) * (cf & 0xffffu) + static_cast<uint32_t>(wr[2 * p + 1]) * (cf >> 16);
+                        }
+                        bt[c] = std::min((s >> 23) & 0xffffu, 255u);
+                    }
+                }
+                const int xo = flip ? dstW - 1 - x : x;
+                if (n.dtype == 0) {
+                    uint8_t *o = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt + static_cast<size_t>(xo) * C;
+                    for (int c = 0; c < C; ++c)
+                        o[c] = static_cast<uint8_t>(bt[c]);
+                } else {
+                    const size_t elem = n.dtype == 1 ? 4 : 2;
+                    for (int p = 0; p < n.planes; ++p) {
+                        volatile float m = static_cast<float>(bt[n.order[p]]) * n.scale[p];  // two roundings
+                        const float f = m + n.bias[p];
+                        uint8_t *o = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(p) * planeSt +
+                                     static_cast<size_t>(y) * dstSt + static_cast<size_t>(xo) * elem;
+                        if (n.dtype == 1) {
+                            std::memcpy(o, &f, 4);
+                        } else {
+                            const uint16_t h = n.dtype == 2 ? f16_bits_host(f) : bf16_bits_host(f);
+                            std::memcpy(o, &h, 2);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+} // namespace iqo_amd

@@ -1,0 +1,135 @@
+// roi.hpp -- crop-and-resize of a batch of boxes to one output size (iqo_hip_resize_rois_device):
+// the per-call ARENA the kernel (kernels_roi.hip roi_kernel) and its CPU twin (roi_walk) both read,
+// the per-plan cache of axis tables that fills it, and the twin itself.  Pure C++ (no HIP).
+//
+// Box i of a call is a rectangle (x, y, w, h) of frame `frame`; its output is what the planar resize
+// (w, h) -> (dstW, dstH) gives on the cropped image, channel by channel.  Each axis is independent
+// (plan.hpp build_axis), so a box needs the X table of (w -> dstW) and the Y table of (h -> dstH),
+// both in the one-window-per-coordinate form of plan.hpp axis_windows.
+//
+// Arena: one flat buffer of 32-bit words.
+//   header   kRoiHdrWords words    see RoiHdr
+//   records  nRois x kRoiRecWords  see RoiRec
+//   tables   every distinct X table (one per distinct w) and Y table (one per distinct h), once
+// X table (word offsets from the table's start):
+//   [0] NP  coefficient pairs per column      [1] padL  work columns left of column 0 (even)
+//   [2] pitchDw  work-row pitch of one channel (dwords; >= (padL + w + padR + 1) / 2, odd)
+//   [3] taps of the reference's table
+//   [4 ..)  dstW x {a, D}: even window start, Lanczos border divisor * 64 (0: main)
+//   then    NP x dstW coefficient pairs (c_2p, c_2p+1) from the even start, pair-major
+// Y table:
+//   [0] nYp taps per row, padded to even       [1] taps of the reference's table     [2], [3] 0
+//   [4 ..)  dstH x {start, lo, hi, deno}
+//   then    dstH x nYp / 2 words, two 16-bit coefficients each
+#pragma once
+
+#include "plan.hpp"
+
+#include <cstddef>
+#include <cstdint>
+#include <list>
+#include <memory>
+#include <unordered_map>
+#include <vector>
+
+namespace iqo_amd {
+
+constexpr int kRoiHdrWords = 16;
+constexpr int kRoiRecWords = 16;
+constexpr uint32_t kRoiMagic = 0x494f5231u;  // "IOR1"
+constexpr int kRoiMaxTaps = 128;             // iqo_hip.h IQO_HIP_ROI_MAX_TAPS
+constexpr int kRoiLdsMax = 64 * 1024;        // iqo_hip.h IQO_HIP_ROI_LDS_BYTES: one workgroup's LDS
+constexpr int kRoiLdsTarget = 16 * 1024;     // rows per workgroup: as many as fit in this (at most kRoiMaxRows)
+constexpr int kRoiMaxRows = 8;
+
+// header words
+enum RoiHdr { kHMagic = 0, kHRois, kHGroups, kHDstW, kHDstH, kHChannels, kHLanczos, kHRowBytes, kHRecOff, kHWords };
+// record words
+enum RoiRec {
+    kRFrame = 0,
+    kROffLo,   // byte offset of the box's first pixel from the source base: frame * frameSt + y * srcSt + x * C
+    kROffHi,
+    kRX,
+    kRY,
+    kRW,
+    kRH,
+    kRFlags,   // bit 0: mirror the output columns
+    kRXTab,    // word offset of the box's X table
+    kRYTab,
+    kRRows,    // output rows per workgroup
+    kRFirst,   // first workgroup of the box
+    kRGroups,  // its workgroups: ceil(dstH / rows)
+    kRPitch    // work-row pitch of one channel (dwords), the X table's
+};
+
+struct RoiBox {
+    int frame, x, y, w, h, flags;
+};
+
+// Host cache of axis tables in arena form, keyed by (axis, srcLen); dstLen, method and degree are the
+// owner's.  Least recently used tables are dropped beyond `cap` bytes (a table in use by the batch
+// being assembled stays alive through its shared_ptr).
+class RoiTableCache {
+public:
+    typedef std::shared_ptr<const std::vector<uint32_t>> Table;
+    RoiTableCache(Method m, unsigned degree, int dstW, int dstH, size_t capBytes = size_t(64) << 20)
+        : m_(m), degree_(degree), dstW_(dstW), dstH_(dstH), cap_(capBytes)
+    {
+    }
+    // nullptr (with *why: 0 invalid shape, 1 over kRoiMaxTaps) when the axis has no table
+    Table get(bool isX, int srcLen, int *why);
+    size_t bytes() const { return bytes_; }
+    size_t misses() const { return misses_; }
+    void clear();
+    Method method() const { return m_; }
+    int dstW() const { return dstW_; }
+    int dstH() const { return dstH_; }
+
+private:
+    struct Entry {
+        uint64_t key;
+        Table t;
+    };
+    Method m_;
+    unsigned degree_;
+    int dstW_, dstH_;
+    size_t cap_, bytes_ = 0, misses_ = 0;
+    std::list<Entry> lru_;  // front: most recent
+    std::unordered_map<uint64_t, std::list<Entry>::iterator> map_;
+};
+
+struct RoiLayout {
+    int nRois = 0, channels = 0;
+    size_t words = 0;          // arena size
+    int nXTables = 0, nYTables = 0;
+    uint32_t groups = 0;       // total workgroups
+    size_t ldsBytes = 0;       // dynamic LDS of the launch: the largest workgroup's
+    // per distinct length: table and its word offset in the arena
+    std::vector<std::pair<RoiTableCache::Table, uint32_t>> tables;
+    std::vector<uint32_t> rec;  // nRois x kRoiRecWords
+    std::vector<std::pair<int, int>> xIdx, yIdx;  // sorted (distinct length, index in tables)
+};
+
+// Status of roi_layout: kRoiOk, or the first offending box in *bad (-1: an argument of the call)
+enum { kRoiOk = 0, kRoiInvalid = 1, kRoiUnsupported = 2 };
+
+// Validates the call and lays the arena out.  srcSt / frameSt in bytes.
+int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, size_t nFrames, size_t frameW,
+               size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad);
+// Writes the arena (out->words words) to `arena`.
+void roi_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena);
+
+// The float epilogue's parameters (kernels.hpp NormDev without HIP types)
+struct RoiNorm {
+    int dtype = 0, planes = 0;  // dtype 0: U8 output
+    int order[4] = {0, 0, 0, 0};
+    float scale[4] = {0, 0, 0, 0}, bias[4] = {0, 0, 0, 0};
+};
+
+// CPU twin of roi_kernel: walks the arena with the kernel's integer formulas.  U8: dst rows dstSt bytes
+// apart, outputs dstRoiSt apart.  Norm (n.dtype != 0): element (i, p, y, x) at i * dstRoiSt + p * planeSt +
+// y * dstSt + x * elem.
+void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+              void *dst, const RoiNorm &n);
+
+} // namespace iqo_amd
