@@ -688,6 +688,18 @@ typedef struct {
 int iqo_host_roi_arena_stats(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
                              const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
                              iqo_hip_roi_arena_stats *stats, int *badRoi);
+/* Host-only: what the layout of a call decides for ONE box of w x h pixels (the layout of a one-box call, the
+ * box being the whole of a tightly packed frame).  Same status codes as the calls above. */
+typedef struct {
+    int rows;             /* output rows per workgroup */
+    unsigned workgroups;  /* ceil(dstH / rows) */
+    size_t ldsBytes;      /* dynamic LDS of one workgroup: rows x (channels x pitchDw x 4 + nYp x 8) */
+    int nYp;              /* Y taps per output row, padded to even */
+    int np;               /* NP: X coefficient pairs per output column */
+    int pitchDw;          /* work-row pitch of one channel, dwords */
+} iqo_hip_roi_box_layout;
+int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
+                            iqo_hip_roi_box_layout *out);
 
 /* Drop-in classes (iqo::LanczosResizer, AreaResizer, LinearResizer): how many objects this process constructed on the
  * HIP backend, and on the CPU backend (no gfx950 device) plus the resize() calls of HIP objects that fell back to the

@@ -19,7 +19,7 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "host_yuv_to_rgb", "yuv_rgb_workspace_bytes", "CHROMA_REPLICATE", "CHROMA_FULL", "CHROMA_MODES",
            "host_chroma_full_kernel", "host_rgb_to_yuv", "host_rgb_to_yuv420", "rgb_yuv_workspace_bytes",
            "SOURCE_ORDERS", "RoiResizer", "Roi", "RoiArenaStats", "host_resize_rois", "host_roi_arena_stats",
-           "ROI_MAX_TAPS", "ROI_LDS_BYTES"]
+           "RoiBoxLayout", "host_roi_box_layout", "ROI_MAX_TAPS", "ROI_LDS_BYTES"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -97,6 +97,12 @@ class RoiArenaStats(ctypes.Structure):
     """iqo_hip_roi_arena_stats"""
     _fields_ = [("arenaBytes", _c_sz), ("xTables", ctypes.c_int), ("yTables", ctypes.c_int),
                 ("workgroups", ctypes.c_uint), ("ldsBytes", _c_sz), ("recordBytes", _c_sz)]
+
+
+class RoiBoxLayout(ctypes.Structure):
+    """iqo_hip_roi_box_layout"""
+    _fields_ = [("rows", ctypes.c_int), ("workgroups", ctypes.c_uint), ("ldsBytes", _c_sz), ("nYp", ctypes.c_int),
+                ("np", ctypes.c_int), ("pitchDw", ctypes.c_int)]
 
 
 ROI_MAX_TAPS, ROI_LDS_BYTES = 128, 65536  # IQO_HIP_ROI_MAX_TAPS, IQO_HIP_ROI_LDS_BYTES
@@ -216,6 +222,7 @@ def lib():
     L.iqo_host_resize_rois_norm.argtypes = roi_host + roi_src + [ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz, _vp, pi]
     L.iqo_host_roi_arena_stats.argtypes = roi_host + [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz,
                                                       ctypes.POINTER(RoiArenaStats), pi]
+    L.iqo_host_roi_box_layout.argtypes = roi_host + [_c_sz, _c_sz, ctypes.POINTER(RoiBoxLayout)]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -523,6 +530,20 @@ def host_roi_arena_stats(method, degree, dstW, dstH, channels, boxes, nFrames, f
     _check_rois(rc, bad, boxes, "host_roi_arena_stats")
     return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
             "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
+
+
+def host_roi_box_layout(method, degree, channels, dstW, dstH, w, h):
+    """iqo_host_roi_box_layout: {"rows", "workgroups", "lds_bytes", "nYp", "NP", "pitchDw"} the layout of a call
+    decides for one box of w x h pixels, without a GPU."""
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    bl = RoiBoxLayout()
+    rc = lib().iqo_host_roi_box_layout(m, degree, channels, dstW, dstH, w, h, ctypes.byref(bl))
+    if rc != 0:
+        err = IqoError("host_roi_box_layout: %s (%d) (box %d x %d)" % (lib().iqo_hip_strerror(rc).decode(), rc, w, h))
+        err.status, err.bad_roi = rc, -1  # IQO_HIP_E*; the call names no box index
+        raise err
+    return {"rows": bl.rows, "workgroups": bl.workgroups, "lds_bytes": bl.ldsBytes, "nYp": bl.nYp, "NP": bl.np,
+            "pitchDw": bl.pitchDw}
 
 
 def _ptr(obj):

@@ -3759,4 +3759,30 @@ int iqo_host_roi_arena_stats(int method, unsigned degree, int channels, size_t d
                      frameW * C * frameH, nullptr, nullptr, false, 0, 0, 0, nullptr, stats, badRoi);
 }
 
+int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
+                            iqo_hip_roi_box_layout *out)
+{
+    if (!out || method < 0 || method > 2 || !dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20) || !w || !h ||
+        w > (1u << 24) || h > (1u << 24))
+        return IQO_HIP_EINVAL;
+    // the box as the whole of one tightly packed frame: roi_layout on a one-box call, as the device call
+    const size_t C = channels > 0 ? static_cast<size_t>(channels) : 1;
+    const iqo_amd::RoiBox box = {0, 0, 0, static_cast<int>(w), static_cast<int>(h), 0};
+    iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
+    iqo_amd::RoiLayout l;
+    int bad = -1;
+    const int st = iqo_amd::roi_layout(&cache, channels, 1, &box, 1, w, h, w * C, w * C * h, &l, &bad);
+    if (st != iqo_amd::kRoiOk)
+        return roi_status(st);
+    const uint32_t *xt = l.tables[static_cast<size_t>(l.xIdx[0].second)].first->data();
+    const uint32_t *yt = l.tables[static_cast<size_t>(l.yIdx[0].second)].first->data();
+    out->rows = static_cast<int>(l.rec[iqo_amd::kRRows]);
+    out->workgroups = l.rec[iqo_amd::kRGroups];
+    out->ldsBytes = l.ldsBytes;
+    out->nYp = static_cast<int>(yt[0]);
+    out->np = static_cast<int>(xt[0]);
+    out->pitchDw = static_cast<int>(l.rec[iqo_amd::kRPitch]);
+    return IQO_HIP_OK;
+}
+
 } // extern "C"

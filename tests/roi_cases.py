@@ -62,14 +62,14 @@ def boxes(method, degree):
 
 
 @functools.lru_cache(maxsize=None)
-def _ref_clean(method, degree, w, h):
+def _ref_clean(method, degree, w, h, dw=DW, dh=DH):
     """False where the reference itself has no clean run of the shape -- a zero border denominator (it traps:
     several of the tiny Lanczos boxes) or reads past its source (Area at non-integer ratios) -- as its sanitizer
     build tells (the check of tests/test_oracle_golden.py).  Such boxes are pinned by the oracle alone."""
     exe = os.path.join(ol.REF_DIR, "ref_asan_check")
     if not os.path.exists(exe):
         return False
-    r = subprocess.run([exe, str(ol.METHODS[method]), str(degree), str(w), str(h), str(DW), str(DH), "1"],
+    r = subprocess.run([exe, str(ol.METHODS[method]), str(degree), str(w), str(h), str(dw), str(dh), "1"],
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return r.returncode == 0
 
