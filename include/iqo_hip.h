@@ -141,8 +141,37 @@ int iqo_hip_plan_set_option(iqo_hip_plan *plan, const char *key, long value);
 /* Drop-in resize with HOST pointers (byte strides), synchronous: H2D, kernels, D2H. */
 int iqo_hip_resize(iqo_hip_plan *plan, size_t srcSt, const uint8_t *src, size_t dstSt, uint8_t *dst);
 
+/* ---- Layout limits.  Frame strides are unlimited (64-bit) for every kernel.  Within a frame most kernel
+ * families address rows with 32-bit byte offsets, so each family limits the row strides and the SPAN of a
+ * call: the bytes from the first byte of the source window (destination band) to the last byte touched,
+ * (rows - 1) * stride + srcW * channels (dstW * channels), the rows being the source window's or the
+ * band's.  The largest accepted values, 0 = unlimited:
+ *
+ *   family (IQO_KERNEL_*)                          srcSpan, dstSpan         srcSt        dstSt
+ *   GENERAL, AREA_INT, PACKED_GENERAL              0                        0            0
+ *   TILE, PACKED_TILE                              2^31 - 1                 2^24 - 1     2^31 - 1
+ *   LANCZOS_STREAM, LINEAR_UP2                     IQO_HIP_DROP_OFFSET - 1  DROP - 1     DROP - 1
+ *   WALK (source row rounded up to 4 bytes)        IQO_HIP_DROP_OFFSET - 1  2^24 - 1     DROP - 1
+ *   LANCZOS_UP2 / _D32 / _D31 / _U23, LINEAR_U23,
+ *   AREA_D32, RYX, RYG                             IQO_HIP_DROP_OFFSET - 1  2^24 - 1     2^24 - 1
+ *
+ * IQO_HIP_DROP_OFFSET is the byte offset these kernels give an access that must not happen; a span that
+ * reached it would turn such an access into a real one.  Which family a call runs depends on the plan,
+ * its options and the alignment of the layout (iqo_hip_plan_query, iqo_host_kernel_for_layout).
+ * iqo_host_layout_limits reports the row of a family (host-only; IQO_HIP_EINVAL for an unknown family or a
+ * null pointer); the launch functions test against the same table (libiqo_amd/csrc/kernels.hpp). */
+#define IQO_HIP_DROP_OFFSET 0x7ff00000
+typedef struct iqo_hip_layout_limits {
+    uint64_t srcSpanMax, dstSpanMax;   /* bytes, first to last of the window / band; 0 = unlimited */
+    uint64_t srcStMax, dstStMax;       /* row strides, bytes; 0 = unlimited */
+} iqo_hip_layout_limits;
+int iqo_host_layout_limits(int kernel, iqo_hip_layout_limits *out);
+
 /* Batched resize of nFrames frames resident in device memory, asynchronous on `stream`.
- * Frame f reads dSrc + f*srcFrameSt and writes dDst + f*dstFrameSt. */
+ * Frame f reads dSrc + f*srcFrameSt and writes dDst + f*dstFrameSt.
+ * IQO_HIP_EINVAL: a null pointer, srcSt < srcW*channels, dstSt < dstW*channels, or a layout beyond the
+ * limits above of the family the call runs (source window: the rows iqo_hip_band_src_rows names for the
+ * whole frame).  On IQO_HIP_EINVAL nothing is launched and the destination is untouched. */
 int iqo_hip_resize_device(iqo_hip_plan *plan, size_t nFrames, size_t srcSt, size_t srcFrameSt,
                           const uint8_t *dSrc, size_t dstSt, size_t dstFrameSt, uint8_t *dDst,
                           void *stream);
@@ -240,7 +269,11 @@ int iqo_hip_band_src_rows(const iqo_hip_plan *plan, size_t dstRow0, size_t dstRo
  * (as returned by iqo_hip_band_src_rows, or any window containing it); dDstBand points at the
  * band's first row.  Rows are computed with their GLOBAL indices, so a banded result is
  * byte-identical to the unsharded one.  IQO_HIP_EINVAL if the window starts below the band's
- * first source row; the kernels read no row past the end of the band's window. */
+ * first source row; the kernels read no row past the end of the band's window.
+ * The layout limits above apply to the band: the source span runs from row srcRow0 to the last row the
+ * band reads, the destination span over the band's dstRows rows, so a frame whose whole span is over a
+ * limit can still be resized band by band.  IQO_HIP_EINVAL for a band beyond them; on IQO_HIP_EINVAL
+ * nothing is launched and the destination is untouched. */
 int iqo_hip_resize_band(iqo_hip_plan *plan, size_t nFrames, size_t dstRow0, size_t dstRows,
                         size_t srcRow0, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrcWindow,
                         size_t dstSt, size_t dstFrameSt, uint8_t *dDstBand, void *stream);
@@ -259,7 +292,11 @@ iqo_hip_plan *iqo_hip_yuv_plane(iqo_hip_yuv_plan *plan, int plane);
 /* Device-resident batch, asynchronous on `stream`: frame f's planes start at srcY/srcU/srcV +
  * f*srcFrameSt (likewise dst).  All three planes go in ONE launch when the plane kernels have a
  * fused instantiation (*fused = 1; the fast kernels of every BASELINE shape do), else one launch
- * per plane (*fused = 0).  `fused` may be NULL. */
+ * per plane (*fused = 0).  `fused` may be NULL.
+ * IQO_HIP_EINVAL: a null pointer, a stride below its row, or a plane whose layout is beyond the layout
+ * limits (above iqo_hip_resize_device) of the family that plane runs; the fused launch counts every row
+ * of a source plane as its window.  All three planes are checked before the first launch: on
+ * IQO_HIP_EINVAL nothing is launched and no destination plane is touched. */
 int iqo_hip_resize_yuv420_device(iqo_hip_yuv_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
                                  size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcU, const uint8_t *srcV,
                                  size_t dstStY, size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstU,
@@ -282,7 +319,10 @@ void iqo_hip_nv12_plan_destroy(iqo_hip_nv12_plan *plan);
  * full-grid UV plan of IQO_CHROMA_FULL (NULL before iqo_hip_nv12_plan_set_chroma built it). */
 iqo_hip_plan *iqo_hip_nv12_plane(iqo_hip_nv12_plan *plan, int plane);
 /* Device-resident batch, asynchronous on `stream`: frame f's planes start at srcY / srcUV +
- * f*srcFrameSt (likewise dst). */
+ * f*srcFrameSt (likewise dst).
+ * IQO_HIP_EINVAL: a null pointer, a stride below its row, or a plane whose layout is beyond the layout
+ * limits (above iqo_hip_resize_device) of the family that plane runs.  Both planes are checked before the
+ * first launch: on IQO_HIP_EINVAL nothing is launched and neither destination plane is touched. */
 int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *plan, size_t nFrames, size_t srcStY, size_t srcStUV,
                                size_t srcFrameSt, const uint8_t *srcY, const uint8_t *srcUV, size_t dstStY,
                                size_t dstStUV, size_t dstFrameSt, uint8_t *dstY, uint8_t *dstUV, void *stream);

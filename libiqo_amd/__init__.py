@@ -328,6 +328,25 @@ def host_instances(kernel):
     return out
 
 
+class LayoutLimits(ctypes.Structure):
+    """iqo_hip_layout_limits: the largest accepted spans and row strides of a kernel family, 0 = unlimited."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("srcSpanMax", "dstSpanMax", "srcStMax", "dstStMax")]
+
+
+DROP_OFFSET = 0x7ff00000  # iqo_hip.h IQO_HIP_DROP_OFFSET
+
+
+def host_layout_limits(kernel):
+    """(srcSpanMax, dstSpanMax, srcStMax, dstStMax) of a kernel family (a KERNELS name), 0 = unlimited: the
+    table the launch functions test a layout against -- host only, no GPU."""
+    family = {v: k for k, v in KERNELS.items()}[kernel]
+    f = lib().iqo_host_layout_limits
+    f.argtypes = [ctypes.c_int, ctypes.POINTER(LayoutLimits)]
+    m = LayoutLimits()
+    _check(f(family, ctypes.byref(m)), "host_layout_limits")
+    return (m.srcSpanMax, m.dstSpanMax, m.srcStMax, m.dstStMax)
+
+
 def host_lanczos_yfold(method, degree, srcW, srcH, dstW, dstH, pxScale=1):
     """True when a call of this shape runs the block-shared Lanczos 2:1 streamer with the folded vertical
     pass (its own Y table has an outer tap twice its neighbour) -- host only, no GPU."""

@@ -1595,6 +1595,27 @@ iqo_amd::Io make_io(size_t frames, const uint8_t *src, size_t srcSt, size_t srcF
     return io;
 }
 
+// Whether the launcher of `kernel` takes this layout: kernels.hpp layout_ok on the Io that run_band builds
+// for output rows [rb, re) of the plan, with the source window [srcRow0, srcRowEnd).  Host arithmetic
+// only, so an entry with several planes can ask for all of them before its first launch.
+bool layout_accepted(const iqo_hip_plan *h, int kernel, int rb, int re, size_t srcRow0, int srcRowEnd, size_t srcSt,
+                     size_t dstSt)
+{
+    const iqo_amd::Io io = make_io(1, nullptr, srcSt, 0, srcRow0, srcRowEnd, nullptr, dstSt, 0, rb);
+    const int64_t C = h->channels;
+    int64_t sb, db;
+    return iqo_amd::layout_ok(kernel, io, re, h->p.srcW * C, h->p.dstW * C, &sb, &db);
+}
+
+// ... of a whole frame of one plane of an I420 / NV12 call.  wholeSource: the window is every source row (the
+// fused I420 launch), which contains the rows run_band names
+bool plane_layout_accepted(const iqo_hip_plan *h, int kernel, bool wholeSource, size_t srcSt, size_t dstSt)
+{
+    int s0, s1;
+    iqo_amd::band_src_rows(h->p, 0, h->p.dstH, &s0, &s1);
+    return layout_accepted(h, kernel, 0, h->p.dstH, 0, wholeSource ? h->p.srcH : s1, srcSt, dstSt);
+}
+
 int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t srcRow0, size_t srcSt,
              size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstFrameSt, uint8_t *dst, hipStream_t s)
 {
@@ -2294,8 +2315,14 @@ int iqo_hip_resize_yuv420_device(iqo_hip_yuv_plan *yp, size_t nFrames, size_t sr
     const int ky = kernel_for_layout(hy, srcY, srcStY, srcFrameSt, dstY, dstStY, dstFrameSt);
     const int ku = kernel_for_layout(hc, srcU, srcStUV, srcFrameSt, dstU, dstStUV, dstFrameSt);
     const int kv = kernel_for_layout(hc, srcV, srcStUV, srcFrameSt, dstV, dstStUV, dstFrameSt);
-    if (ky == ku && ku == kv &&
-        (ky == IQO_KERNEL_LANCZOS_STREAM || ky == IQO_KERNEL_AREA_INT || ky == IQO_KERNEL_LINEAR_UP2)) {
+    const bool fusable = ky == ku && ku == kv &&
+                         (ky == IQO_KERNEL_LANCZOS_STREAM || ky == IQO_KERNEL_AREA_INT || ky == IQO_KERNEL_LINEAR_UP2);
+    // every plane's layout against its launcher's limits before the first launch: a rejected chroma plane
+    // must not leave a written Y plane behind
+    if (!plane_layout_accepted(hy, ky, fusable, srcStY, dstStY) || !plane_layout_accepted(hc, ku, fusable, srcStUV, dstStUV) ||
+        !plane_layout_accepted(hc, kv, fusable, srcStUV, dstStUV))
+        return IQO_HIP_EINVAL;
+    if (fusable) {
         // frames per launch: as run_band
         size_t chunk = std::min<size_t>(65535, hy->chunkFrames > 0 ? static_cast<size_t>(hy->chunkFrames) : 65535);
         const size_t n = (nFrames + chunk - 1) / chunk;
@@ -2318,6 +2345,8 @@ int iqo_hip_resize_yuv420_device(iqo_hip_yuv_plan *yp, size_t nFrames, size_t sr
                 *fused = 1;
             return IQO_HIP_OK;
         }
+        if (e == hipErrorInvalidValue)  // a launcher's own rejection, made before it launches: as run_band
+            return IQO_HIP_EINVAL;
         if (e != hipErrorNotSupported)
             return IQO_HIP_EHIP;
         (void)hipGetLastError();
@@ -2397,7 +2426,19 @@ int iqo_hip_resize_nv12_device(iqo_hip_nv12_plan *np, size_t nFrames, size_t src
 {
     if (!np || !np->y || !np->uv)
         return IQO_HIP_EINVAL;
-    // two launches on the same stream (run_band checks pointers and strides per plane)
+    // both planes' pointers, strides and layouts before the first launch: a rejected UV plane must not
+    // leave a written Y plane behind
+    iqo_hip_plan *hy = np->y, *huv = np->uv;
+    if (!srcY || !srcUV || !dstY || !dstUV || srcStY < static_cast<size_t>(hy->p.srcW) ||
+        dstStY < static_cast<size_t>(hy->p.dstW) || srcStUV < 2 * static_cast<size_t>(huv->p.srcW) ||
+        dstStUV < 2 * static_cast<size_t>(huv->p.dstW))
+        return IQO_HIP_EINVAL;
+    if (!plane_layout_accepted(hy, kernel_for_layout(hy, srcY, srcStY, srcFrameSt, dstY, dstStY, dstFrameSt), false, srcStY,
+                               dstStY) ||
+        !plane_layout_accepted(huv, kernel_for_layout(huv, srcUV, srcStUV, srcFrameSt, dstUV, dstStUV, dstFrameSt), false,
+                               srcStUV, dstStUV))
+        return IQO_HIP_EINVAL;
+    // two launches on the same stream
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = run_band(np->y, nFrames, 0, static_cast<size_t>(np->y->p.dstH), 0, srcStY, srcFrameSt, srcY, dstStY,
                       dstFrameSt, dstY, s);
@@ -3385,6 +3426,24 @@ int iqo_host_lanczos_yfold(int method, unsigned degree, size_t srcW, size_t srcH
     if (h.p.kernel != IQO_KERNEL_LANCZOS_STREAM)
         return 0;
     return iqo_amd::symb_yfold(lanczos_dev(&h)) ? 1 : 0;
+}
+
+int iqo_host_layout_limits(int kernel, iqo_hip_layout_limits *out)
+{
+    static_assert(iqo_amd::kFamGeneral == IQO_KERNEL_GENERAL && iqo_amd::kFamLanczosStream == IQO_KERNEL_LANCZOS_STREAM &&
+                      iqo_amd::kFamAreaInt == IQO_KERNEL_AREA_INT && iqo_amd::kFamLinearUp2 == IQO_KERNEL_LINEAR_UP2 &&
+                      iqo_amd::kFamPackedTile == IQO_KERNEL_PACKED_TILE &&
+                      iqo_amd::kFamPackedGeneral == IQO_KERNEL_PACKED_GENERAL &&
+                      iqo_amd::kFamCount == IQO_KERNEL_PACKED_GENERAL + 1 && iqo_amd::kOobOffset == IQO_HIP_DROP_OFFSET,
+                  "kernels.hpp kFam* are iqo_hip.h IQO_KERNEL_*");
+    if (!out || kernel < 0 || kernel >= iqo_amd::kFamCount)
+        return IQO_HIP_EINVAL;
+    const iqo_amd::LayoutLimits m = iqo_amd::layout_limits(kernel);
+    out->srcSpanMax = static_cast<uint64_t>(m.srcSpanMax);
+    out->dstSpanMax = static_cast<uint64_t>(m.dstSpanMax);
+    out->srcStMax = static_cast<uint64_t>(m.srcStMax);
+    out->dstStMax = static_cast<uint64_t>(m.dstStMax);
+    return IQO_HIP_OK;
 }
 
 int iqo_host_instance_count(int family) { return iqo_amd::instances(family).count; }

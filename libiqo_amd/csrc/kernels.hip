@@ -235,10 +235,10 @@ __global__ __launch_bounds__(256) void tile_kernel(TileArgs a)
                 const int gg = valid ? tt - rr * gE : 0;
                 const int o = static_cast<int>(__umul24(rmin + rr - srcRow0, srcSt)) + srcMis + colStart + 8 * gg;
                 if (srcA4) {
-                    v[b] = __builtin_amdgcn_raw_buffer_load_b64(srcR, valid ? o : 0x7ff00000, 0, 0);
+                    v[b] = __builtin_amdgcn_raw_buffer_load_b64(srcR, valid ? o : kOobOffset, 0, 0);
                 } else {
                     const int d = o & 3;
-                    const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(srcR, valid ? o - d : 0x7ff00000, 0, 0);
+                    const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(srcR, valid ? o - d : kOobOffset, 0, 0);
                     v[b] = u32x2{__builtin_amdgcn_alignbyte(w.y, w.x, d), __builtin_amdgcn_alignbyte(w.z, w.y, d)};
                 }
                 dstOff[b] = valid ? rr * spitch + 8 * gg : -1;
@@ -459,7 +459,7 @@ __device__ __forceinline__ void lanczos_stream_kernel_body(const LanczosArgs &a,
     const int cb = KX * x0 - 16 + 16 * lane;      // first source column of this lane's block
     const int outX = x0 + (lane - 1) * OUTS;      // first output column of this lane
     const bool produce = lane >= 1 && lane <= 62 && outX < L.dstW;
-    const int voff = (cb >= 0 && cb < L.srcW) ? cb : 0x7ff00000;  // off-image blocks read zero
+    const int voff = (cb >= 0 && cb < L.srcW) ? cb : kOobOffset;  // off-image blocks read zero
     const bool edgeL = x0 == 0, edgeR = x0 + OPW >= L.dstW;       // wave holds border columns
     const bool laneL = outX == 0, laneR = outX == L.dstW - OUTS;  // ... in this lane
 
@@ -471,8 +471,8 @@ __device__ __forceinline__ void lanczos_stream_kernel_body(const LanczosArgs &a,
     const int srcSt = static_cast<int>(a.io.srcSt), dstSt = static_cast<int>(a.io.dstSt);
     const int srcRow0 = a.io.srcRow0;
     const int dbg = IQO_DBG(a);
-    const int svoff = (dbg & 2) ? 0x7ff00000 : voff;
-    const int stoff = (produce && !(dbg & 1)) ? outX : 0x7ff00000;  // dropped for non-producers
+    const int svoff = (dbg & 2) ? kOobOffset : voff;
+    const int stoff = (produce && !(dbg & 1)) ? outX : kOobOffset;  // dropped for non-producers
 
     // Branch-free row load (r < 0 wraps to a huge unsigned soffset, r >= srcH lies past the
     // range): no branches keep the waitcnt counting exact across the unrolled rows.
@@ -796,7 +796,7 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
     const int cb = 2 * x0 - 16 + 16 * lane;
     const int outX = x0 + (lane - 1) * 8;
     const bool produce = lane >= 1 && lane <= np && outX < L.dstW;
-    const int voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : 0x7ff00000;
+    const int voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : kOobOffset;
     const bool edgeL = x0 == 0 && !(IQO_DBG(a) & 4), edgeR = x0 + opw >= L.dstW && !(IQO_DBG(a) & 4);
     const bool laneL = outX == 0, laneR = outX == L.dstW - 8;
 
@@ -808,8 +808,8 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
     const int srcSt = static_cast<int>(a.io.srcSt), dstSt = static_cast<int>(a.io.dstSt);
     const int srcRow0 = a.io.srcRow0;
     const int dbg = IQO_DBG(a);
-    const int svoff = (dbg & 2) ? 0x7ff00000 : voff;
-    const int stoff = (produce && !(dbg & 1)) ? outX : 0x7ff00000;
+    const int svoff = (dbg & 2) ? kOobOffset : voff;
+    const int stoff = (produce && !(dbg & 1)) ? outX : kOobOffset;
     // Odd bands walk bottom-up: a band boundary's halo rows are then read by both bands at the
     // same time (both at their start or both at their end) and the second read hits the
     // Infinity Cache instead of HBM.  The window arithmetic is symmetric, so only the row order
@@ -825,7 +825,7 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
                                  (__attribute__((address_space(3))) uint8_t *)ring)) +
                              static_cast<uint32_t>(wib * K * SLOT);
     const uint8_t *ringLane = ring + wib * K * SLOT + lane * 16;
-    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : 0x7ff00000; };
+    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : kOobOffset; };
     // iteration i (output row y0 + i, or y1 - 1 - i walking up) brings walk rows NY-2 and NY-1
     auto rowAt = [&](int i, int t) { return dir > 0 ? rFirst + 2 * i + t : rLast - 2 * i - t; };
     auto dma_iter = [&](int i) {
@@ -868,12 +868,12 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
         if (edgeL) {
             const int4 e = edgeSum[wib][0][lane & 63];
             const uint32_t w = fix(e.x, 0) | (fix(e.y, 1) << 8) | (fix(e.z, 2) << 16) | (fix(e.w, 3) << 24);
-            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 1) ? rowOff : 0x7ff00000, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 1) ? rowOff : kOobOffset, 0, 0);
         }
         if (edgeR) {
             const int4 e = edgeSum[wib][1][lane & 63];
             const uint32_t w = fix(e.x, 4) | (fix(e.y, 5) << 8) | (fix(e.z, 6) << 16) | (fix(e.w, 7) << 24);
-            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 1) ? rowOff + L.dstW - 4 : 0x7ff00000,
+            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 1) ? rowOff + L.dstW - 4 : kOobOffset,
                                                   0, 0);
         }
     };
@@ -898,7 +898,7 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
 #pragma unroll
     for (int j = 0; j < K - 1; ++j) {
         dma_iter(j);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, dstR, 0x7ff00000, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, dstR, kOobOffset, 0, 0);
     }
 
     auto row = [&](auto uc, int base) {
@@ -1065,7 +1065,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     const int cb = 2 * x0 - 16 + 16 * lane;
     const int outX = x0 + (lane - 1) * 8;
     const bool produce = lane >= 1 && lane <= np && outX < L.dstW;
-    const int voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : 0x7ff00000;  // prologue loads
+    const int voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : kOobOffset;  // prologue loads
     const int ldsCol = lane <= np + 1 ? 16 + cb : 0;  // this lane's 16 bytes in an LDS ring row
     const bool edgeL = x0 == 0 && !(IQO_DBG(a) & 4), edgeR = x0 + opw >= L.dstW && !(IQO_DBG(a) & 4);
     const bool laneL = outX == 0, laneR = outX == L.dstW - 8;
@@ -1091,8 +1091,8 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     const int srcSt = static_cast<int>(a.io.srcSt), dstSt = static_cast<int>(a.io.dstSt);
     const int srcRow0 = a.io.srcRow0;
     const int dbg = IQO_DBG(a);
-    const int svoff = (dbg & 2) ? 0x7ff00000 : voff;
-    const int stoff = (produce && !(dbg & 1) && !regL && !regR) ? outX : 0x7ff00000;
+    const int svoff = (dbg & 2) ? kOobOffset : voff;
+    const int stoff = (produce && !(dbg & 1) && !regL && !regR) ? outX : kOobOffset;
 #ifdef IQO_SYMB_STAUX
     constexpr int STNT = IQO_SYMB_STAUX;  // variant builds: store cache policy bits (1 sc0, 2 nt, 16 sc1)
 #else
@@ -1117,7 +1117,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     const uint32_t ldsBase = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
         (__attribute__((address_space(3))) uint8_t *)lds));
     const uint8_t *ringLane = ring + ldsCol;
-    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : 0x7ff00000; };
+    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : kOobOffset; };
     // iteration i (output row y0 + i, or y1 - 1 - i walking up) brings walk rows NY-2 and NY-1
     auto rowAt = [&](int i, int t) { return dir > 0 ? rFirst + 2 * i + t : rLast - 2 * i - t; };
     // the DMA rows of iteration j are linear in j and inside [rFirst, rLast] exactly when j < nRows
@@ -1134,14 +1134,14 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         const uint32_t s = ldsBase + static_cast<uint32_t>(slot * slotBytes);
         const bool in = j < nRows;
         const bool nt = (IQO_SYMB_NT & 1) || j < ntEnd;  // uniform
-        const int so0 = in ? dmaSoff0 + j * dmaStep : 0x7ff00000;
-        const int so1 = in ? dmaSoff0 + j * dmaStep + dmaNext : 0x7ff00000;
+        const int so0 = in ? dmaSoff0 + j * dmaStep : kOobOffset;
+        const int so1 = in ? dmaSoff0 + j * dmaStep + dmaNext : kOobOffset;
 #pragma unroll
         for (int jj = 0; jj < CPW; ++jj) {
             const int c = wcol + jj * wpr;
             const bool real = c < a.chunks;  // uniform; otherwise a same-count DMA into the sink
             const int col = 1024 * c + 16 * lane;
-            const int v = (real && col < L.srcW && !(dbg & 2)) ? col : 0x7ff00000;
+            const int v = (real && col < L.srcW && !(dbg & 2)) ? col : kOobOffset;
             const uint32_t d0 = real ? s + 16 + 1024 * c : ldsBase + sinkLds;
             const uint32_t d1 = real ? d0 + rowPitch : d0;
 #if IQO_SYMB_DMA1
@@ -1205,12 +1205,12 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         if (edgeL) {
             const int4 e = edgeSum[0][lane & (EB - 1)];
             const uint32_t w = fix(e.x, 0) | (fix(e.y, 1) << 8) | (fix(e.z, 2) << 16) | (fix(e.w, 3) << 24);
-            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 65) ? rowOff : 0x7ff00000, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 65) ? rowOff : kOobOffset, 0, 0);
         }
         if (edgeR) {
             const int4 e = edgeSum[1][lane & (EB - 1)];
             const uint32_t w = fix(e.x, 4) | (fix(e.y, 5) << 8) | (fix(e.z, 6) << 16) | (fix(e.w, 7) << 24);
-            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 65) ? rowOff + L.dstW - 4 : 0x7ff00000,
+            __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 65) ? rowOff + L.dstW - 4 : kOobOffset,
                                                   0, 0);
         }
     };
@@ -1258,7 +1258,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
             for (int r0 = 0; r0 < H; r0 += 4) {
                 const int r = r0 + (lane >> 4), piece = (lane & 15) * 8;
                 const u32x2 val = *reinterpret_cast<const u32x2 *>(lineBuf + (side * H + min(r, H - 1)) * 128 + piece);
-                const int off = r < n && !(dbg & 65) ? (yb + dir * r - a.io.dstRow0) * dstSt + colBase + piece : 0x7ff00000;
+                const int off = r < n && !(dbg & 65) ? (yb + dir * r - a.io.dstRow0) * dstSt + colBase + piece : kOobOffset;
                 __builtin_amdgcn_raw_buffer_store_b64(val, dstR, off, 0, STNT);
             }
         }
@@ -1290,7 +1290,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
 #pragma unroll
     for (int j = 0; j < K - 1; ++j) {
         dma_iter(j, j);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, dstR, 0x7ff00000, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, dstR, kOobOffset, 0, 0);
     }
 
     uint4 n0, n1;  // this iteration's two new rows (read from LDS one iteration ahead)
@@ -1556,7 +1556,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
     constexpr int EB = 16;                      // rows of parked border-column sums per flush
     constexpr int PITCH = 2048;                 // ring row: 128 virtual lanes x 16 B
     constexpr int SLOT = 2 * PITCH;
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint8_t *const ring = lds;
     int4 *const edgeSum = reinterpret_cast<int4 *>(lds + K * SLOT);  // [F][side][EB]
@@ -1833,7 +1833,7 @@ template <int NP, int VY, int NV, bool LZ>
 __global__ __launch_bounds__(256) void walk_kernel(WalkArgs a)
 {
     // VY: vertical taps, 2 * NP or 2 * NP - 2 (plan.cpp build_walk_tables)
-    constexpr int OOB = 0x7ff00000;      // buffer offset past every range: no traffic, reads 0
+    constexpr int OOB = kOobOffset;      // buffer offset past every range: no traffic, reads 0
     extern __shared__ __attribute__((aligned(16))) uint8_t wl[];
     const WalkDev &W = a.w;
     const TileDev &t = W.t;
@@ -2332,8 +2332,8 @@ __device__ __forceinline__ void linear_up2_kernel_body(const LinearArgs &a, cons
     const int x0 = max(0, min(wcol * 8 * np, g.srcW - 8 * np));  // first source column of lane 1
     const int cb = x0 - 8 + 8 * lane;
     const bool produce = lane >= 1 && lane <= np;
-    const int voff = (lane <= np + 1 && cb >= 0 && cb < g.srcW) ? cb : 0x7ff00000;
-    const int stoff = produce ? F * cb : 0x7ff00000;
+    const int voff = (lane <= np + 1 && cb >= 0 && cb < g.srcW) ? cb : kOobOffset;
+    const int stoff = produce ? F * cb : kOobOffset;
     // replicated border columns (work + 128) >> 8 == (work * 2^15 + 2^22) >> 23: the border lanes
     // take the weight pair (0, 2^15) / (2^15, 0) for their outer output, so no branch is needed
     const uint32_t cxFirst = cb == 0 ? 0x80000000u : g.cx[0];
@@ -2355,7 +2355,7 @@ __device__ __forceinline__ void linear_up2_kernel_body(const LinearArgs &a, cons
                                                // row's second sample has weight 0)
 
     auto load_row = [&](int r) -> u32x2 {
-        return __builtin_amdgcn_raw_buffer_load_b64(srcR, voff, r <= rLast ? (r - srcRow0) * srcSt : 0x7ff00000,
+        return __builtin_amdgcn_raw_buffer_load_b64(srcR, voff, r <= rLast ? (r - srcRow0) * srcSt : kOobOffset,
                                                     0);  // default policy: 1 % faster than nt on C4
     };
     auto unpack = [&](u32x2 v, uint32_t (&P)[5]) {
@@ -2387,10 +2387,10 @@ __device__ __forceinline__ void linear_up2_kernel_body(const LinearArgs &a, cons
 #pragma unroll
         for (int q = 0; q < OPL / 4; ++q)
             o[q] = pack23_hi(pack23_lo(s[4 * q], s[4 * q + 1]), s[4 * q + 2], s[4 * q + 3]);
-        const int rowOff = valid ? (y - dstRow0) * dstSt : 0x7ff00000;
+        const int rowOff = valid ? (y - dstRow0) * dstSt : kOobOffset;
         if constexpr (F == 3)
             store_row24<NTST ? 2 : 0>(stage + 2048 * wib, o, produce, lane, 24 * np, dstR,
-                                      valid ? 3 * x0 + rowOff : 0x7ff00000);
+                                      valid ? 3 * x0 + rowOff : kOobOffset);
         else
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{o[0], o[1], o[2], o[3]}, dstR, stoff, rowOff, NTST ? 2 : 0);
     };
@@ -2425,7 +2425,7 @@ __device__ __forceinline__ void linear_up2_kernel_body(const LinearArgs &a, cons
         pre[i] = load_row(kLo + 1 + i);
 #pragma unroll
         for (int j = 0; j < 2 * F - 2; ++j)  // (2x: one store per row, 3x: two)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, dstR, 0x7ff00000, 0x7ff00000 + 64 * (F * i + j), 0);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, dstR, kOobOffset, kOobOffset + 64 * (F * i + j), 0);
     }
     for (int base = kLo; base < kHi; base += PD) {
         static_for<PD>([&](auto uc) {
@@ -2639,10 +2639,8 @@ hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd,
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
     const int rows = rowEnd - rowBegin;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + t.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + t.dstW;  // stores are relative to dstRow0
-    if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31) || io.srcSt >= (int64_t(1) << 24) ||
-        io.dstSt >= (int64_t(1) << 31) || t.srcH >= (1 << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamTile, io, rowEnd, t.srcW, t.dstW, &sb, &db) || t.srcH >= (1 << 24))
         return hipErrorInvalidValue;
     const int nTx = (t.dstW + t.CT - 1) / t.CT, nTy = (rows + t.TH - 1) / t.TH;
     const uint64_t nTiles = static_cast<uint64_t>(nTx) * static_cast<uint64_t>(nTy) * static_cast<uint64_t>(io.frames);
@@ -2674,9 +2672,9 @@ hipError_t launch_walk(const WalkDev &w, const Io &io, int rowBegin, int rowEnd,
     const TileDev &t = w.t;
     // the buffer range ends at the dword holding the window's last pixel: a dword load that
     // crosses the range end reads as 0, and an aligned dword never crosses a page
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + ((t.srcW + 3) & ~3);
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + t.dstW;  // stores are relative to dstRow0
-    if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31) || io.srcSt >= (int64_t(1) << 24))
+    // (kernels.hpp layout_ok rounds the walker's source row up to whole dwords)
+    int64_t sb, db;
+    if (!layout_ok(kFamWalk, io, rowEnd, t.srcW, t.dstW, &sb, &db))
         return hipErrorInvalidValue;
     const Instance *inst = walk_instance(w);
     if (!inst)
@@ -2918,11 +2916,9 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
             a.tailBands = 0;  // the bands are already short
     }
     // buffer ranges: the source window spans rows [srcRow0, srcRowEnd) of the frame, the destination
-    // band rows [rowBegin, rowEnd); both must be addressable with 31-bit offsets
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + l.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + l.dstW;  // stores are relative to dstRow0
-    if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31) || io.srcSt >= (int64_t(1) << 31) ||
-        io.dstSt >= (int64_t(1) << 31))
+    // band rows [rowBegin, rowEnd); both must end below the offset that drops an access (kernels.hpp)
+    int64_t sb, db;
+    if (!layout_ok(kFamLanczosStream, io, rowEnd, l.srcW, l.dstW, &sb, &db))
         return hipErrorInvalidValue;
     a.srcBytes = static_cast<int>(sb);
     a.dstBytes = static_cast<int>(db);
@@ -3037,9 +3033,8 @@ hipError_t prep_linear(const LinearDev &g, const Io &io, int rowBegin, int rowEn
     bands = (rows + rpb - 1) / rpb;
     LinearArgs &a = P->a;
     a = LinearArgs{g, io, rowBegin, rowEnd, rpb, 0, 0, bands, wpr, np};
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + g.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + g.dstW;  // stores are relative to dstRow0
-    if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31))
+    int64_t sb, db;
+    if (!layout_ok(kFamLinearUp2, io, rowEnd, g.srcW, g.dstW, &sb, &db))
         return hipErrorInvalidValue;
     a.srcBytes = static_cast<int>(sb);
     a.dstBytes = static_cast<int>(db);

@@ -29,7 +29,60 @@ struct Io {
 // function of the *Dev, no device query and no launch.  Parameters a family does not have are 0.
 constexpr int kFamTile = 4, kFamWalk = 5, kFamUp2 = 6, kFamD32 = 7, kFamA32 = 8, kFamU23 = 9, kFamL23 = 10,
               kFamD31 = 11, kFamRyx = 12, kFamRyg = 13;  // iqo_hip.h IQO_KERNEL_* (abi.hip asserts it)
+constexpr int kFamGeneral = 0, kFamLanczosStream = 1, kFamAreaInt = 2, kFamLinearUp2 = 3, kFamPackedTile = 14,
+              kFamPackedGeneral = 15, kFamCount = 16;
 constexpr int kSubRyu = 1;       // Instance::sub within kFamRyg: ryu_kernel (0: ryg_kernel)
+
+// --- address-range limits: the ONE table of what layouts each family's launcher accepts.
+// The buffer-addressed kernels drop an access (a store of a lane that produces nothing, a load of an
+// off-image block that must read 0) by giving it the byte offset kOobOffset, which the hardware's range
+// check refuses as long as the buffer range -- the span below -- does not reach it.  Twice the sentinel
+// plus the largest row offset still fits 32 bits, so `sentinel + row offset` never wraps into the range.
+constexpr int kOobOffset = 0x7ff00000;
+// Largest accepted value of each quantity, 0: unlimited (the family addresses through 64-bit pointers).
+// Span: bytes from the first byte of the source window / destination band to the last byte touched,
+// (rows - 1) * stride + row bytes, the launchers' sb / db and the kernels' buffer range.
+struct LayoutLimits {
+    int64_t srcSpanMax, dstSpanMax, srcStMax, dstStMax;
+};
+constexpr LayoutLimits layout_limits(int family)
+{
+    constexpr int64_t kSentinel = kOobOffset - 1;          // a span the sentinel stays outside of
+    constexpr int64_t kInt = (int64_t(1) << 31) - 1;       // 32-bit signed row offsets
+    constexpr int64_t kMul24 = (int64_t(1) << 24) - 1;     // row * stride by a 24-bit multiply
+    switch (family) {
+    case kFamGeneral:
+    case kFamAreaInt:        // (with linear_d2)
+    case kFamPackedGeneral:
+        return {0, 0, 0, 0};
+    case kFamTile:           // the sentinel only on loads whose value is discarded
+    case kFamPackedTile:
+        return {kInt, kInt, kMul24, kInt};
+    case kFamLanczosStream:  // every streamer body and lanczos_stack: dropped stores, zero-reading loads
+    case kFamLinearUp2:
+        return {kSentinel, kSentinel, kSentinel, kSentinel};
+    case kFamWalk:
+        return {kSentinel, kSentinel, kMul24, kSentinel};
+    default:                 // the exact-ratio and ratio-row kernels (kernels_ratio.hip)
+        return {kSentinel, kSentinel, kMul24, kMul24};
+    }
+}
+// The check every launcher makes (and the C ABI, before a call's first launch): the spans of output rows
+// [.., rowEnd) of `io`, whose rows hold srcRowBytes / dstRowBytes bytes, against the family's limits.
+// The walker's source range ends at the dword that holds the window's last pixel.  *sb / *db: the spans.
+inline bool layout_ok(int family, const Io &io, int rowEnd, int64_t srcRowBytes, int64_t dstRowBytes, int64_t *sb,
+                      int64_t *db)
+{
+    const LayoutLimits m = layout_limits(family);
+    if (family == kFamWalk)
+        srcRowBytes = (srcRowBytes + 3) & ~int64_t(3);
+    if ((m.srcStMax && (io.srcSt < 0 || io.srcSt > m.srcStMax)) || (m.dstStMax && (io.dstSt < 0 || io.dstSt > m.dstStMax)))
+        return false;
+    // (strides of a limited family are below 2^31 here, so the products cannot wrap)
+    *sb = m.srcSpanMax ? static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + srcRowBytes : 0;
+    *db = m.dstSpanMax ? static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + dstRowBytes : 0;  // stores are relative to dstRow0
+    return *sb <= m.srcSpanMax && *db <= m.dstSpanMax;
+}
 struct Instance {
     int family, sub;
     int LZ, P, Q, T, NP, PD, ADJ, CPT, UC, NL, RUN, KM, VY, NV, NT, F, VARIANT;

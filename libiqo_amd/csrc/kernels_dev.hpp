@@ -172,7 +172,7 @@ template <int AUX>
 __device__ __forceinline__ void store_row24(uint8_t *sb, const uint32_t (&o)[6], bool produce, int lane, int nb,
                                             __amdgpu_buffer_rsrc_t dstR, int base)
 {
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     if (produce) {
         u32x2 *p = reinterpret_cast<u32x2 *>(sb + 24 * (lane - 1));
         p[0] = u32x2{o[0], o[1]};

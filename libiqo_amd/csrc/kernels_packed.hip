@@ -294,10 +294,10 @@ __global__ __launch_bounds__(256) void packed_tile_kernel(std::conditional_t<NOR
                 const int kk = valid ? kLo + tt - rr * nF : 0;
                 const int o = static_cast<int>(__umul24(rmin + rr - srcRow0, srcSt)) + srcMis + gb0 + 8 * kk;
                 if (srcA4) {
-                    v[b] = __builtin_amdgcn_raw_buffer_load_b64(srcR, valid ? o : 0x7ff00000, 0, 0);
+                    v[b] = __builtin_amdgcn_raw_buffer_load_b64(srcR, valid ? o : kOobOffset, 0, 0);
                 } else {
                     const int d = o & 3;
-                    const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(srcR, valid ? o - d : 0x7ff00000, 0, 0);
+                    const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(srcR, valid ? o - d : kOobOffset, 0, 0);
                     v[b] = u32x2{__builtin_amdgcn_alignbyte(w.y, w.x, d), __builtin_amdgcn_alignbyte(w.z, w.y, d)};
                 }
                 dstOff[b] = valid ? rr * spitch + 8 * kk : -1;
@@ -628,13 +628,12 @@ hipError_t launch_ptile(const TileDev &t, int channels, const Io &io, const Norm
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
     const int rows = rowEnd - rowBegin;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + static_cast<int64_t>(t.srcW) * channels;
     // stores are relative to dstRow0; a float frame: the last plane's last row
     const int64_t rowB = norm ? static_cast<int64_t>(t.dstW) * (norm->dtype == 1 ? 4 : 2) : static_cast<int64_t>(t.dstW) * channels;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + rowB +
-                       (norm ? static_cast<int64_t>(norm->planes - 1) * norm->planeSt : 0);
-    if (sb >= (int64_t(1) << 31) || db >= (int64_t(1) << 31) || io.srcSt >= (int64_t(1) << 24) ||
-        io.dstSt >= (int64_t(1) << 31) || t.srcH >= (1 << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamPackedTile, io, rowEnd, static_cast<int64_t>(t.srcW) * channels,
+                   rowB + (norm ? static_cast<int64_t>(norm->planes - 1) * norm->planeSt : 0), &sb, &db) ||
+        t.srcH >= (1 << 24))
         return hipErrorInvalidValue;
     const int nTx = (t.dstW + t.CT - 1) / t.CT, nTy = (rows + t.TH - 1) / t.TH;
     const uint64_t nTiles = static_cast<uint64_t>(nTx) * static_cast<uint64_t>(nTy) * static_cast<uint64_t>(io.frames);

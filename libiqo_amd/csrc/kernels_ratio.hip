@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void lanczos_up2_kernel(Up2Args a)
     constexpr int H = NT / 2;        // coefficient pairs of a phase 1 .. F-1 output
     constexpr int OFF = 1 - NT / 2;  // window start relative to x / F (y / F)
     constexpr int OPL = 8 * F;       // output columns per lane
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     const Up2Dev &u = a.u;
     // the rounding bias in a VGPR, the first dot's third operand (sdot2_sv)
     const int bias = static_cast<int>(opaque(1u << 19));
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256) void lanczos_d32_kernel(D32Args a)
     constexpr int U = NW / 3;             // groups per unrolled trip (window slots repeat)
     static_assert(GW >= 3 && NTY <= 8 && NPX <= 5 && PO1 + NTY == GW, "tap structure (mirror-symmetric)");
     static_assert(BX0 >= -4 && 9 + BX0 + 1 + 2 * NPX - 1 <= 15, "column windows within the lane's work pairs");
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     static_assert(U % PD == 0, "prefetch slots repeat within a trip");
     const D32Dev &d = a.d;
     __shared__ int4 park[4][2][8][2];  // per wave, side, row slot: the edge lane's 8 raw sums
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(256) void lanczos_d31_kernel(D31Args a)
     using S = D31Shape<VAR>;
     constexpr int NW = (S::NR + 2) / 3 * 3;  // register window rows (whole groups of 3)
     constexpr int U = NW / 3;                // output rows per unrolled trip (window slots repeat)
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     constexpr int OWN = -S::EB / 2;          // E index of the lane's own pair 0
     static_assert(U % PD == 0, "prefetch slots repeat within a trip");
     static_assert(OWN - S::NL >= 0 && OWN + 6 + S::NL == S::NE, "work pairs: NL from each neighbour");
@@ -836,7 +836,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(T > 20 && !
     constexpr int NW = ((NW0 / P) * Q) % 2 ? NW0 + P : NW0;  // ... and an even number of rows per trip
     constexpr int U = NW / P;                     // groups per unrolled trip (window slots repeat)
     constexpr int UQ = U * Q;                     // output rows per trip
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     constexpr int PADB = 2 * kRyxPadK;            // work-row byte padding left of column 0
     static_assert(U % PD == 0, "prefetch slots repeat within a trip");
     static_assert(UQ % 2 == 0, "work-row buffer parity is static within a trip");
@@ -1236,7 +1236,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(T > 22 || N
     static_assert(CPT >= 2 && CPT <= 4, "output columns per thread");
     static_assert(NL >= 1 && NL <= 4, "rows loaded per output row: 1 (upscales), 2 .. 4 (down to 2:1 .. 4:1)");
     constexpr int NPK = (CPT + 1) / 2;  // packed column pairs (an odd CPT: the last pair repeats its column)
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     constexpr int PADB = 2 * kRyxPadK;  // work-row byte padding left of column 0
     static_assert(PD % 2 == 0 && T >= 2, "the unrolled trip covers both work-row buffers");
     const RygDev &d = a.d;
@@ -1508,7 +1508,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void r
     static_assert(KM >= 2 && KM <= 6, "output rows per window position (rows grow by at most KM)");
     constexpr int NQ = RUN ? RUN : NP;  // pairs read (and dots) per column
     constexpr int NPK = (CPT + 1) / 2;
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     constexpr int PADB = 2 * kRyxPadK;
     constexpr int U = ct_lcm<ct_lcm<T, PD>::value, 2>::value;  // positions per unrolled trip
     const RygDev &d = a.d;
@@ -1791,7 +1791,7 @@ struct U23Args {
 template <int PD>
 __global__ __launch_bounds__(256) void lanczos_u23_kernel(U23Args a)
 {
-    constexpr int NW = 8, U = 4, OOB = 0x7ff00000;
+    constexpr int NW = 8, U = 4, OOB = kOobOffset;
     static_assert(U % PD == 0, "prefetch slots repeat within a trip");
     const U23Dev &d = a.d;
     __shared__ int4 park[4][2][3 * U][3];  // per wave, side, row slot: the edge lane's 12 raw sums
@@ -2009,7 +2009,7 @@ struct L23Args {
 template <int PD>
 __global__ __launch_bounds__(256) void linear_u23_kernel(L23Args a)
 {
-    constexpr int NW = 4, U = 2, OOB = 0x7ff00000;
+    constexpr int NW = 4, U = 2, OOB = kOobOffset;
     static_assert(U % PD == 0, "prefetch slots repeat within a trip");
     const L23Dev &d = a.d;
     const int lane = static_cast<int>(threadIdx.x) & 63;
@@ -2152,7 +2152,7 @@ struct A32Args {
 template <int PD>
 __global__ __launch_bounds__(256) void area_d32_kernel(A32Args a)
 {
-    constexpr int OOB = 0x7ff00000;
+    constexpr int OOB = kOobOffset;
     const A32Dev &d = a.d;
     const int lane = static_cast<int>(threadIdx.x) & 63;
     const int wib = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
@@ -2542,9 +2542,8 @@ hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, i
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + u.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + u.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24) ||
+    int64_t sb, db;
+    if (!layout_ok(kFamUp2, io, rowEnd, u.srcW, u.dstW, &sb, &db) ||
         (u.NT != 4 && u.NT != 6) || (u.F != 2 && u.F != 3) || u.dstW % (8 * u.F) || u.dstW != u.F * u.srcW ||
         u.dstW < 16 * u.F || u.dstH != u.F * u.srcH)
         return hipErrorInvalidValue;
@@ -2589,9 +2588,8 @@ hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.dstW % 8 || d.dstW < 16 || 2 * d.srcW != 3 * d.dstW)
         return hipErrorInvalidValue;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamD32, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return hipErrorInvalidValue;
     // producing lanes per wave: the fewest waves per row, then the fewest lanes that tile the width
     const int lanes = d.dstW / 8;
@@ -2630,9 +2628,8 @@ hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.dstW % 4 || d.dstW < 16 || d.srcW != 3 * d.dstW)
         return hipErrorInvalidValue;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamD31, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return hipErrorInvalidValue;
     // producing lanes per wave (4 outputs each): the fewest waves per row, then the fewest lanes
     // that tile the width
@@ -2669,9 +2666,8 @@ hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.srcW < 16 || d.srcW > 8192 || d.dstW > 4096)
         return hipErrorInvalidValue;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamRyx, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return hipErrorInvalidValue;
     const Instance *inst = ryx_instance(d);
     if (!inst)
@@ -2737,9 +2733,8 @@ hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.srcW < 16 || d.srcW > 8192 || d.dstW > 4096 || !d.rowRec)
         return iqo_ryg_einval(1);
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamRyg, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return iqo_ryg_einval(2);
     const bool byPos = d.nl == 1 && d.posRec;
     const Instance *inst = ryg_instance(d, byPos, d.colRun ? d.run : 0);
@@ -2798,9 +2793,8 @@ hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.dstW % 12 || d.dstW < 24 || 3 * d.srcW != 2 * d.dstW)
         return hipErrorInvalidValue;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamU23, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return hipErrorInvalidValue;
     const int lanes = d.dstW / 12;
     int wpr = (lanes + 61) / 62;
@@ -2835,9 +2829,8 @@ hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.dstW % 12 || d.dstW < 24 || 3 * d.srcW != 2 * d.dstW || d.srcW < 8)
         return hipErrorInvalidValue;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamL23, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return hipErrorInvalidValue;
     const int lanes = d.dstW / 12;
     int wpr = (lanes + 61) / 62;
@@ -2872,9 +2865,8 @@ hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipSuccess;
     if (d.dstW % 8 || d.dstW < 8 || 2 * d.srcW != 3 * d.dstW)
         return hipErrorInvalidValue;
-    const int64_t sb = static_cast<int64_t>(io.srcRowEnd - io.srcRow0 - 1) * io.srcSt + d.srcW;
-    const int64_t db = static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + d.dstW;  // stores are relative to dstRow0
-    if (sb >= 0x7ff00000 || db >= 0x7ff00000 || io.srcSt >= (int64_t(1) << 24) || io.dstSt >= (int64_t(1) << 24))
+    int64_t sb, db;
+    if (!layout_ok(kFamA32, io, rowEnd, d.srcW, d.dstW, &sb, &db))
         return hipErrorInvalidValue;
     const int lanes = d.dstW / 8;
     int wpr = (lanes + 63) / 64;
