@@ -637,7 +637,7 @@ __global__ __launch_bounds__(256, 3) void lanczos_stream_kernel(LanczosArgs a)
 // 16-byte-per-lane LDS-DMA of one source row into LDS bytes [lds, lds + 1024) of this wave, with
 // the default cache policy (fresh data, C2: 2.7 % faster than nontemporal on every row -- the halo
 // rows that neighbouring bands share stay in L2; the block-shared streamer loads the rows no other
-// band reads with dma_row_nt).  M0 is saved and restored inside the statement (it is
+// band reads nontemporal, dma_pair_masked<true>).  M0 is saved and restored inside the statement (it is
 // compiler-reserved).
 __device__ __forceinline__ void dma_row(uint32_t lds, int voff, __amdgpu_buffer_rsrc_t rsrc, int soff)
 {
@@ -663,14 +663,15 @@ __device__ __forceinline__ void dma_row_masked(uint32_t lds, int voff, __amdgpu_
                  : "memory");
 }
 
-#ifndef IQO_SYMB_EDGE_BATCH
-#define IQO_SYMB_EDGE_BATCH 16  // rows of border-column sums parked before a flush (narrow-row scheme; C2 before the line scheme: 64 -> 16 cut write traffic +4.5% -> +2%)
-#endif
-#ifndef IQO_SYMB_NT
-#define IQO_SYMB_NT 2  // block-shared streamer cache policy: nontemporal DMA loads of every row (1) / stores (2);
-                       // stores by default (C2 x256: 0.549 -> 0.544 ms at 24 bands, 0.531 -> 0.520 at 96; nontemporal
-                       // loads of every row lose the halo rows neighbouring bands share in L2: 0.560)
-#endif
+// rows of border-column sums parked before a flush (the block-shared streamer's narrow-row scheme and
+// the stacked streamer; C2 before the line scheme: 64 -> 16 cut write traffic +4.5% -> +2%)
+constexpr int kSymbEdgeBatch = 16;
+// Block-shared streamer cache policy.  Output stores are nontemporal (aux 2: C2 x256 0.549 -> 0.544 ms
+// at 24 bands, 0.531 -> 0.520 at 96).  Of the DMA loads, the rows this band alone reads go nontemporal
+// and the halo rows a neighbouring band reads too keep the default policy (dma_iter's j < ntEnd;
+// nontemporal loads of every row lose the halo rows in L2: 0.560).
+constexpr int kSymbStoreAux = 2;
+constexpr bool kSymbNtPrivateRows = true;
 // The block-shared streamer's border-column scheme: whole 128-byte pieces parked and stored once per
 // trip (rows of >= 256 outputs with >= 16 producing lanes per wave), else the divided bytes stored
 // over the row (narrow rows)
@@ -680,63 +681,14 @@ inline __host__ __device__ bool symb_line(int dstW, int np) { return dstW >= 256
 // (NX > 16, Lanczos-5: 8 border sums per row and side)
 constexpr int symb_edge_bytes(int NY, int NX)
 {
-    return 2 * (NY / 2) * (128 + (NX > 16 ? 32 : 16)) > 2 * IQO_SYMB_EDGE_BATCH * 16
+    return 2 * (NY / 2) * (128 + (NX > 16 ? 32 : 16)) > 2 * kSymbEdgeBatch * 16
                ? 2 * (NY / 2) * (128 + (NX > 16 ? 32 : 16))
-               : 2 * IQO_SYMB_EDGE_BATCH * 16;
+               : 2 * kSymbEdgeBatch * 16;
 }
-// cache policy of dma_row_nt (variant builds, IQO_SYMB_LDPOL): 0 nt, 1 sc0, 2 sc1, 3 sc0 sc1, 4 sc1 nt
-#ifndef IQO_SYMB_LDPOL
-#define IQO_SYMB_LDPOL 0
-#endif
-#if IQO_SYMB_LDPOL == 1
-#define IQO_SYMB_LDPOL_S "sc0"
-#elif IQO_SYMB_LDPOL == 2
-#define IQO_SYMB_LDPOL_S "sc1"
-#elif IQO_SYMB_LDPOL == 3
-#define IQO_SYMB_LDPOL_S "sc0 sc1"
-#elif IQO_SYMB_LDPOL == 4
-#define IQO_SYMB_LDPOL_S "sc1 nt"
-#else
-#define IQO_SYMB_LDPOL_S "nt"
-#endif
-// Instruction-stream levers of the block-shared streamer (round 8; a variant build with one of them
-// set to 0 times it alone, scripts/build_variant.sh; profiles/r08/steady_ab_levers.txt):
-//   IQO_SYMB_DMA1   one exec-masked DMA form per cache policy (dma_pair_masked) in place of the
-//                   {default, nt} x {whole, partial chunk} ladder of four copies per row
-//   IQO_SYMB_FOLD   the host picks the folded vertical pass where the Y table allows it (symb_yfold)
-#ifndef IQO_SYMB_DMA1
-#define IQO_SYMB_DMA1 1
-#endif
-#ifndef IQO_SYMB_FOLD
-#define IQO_SYMB_FOLD 1
-#endif
-#if !IQO_SYMB_DMA1  // (the ladder's two nontemporal forms)
-__device__ __forceinline__ void dma_row_nt(uint32_t lds, int voff, __amdgpu_buffer_rsrc_t rsrc, int soff)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory");
-}
-// dma_row_masked with the cache policy of dma_row_nt
-__device__ __forceinline__ void dma_row_masked_nt(uint32_t lds, int voff, __amdgpu_buffer_rsrc_t rsrc, int soff,
-                                                  uint64_t mask)
-{
-    uint32_t keep;
-    uint64_t save;
-    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %6\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %3, %4, %5 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %0\n\ts_mov_b64 exec, %1"
-                 : "=&s"(keep), "=&s"(save)
-                 : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff), "s"(mask)
-                 : "memory");
-}
-#endif
 
 // The two ring rows of one iteration in one statement, for the lanes of `mask` (all ones except in
 // the wave that owns the row's last, partial chunk): one form serves whole and partial chunks, and
-// exec and M0 are saved and restored once for the pair.  NT: the cache policy of dma_row_nt.
+// exec and M0 are saved and restored once for the pair.  NT: nontemporal (the band's private rows).
 template <bool NT>
 __device__ __forceinline__ void dma_pair_masked(uint32_t lds0, uint32_t lds1, int voff, __amdgpu_buffer_rsrc_t rsrc,
                                                 int soff0, int soff1, uint64_t mask)
@@ -745,8 +697,8 @@ __device__ __forceinline__ void dma_pair_masked(uint32_t lds0, uint32_t lds1, in
     uint64_t save;
     if constexpr (NT)
         asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %8\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "buffer_load_dwordx4 %4, %5, %6 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                     "buffer_load_dwordx4 %4, %5, %7 offen " IQO_SYMB_LDPOL_S " lds\n\ts_mov_b32 m0, %0\n\t"
+                     "buffer_load_dwordx4 %4, %5, %6 offen nt lds\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                     "buffer_load_dwordx4 %4, %5, %7 offen nt lds\n\ts_mov_b32 m0, %0\n\t"
                      "s_mov_b64 exec, %1"
                      : "=&s"(keep), "=&s"(save)
                      : "s"(lds0), "s"(lds1), "v"(voff), "s"(rsrc), "s"(soff0), "s"(soff1), "s"(mask)
@@ -764,6 +716,245 @@ __device__ __forceinline__ void dma_pair_masked(uint32_t lds0, uint32_t lds1, in
 // X coefficient pair p of the symmetric streamers (pairs 8, 9 of Lanczos-5 live in cy[8], cy[9]:
 // kernels.hpp LanczosDev)
 __device__ __forceinline__ uint32_t cxo_at(const LanczosDev &L, int p) { return p < 8 ? L.cxo[p] : L.cy[p]; }
+
+// ---- the pieces the three symmetric streamers share: lanczos_sym_kernel_body (per-wave ring),
+// lanczos_symb_kernel_body (block-shared ring) and lanczos_stack_kernel (frames side by side).  Each
+// body keeps where its ring lives and how dma_iter / read_iter fill and read it, its wait counts and
+// barriers, and its border-column scheme.  `dbg` is the caller's IQO_DBG value (0 in the shipped
+// library; variant builds: 1 no stores, 2 no source loads, 4 no border columns, 8 no border rows,
+// 32 every band top-down).
+
+// odd-aligned u16 pairs Q_1..Q_8 of one row: (b1,b2) (b3,b4) ... (b15,b16), b16 = right
+// neighbour's byte 0
+__device__ __forceinline__ void unpack_odd(uint4 v, uint32_t (&q)[8])
+{
+    const uint32_t r = static_cast<uint32_t>(
+        __builtin_amdgcn_mov_dpp(static_cast<int>(v.x), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
+    q[0] = __builtin_amdgcn_perm(0u, v.x, 0x0c020c01u);
+    q[1] = __builtin_amdgcn_perm(v.y, v.x, 0x0c040c03u);
+    q[2] = __builtin_amdgcn_perm(0u, v.y, 0x0c020c01u);
+    q[3] = __builtin_amdgcn_perm(v.z, v.y, 0x0c040c03u);
+    q[4] = __builtin_amdgcn_perm(0u, v.z, 0x0c020c01u);
+    q[5] = __builtin_amdgcn_perm(v.w, v.z, 0x0c040c03u);
+    q[6] = __builtin_amdgcn_perm(0u, v.w, 0x0c020c01u);
+    q[7] = __builtin_amdgcn_perm(r, v.w, 0x0c040c03u);
+}
+
+// One band: output rows [y0, y1) (rpb rows per band) and the order its source rows are walked in.
+// Odd bands walk bottom-up: a band boundary's halo rows are then read by both bands at the
+// same time (both at their start or both at their end) and the second read hits the
+// Infinity Cache instead of HBM.  The window arithmetic is symmetric, so only the row order
+// changes: walk index t of iteration i is source row rowAt(i, t).
+template <int NY>
+struct SymBand {
+    int y0, y1, dir;
+    int rFirst, rLast;  // first / last source row the band reads
+    int nRows;
+    int srcRow0, srcSt;
+    // the DMA rows of iteration j are linear in j and inside [rFirst, rLast] exactly when j < nRows
+    // (the last iteration brings the band's last two rows), so their offsets are one running
+    // value instead of two range checks per row
+    int dmaSoff0, dmaStep, dmaNext;
+
+    __device__ __forceinline__ SymBand(const LanczosArgs &a, int band, int rpb, int dbg)
+    {
+        y0 = a.rowBegin + band * rpb;
+        y1 = min(y0 + rpb, a.rowEnd);
+        srcSt = static_cast<int>(a.io.srcSt);
+        srcRow0 = a.io.srcRow0;
+        dir = ((band & 1) && !(dbg & 32)) ? -1 : 1;
+        rFirst = 2 * y0 + a.l.offY;
+        rLast = 2 * (y1 - 1) + a.l.offY + NY - 1;
+        nRows = y1 - y0;
+        dmaSoff0 = (rowAt(0, NY - 2) - srcRow0) * srcSt;
+        dmaStep = 2 * dir * srcSt;
+        dmaNext = dir * srcSt;
+    }
+    __device__ __forceinline__ bool empty() const { return y0 >= y1; }
+    // iteration i (output row outRow(i)) brings walk rows NY-2 and NY-1
+    __device__ __forceinline__ int rowAt(int i, int t) const { return dir > 0 ? rFirst + 2 * i + t : rLast - 2 * i - t; }
+    __device__ __forceinline__ int outRow(int i) const { return dir > 0 ? y0 + i : y1 - 1 - i; }
+    // buffer offset of source row r; rows outside the band's range are dropped (no HBM traffic)
+    __device__ __forceinline__ int row_soff(int r) const
+    {
+        return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : kOobOffset;
+    }
+    // the two DMA rows of iteration j
+    __device__ __forceinline__ void dma_soff(int j, int &so0, int &so1) const
+    {
+        const bool in = j < nRows;
+        so0 = in ? dmaSoff0 + j * dmaStep : kOobOffset;
+        so1 = in ? dmaSoff0 + j * dmaStep + dmaNext : kOobOffset;
+    }
+};
+
+// A lane's columns in the per-wave and the block-shared streamer (strip wcol of the row; the stacked
+// streamer lays its lanes out per frame): source bytes [cb, cb + 16), outputs [outX, outX + 8)
+struct SymLane {
+    int x0, cb, outX, voff;
+    bool produce;
+    bool edgeL, edgeR;  // this wave holds the row's left / right border columns (uniform)
+    bool laneL, laneR;  // this lane holds them
+
+    __device__ __forceinline__ SymLane(const LanczosArgs &a, int wcol, int lane, int dbg)
+    {
+        const LanczosDev &L = a.l;
+        const int np = a.np, opw = 8 * np;
+        x0 = max(0, min(wcol * opw, L.dstW - opw));
+        cb = 2 * x0 - 16 + 16 * lane;
+        outX = x0 + (lane - 1) * 8;
+        produce = lane >= 1 && lane <= np && outX < L.dstW;
+        voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : kOobOffset;
+        edgeL = x0 == 0 && !(dbg & 4);
+        edgeR = x0 + opw >= L.dstW && !(dbg & 4);
+        laneL = outX == 0;
+        laneR = outX == L.dstW - 8;
+    }
+};
+
+// Register window of NY unpacked rows: at iteration i the NY walk rows rowAt(i, t) (t < NY) live in
+// slots (2i + t) mod NY; iteration i brings the last two (t = NY-2, NY-1).  Prologue: walk rows
+// 0 .. NY-3 of iteration 0 go straight to VGPRs (window slots 0 .. NY-3), with the default cache
+// policy: the neighbouring band reads the same halo rows.
+template <int NY>
+__device__ __forceinline__ void sym_window_prologue(uint32_t (&win)[NY][8], __amdgpu_buffer_rsrc_t srcR, int voff,
+                                                    const SymBand<NY> &B)
+{
+    uint4 w0[NY - 2];
+#pragma unroll
+    for (int t = 0; t < NY - 2; ++t) {
+        u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(srcR, voff, B.row_soff(B.rowAt(0, t)), 0);
+        w0[t] = make_uint4(q.x, q.y, q.z, q.w);
+    }
+#pragma unroll
+    for (int t = 0; t < NY - 2; ++t)
+        unpack_odd(w0[t], win[t]);
+}
+
+// Symmetric vertical pass of window phase V: pair p = slots (2V + p, 2V + NY - 1 - p) mod NY.
+// Folded Y taps (FOLD, chosen by the host from the plan's own table, symb_yfold): where one
+// outer tap is twice its neighbour, c_{q+1} = 2 c_q, the two pair sums enter as
+// X = P_q + 2 P_{q+1} -- v_add_lshl_u32 and v_add3_u32 on the packed halves, which stay
+// below 2^16 (P <= 510, X <= 1530), so nothing carries between them -- and c_q X replaces
+// c_q P_q + c_{q+1} P_{q+1}: the same sum modulo 2^16 per half, one VALU instruction less per
+// register.  q = 1 for the 10-row window (1 -2 -4 9 28), q = 0 for the 12-row one (1 2 -3 -5 9 28).
+template <int NY, bool C0ONE, bool FOLD, int V>
+__device__ __forceinline__ void sym_vertical(const uint32_t (&win)[NY][8], std::integral_constant<int, V>,
+                                             const uint32_t (&cy)[16], uint32_t (&acc)[8])
+{
+    static_assert(!FOLD || NY == 10 || NY == 12, "folded Y taps: the 10- and 12-row windows (symb_yfold)");
+    constexpr int H = NY / 2;
+    constexpr int FQ = NY == 10 ? 1 : 0;      // first pair of the fold
+    constexpr int PREST = FOLD ? FQ + 2 : 1;  // first pair of the plain multiply-add loop
+    auto fold_sum = [&](int c) {
+        const uint32_t twice = (win[(2 * V + FQ + 1) % NY][c] + win[(2 * V + NY - 2 - FQ) % NY][c]) << 1;
+        return win[(2 * V + FQ) % NY][c] + win[(2 * V + NY - 1 - FQ) % NY][c] + twice;
+    };
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        if constexpr (FOLD && FQ == 0) {
+            acc[c] = pk_mul(fold_sum(c), cy[0]);
+        } else {
+            const uint32_t p0 = win[(2 * V) % NY][c] + win[(2 * V + NY - 1) % NY][c];
+            acc[c] = C0ONE ? p0 : pk_mul(p0, cy[0]);
+            if constexpr (FOLD)
+                acc[c] = pk_mad(fold_sum(c), cy[FQ], acc[c]);
+        }
+    }
+#pragma unroll
+    for (int p = PREST; p < H; ++p)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const uint32_t pp = win[(2 * V + p) % NY][c] + win[(2 * V + NY - 1 - p) % NY][c];
+            acc[c] = pk_mad(pp, cy[p], acc[c]);
+        }
+}
+
+// Border row yy (uniform, rare): rows outside the image were read as zero, so the work values are
+// divided by the row's own coefficient sum
+__device__ __forceinline__ void sym_border_row(uint32_t (&acc)[8], int yy, const LanczosDev &L, int dbg)
+{
+    if ((yy < L.mainBeginY || yy >= L.mainEndY) && !(dbg & 8)) {
+        const bool top = yy < L.mainBeginY;
+        const int bi = top ? yy : yy - L.mainEndY;
+        const uint32_t m = top ? L.yTopM[bi] : L.yBotM[bi];
+        const int sh = top ? L.yTopS[bi] : L.yBotS[bi];
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            acc[c] = ydiv2(acc[c], m, sh);
+    }
+}
+
+// X coefficient pairs in VGPRs (the VOP2 DPP dot needs a VGPR src1)
+template <int NX>
+__device__ __forceinline__ void sym_cvx(const LanczosDev &L, uint32_t (&cvx)[NX / 2])
+{
+#pragma unroll
+    for (int p = 0; p < NX / 2; ++p)
+        cvx[p] = opaque(cxo_at(L, p));
+}
+
+// Horizontal pass of the block-shared and the stacked streamer, output k of the lane's 8: the
+// neighbour pairs enter the dot products through the DPP source modifier of v_dot2c_i32_i16 (no
+// separate v_mov_dpp); each output starts with an own pair (VOP3P form, the bias VGPR as src2).
+// The caller puts an s_nop 1 before the first output: DPP reads of VGPRs the vertical pass just wrote.
+// (The per-wave streamer keeps its own mov_dpp + SGPR-coefficient form.)
+template <int NX, int OFFX>
+__device__ __forceinline__ int sym_dot_dpp(int k, const uint32_t (&acc)[8], const uint32_t (&cvx)[NX / 2], uint32_t bias,
+                                           const LanczosDev &L)
+{
+    constexpr int JLO = (OFFX + 1) / 2;    // output k, pair p reads Q_{k + p + JLO}
+    constexpr int JHI = 7 + NX / 2 + JLO;  // one past the last pair index read
+    static_assert(JLO >= -7 && JHI <= 17, "horizontal taps must stay within the neighbouring lanes");
+    int pFirst = -1;  // first tap whose pair is this lane's own
+#pragma unroll
+    for (int p = 0; p < NX / 2; ++p) {
+        const int j = k + p + JLO;
+        if (pFirst < 0 && j >= 1 && j <= 8)
+            pFirst = p;
+    }
+    int sacc;
+    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(sacc) : "s"(cxo_at(L, pFirst)), "v"(acc[k + pFirst + JLO - 1]),
+        "v"(bias));
+#pragma unroll
+    for (int p = 0; p < NX / 2; ++p) {
+        const int j = k + p + JLO;
+        if (p == pFirst)
+            continue;
+        if (j <= 0)
+            asm("v_dot2c_i32_i16_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf"
+                : "+v"(sacc) : "v"(acc[j + 7]), "v"(cvx[p]));
+        else if (j >= 9)
+            asm("v_dot2c_i32_i16_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf"
+                : "+v"(sacc) : "v"(acc[j - 9]), "v"(cvx[p]));
+        else
+            sacc = sdot2(acc[j - 1], cxo_at(L, p), sacc);
+    }
+    return sacc;
+}
+
+// eight sums -> the lane's 8 output bytes
+__device__ __forceinline__ u32x2 sym_pack(const int (&sum)[8])
+{
+    u32x2 o;
+    o.x = pack_hi(pack_lo(sum[0], sum[1]), sum[2], sum[3]);
+    o.y = pack_hi(pack_lo(sum[4], sum[5]), sum[6], sum[7]);
+    return o;
+}
+
+// Border columns from parked sums: floor(max(S, 0) / D) with the exact multiply-high constants of
+// plan.cpp magic_x (identity for the interior columns of the edge lane), clamped to a byte; the four
+// bytes of side 0 (left, constants 0..3) / 1 (right, 4..7) as one dword
+__device__ __forceinline__ uint32_t edge_fix(const LanczosDev &L, int sv, int k)
+{
+    const uint32_t qq = __umulhi(static_cast<uint32_t>(max(sv, 0)), L.xM[k]) >> L.xT[k];
+    return min(qq, 255u);
+}
+__device__ __forceinline__ uint32_t edge_word(const LanczosDev &L, int4 e, int side)
+{
+    return edge_fix(L, e.x, 4 * side) | (edge_fix(L, e.y, 4 * side + 1) << 8) | (edge_fix(L, e.z, 4 * side + 2) << 16) |
+           (edge_fix(L, e.w, 4 * side + 3) << 24);
+}
 
 
 template <int NY, int NX, int OFFX, int K, bool C0ONE>
@@ -786,38 +977,22 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
     if (g >= a.bands * a.wavesPerRow)
         return;
     const int band = g / a.wavesPerRow, wcol = g - band * a.wavesPerRow;
-    const int y0 = a.rowBegin + band * a.rowsPerBand;
-    const int y1 = min(y0 + a.rowsPerBand, a.rowEnd);
-    if (y0 >= y1)
+    const int dbg = IQO_DBG(a);
+    const SymBand<NY> B(a, band, a.rowsPerBand, dbg);
+    if (B.empty())
         return;
-
-    const int np = a.np, opw = 8 * np;
-    const int x0 = max(0, min(wcol * opw, L.dstW - opw));
-    const int cb = 2 * x0 - 16 + 16 * lane;
-    const int outX = x0 + (lane - 1) * 8;
-    const bool produce = lane >= 1 && lane <= np && outX < L.dstW;
-    const int voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : kOobOffset;
-    const bool edgeL = x0 == 0 && !(IQO_DBG(a) & 4), edgeR = x0 + opw >= L.dstW && !(IQO_DBG(a) & 4);
-    const bool laneL = outX == 0, laneR = outX == L.dstW - 8;
+    const SymLane G(a, wcol, lane, dbg);
+    const bool edgeL = G.edgeL, edgeR = G.edgeR;
+    const int dir = B.dir, nRows = B.nRows;
 
     const uint8_t *srcFrame = a.io.src + static_cast<int64_t>(by) * a.io.srcFrameSt;
     uint8_t *dstFrame = a.io.dst + static_cast<int64_t>(by) * a.io.dstFrameSt;
     const __amdgpu_buffer_rsrc_t srcR =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(srcFrame), 0, a.srcBytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t dstR = __builtin_amdgcn_make_buffer_rsrc(dstFrame, 0, a.dstBytes, 0x00020000);
-    const int srcSt = static_cast<int>(a.io.srcSt), dstSt = static_cast<int>(a.io.dstSt);
-    const int srcRow0 = a.io.srcRow0;
-    const int dbg = IQO_DBG(a);
-    const int svoff = (dbg & 2) ? kOobOffset : voff;
-    const int stoff = (produce && !(dbg & 1)) ? outX : kOobOffset;
-    // Odd bands walk bottom-up: a band boundary's halo rows are then read by both bands at the
-    // same time (both at their start or both at their end) and the second read hits the
-    // Infinity Cache instead of HBM.  The window arithmetic is symmetric, so only the row order
-    // changes: walk index t of iteration i is source row rowAt(i, t).
-    const int dir = ((band & 1) && !(dbg & 32)) ? -1 : 1;
-    const int rFirst = 2 * y0 + L.offY;                 // first source row the band reads
-    const int rLast = 2 * (y1 - 1) + L.offY + NY - 1;  // last source row the band reads
-    const int nRows = y1 - y0;
+    const int dstSt = static_cast<int>(a.io.dstSt);
+    const int svoff = (dbg & 2) ? kOobOffset : G.voff;
+    const int stoff = (G.produce && !(dbg & 1)) ? G.outX : kOobOffset;
     const uint32_t bias = opaque(1u << 19);            // rounding bias (VOP3P src2 of the first dot)
 
     // LDS ring of this wave: iteration i's two rows live in slot i mod K
@@ -825,14 +1000,11 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
                                  (__attribute__((address_space(3))) uint8_t *)ring)) +
                              static_cast<uint32_t>(wib * K * SLOT);
     const uint8_t *ringLane = ring + wib * K * SLOT + lane * 16;
-    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : kOobOffset; };
-    // iteration i (output row y0 + i, or y1 - 1 - i walking up) brings walk rows NY-2 and NY-1
-    auto rowAt = [&](int i, int t) { return dir > 0 ? rFirst + 2 * i + t : rLast - 2 * i - t; };
     auto dma_iter = [&](int i) {
         const uint32_t s = ldsWave + static_cast<uint32_t>((i % K) * SLOT);
-        const int r = rowAt(i, NY - 2);
-        dma_row(s, svoff, srcR, row_soff(r));
-        dma_row(s + 1024, svoff, srcR, row_soff(r + dir));
+        const int r = B.rowAt(i, NY - 2);
+        dma_row(s, svoff, srcR, B.row_soff(r));
+        dma_row(s + 1024, svoff, srcR, B.row_soff(r + dir));
     };
     auto read_iter = [&](int i, uint4 &r0, uint4 &r1) {
         const uint8_t *p = ringLane + (i % K) * SLOT;
@@ -840,59 +1012,23 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
         r1 = *reinterpret_cast<const uint4 *>(p + 1024);
     };
 
-    // odd-aligned u16 pairs Q_1..Q_8 of one row: (b1,b2) (b3,b4) ... (b15,b16), b16 = right
-    // neighbour's byte 0
-    auto unpack_odd = [&](uint4 v, uint32_t (&q)[8]) {
-        const uint32_t r = static_cast<uint32_t>(
-            __builtin_amdgcn_mov_dpp(static_cast<int>(v.x), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
-        q[0] = __builtin_amdgcn_perm(0u, v.x, 0x0c020c01u);
-        q[1] = __builtin_amdgcn_perm(v.y, v.x, 0x0c040c03u);
-        q[2] = __builtin_amdgcn_perm(0u, v.y, 0x0c020c01u);
-        q[3] = __builtin_amdgcn_perm(v.z, v.y, 0x0c040c03u);
-        q[4] = __builtin_amdgcn_perm(0u, v.z, 0x0c020c01u);
-        q[5] = __builtin_amdgcn_perm(v.w, v.z, 0x0c040c03u);
-        q[6] = __builtin_amdgcn_perm(0u, v.w, 0x0c020c01u);
-        q[7] = __builtin_amdgcn_perm(r, v.w, 0x0c040c03u);
-    };
-
-    // Border columns of rows [yb, yb + n) from the parked sums: floor(max(S, 0) / D) with the
-    // exact multiply-high constants of plan.cpp magic_x (identity for the interior columns of the
-    // edge lane), clamped to a byte, one dword per row and side -- stored after the row's main
-    // store, so it overwrites those 4 bytes.
+    // Border columns of rows [yb, yb + n) from the parked sums (edge_word), one dword per row and
+    // side -- stored after the row's main store, so it overwrites those 4 bytes.
     auto flush_edges = [&](int yb, int n) {
-        auto fix = [&](int sv, int k) {
-            const uint32_t qq = __umulhi(static_cast<uint32_t>(max(sv, 0)), L.xM[k]) >> L.xT[k];
-            return min(qq, 255u);
-        };
         const int rowOff = (yb + dir * lane - a.io.dstRow0) * dstSt;
         if (edgeL) {
-            const int4 e = edgeSum[wib][0][lane & 63];
-            const uint32_t w = fix(e.x, 0) | (fix(e.y, 1) << 8) | (fix(e.z, 2) << 16) | (fix(e.w, 3) << 24);
+            const uint32_t w = edge_word(L, edgeSum[wib][0][lane & 63], 0);
             __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 1) ? rowOff : kOobOffset, 0, 0);
         }
         if (edgeR) {
-            const int4 e = edgeSum[wib][1][lane & 63];
-            const uint32_t w = fix(e.x, 4) | (fix(e.y, 5) << 8) | (fix(e.z, 6) << 16) | (fix(e.w, 7) << 24);
+            const uint32_t w = edge_word(L, edgeSum[wib][1][lane & 63], 1);
             __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 1) ? rowOff + L.dstW - 4 : kOobOffset,
                                                   0, 0);
         }
     };
 
-    // window: at iteration i the NY walk rows rowAt(i, t) (t < NY) live in slots (2i + t) mod NY;
-    // iteration i brings the last two (t = NY-2, NY-1)
     uint32_t win[NY][8];
-    {
-        // walk rows 0 .. NY-3 of iteration 0 go straight to VGPRs (window slots 0 .. NY-3)
-        uint4 w0[NY - 2];
-#pragma unroll
-        for (int t = 0; t < NY - 2; ++t) {
-            u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(srcR, svoff, row_soff(rowAt(0, t)), 0);
-            w0[t] = make_uint4(q.x, q.y, q.z, q.w);
-        }
-#pragma unroll
-        for (int t = 0; t < NY - 2; ++t)
-            unpack_odd(w0[t], win[t]);
-    }
+    sym_window_prologue(win, srcR, svoff, B);
     // ring prologue: DMA(0) .. DMA(K-2), each followed by a dropped store, so that from the first
     // iteration on the vm counter sees the steady-state order DMA(j), S(j-K+1)
 #pragma unroll
@@ -906,7 +1042,7 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
         const int i = base + v;  // iteration = output row y0 + i
         if (i >= nRows)
             return;  // past the band end (uniform)
-        const int yy = dir > 0 ? y0 + i : y1 - 1 - i;
+        const int yy = B.outRow(i);
         // DMA(i) retired: after it come 2 DMAs per later iteration (K-2 of them) and the
         // K-1 stores of iterations i-K+1 .. i-1
         wait_vmcnt<3 * K - 5>();
@@ -916,32 +1052,12 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
         unpack_odd(n0, win[(2 * v + NY - 2) % NY]);
         unpack_odd(n1, win[(2 * v + NY - 1) % NY]);
 
-        // vertical: pair p = slots (2v + p, 2v + NY - 1 - p) mod NY
         uint32_t acc[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t p0 = win[(2 * v) % NY][c] + win[(2 * v + NY - 1) % NY][c];
-            acc[c] = C0ONE ? p0 : pk_mul(p0, L.cy[0]);
-        }
-#pragma unroll
-        for (int p = 1; p < H; ++p)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t pp = win[(2 * v + p) % NY][c] + win[(2 * v + NY - 1 - p) % NY][c];
-                acc[c] = pk_mad(pp, L.cy[p], acc[c]);
-            }
-        if ((yy < L.mainBeginY || yy >= L.mainEndY) && !(dbg & 8)) {
-            // border row (uniform, rare): rows outside the image were read as zero
-            const bool top = yy < L.mainBeginY;
-            const int bi = top ? yy : yy - L.mainEndY;
-            const uint32_t m = top ? L.yTopM[bi] : L.yBotM[bi];
-            const int sh = top ? L.yTopS[bi] : L.yBotS[bi];
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                acc[c] = ydiv2(acc[c], m, sh);
-        }
+        sym_vertical<NY, C0ONE, false>(win, uc, L.cy, acc);
+        sym_border_row(acc, yy, L, dbg);
 
-        // Q_j for j in [JLO, JHI): own pairs 1..8, neighbours' by DPP
+        // horizontal, this streamer's own form (mov_dpp copies, SGPR coefficients; the other two
+        // share sym_dot_dpp): Q_j for j in [JLO, JHI), own pairs 1..8, neighbours' by DPP
         uint32_t q[JHI - JLO];
 #pragma unroll
         for (int j = JLO; j < JHI; ++j) {
@@ -964,17 +1080,14 @@ __device__ __forceinline__ void lanczos_sym_kernel_body(const LanczosArgs &a, co
                 sacc = sdot2(q[k + p], L.cxo[p], sacc);
             sum[k] = sacc;
         }
-        u32x2 o;
-        o.x = pack_hi(pack_lo(sum[0], sum[1]), sum[2], sum[3]);
-        o.y = pack_hi(pack_lo(sum[4], sum[5]), sum[6], sum[7]);
-        __builtin_amdgcn_raw_buffer_store_b64(o, dstR, stoff, (yy - a.io.dstRow0) * dstSt, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(sym_pack(sum), dstR, stoff, (yy - a.io.dstRow0) * dstSt, 0);
         if (edgeL || edgeR) {
             // border columns: the edge lane parks its 4 raw sums (k < 4 left, k >= 4 right) in
             // LDS; every 64 rows and at the band end one pass divides them, one row per lane
             const int slot = i & 63;
-            if (edgeL && laneL)
+            if (edgeL && G.laneL)
                 edgeSum[wib][0][slot] = make_int4(sum[0], sum[1], sum[2], sum[3]);
-            if (edgeR && laneR)
+            if (edgeR && G.laneR)
                 edgeSum[wib][1][slot] = make_int4(sum[4], sum[5], sum[6], sum[7]);
             if (slot == 63 || i == nRows - 1) {
                 __builtin_amdgcn_wave_barrier();
@@ -1007,10 +1120,6 @@ __global__ __launch_bounds__(256, 4) void lanczos_sym_kernel(LanczosArgs a)
 // row before it is refilled.  Waves with fewer chunks than CPW DMA into a sink so the vm-counter
 // pattern is the same in every wave.
 
-#ifndef IQO_SYMB_EXP
-#define IQO_SYMB_EXP 0  // timing experiments in variant builds (wrong output): 1 no vertical MACs,
-                        // 2 half the horizontal dots, 3 / 4 dot2 / dot4 in place of the MACs
-#endif
 template <int NY, int NX, int OFFX, int K, int CPW, bool C0ONE, bool LINE, bool FOLD = false>
 __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, const unsigned bx, const unsigned by,
                                                          const int rpb)
@@ -1018,7 +1127,6 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     constexpr int H = NY / 2;                   // symmetric pairs = iterations per window cycle
     static_assert(NY % 2 == 0 && NX % 2 == 0 && (OFFX & 1), "even taps, odd first X column");
     static_assert(K >= 3 && CPW >= 1, "ring depth (the LDS look-ahead needs K >= 3)");
-    static_assert(!FOLD || NY == 10 || NY == 12, "folded Y taps: the 10- and 12-row windows (symb_yfold)");
     // LDS look-ahead: iteration i reads the ring slot of iteration i+1 (its latency hides behind
     // iteration i's arithmetic), so it waits for DMA(i+1): after this wave's DMA(i+1) come the
     // store of iteration i-K+2 and the 2*CPW DMAs + 1 store of each of iterations i+2 .. i+K-2
@@ -1027,13 +1135,10 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     // K == H: the ring period equals the window period, so every slot index in the unrolled body
     // is a compile-time constant (immediate LDS offsets, no per-row slot arithmetic)
     constexpr bool CSLOT = K == H;
-    constexpr int JLO = (OFFX + 1) / 2;         // output k, pair p reads Q_{k + p + JLO}
-    constexpr int JHI = 7 + NX / 2 + JLO;       // one past the last pair index read
-    static_assert(JLO >= -7 && JHI <= 17, "horizontal taps must stay within the neighbouring lanes");
     // LDS: ring [K slots][2 rows][rowPitch] | edge area (symb_edge_bytes) | 1 KiB DMA sink (only
     // when some wave has fewer chunks than CPW).  Edge area: line scheme [2][H][128] parked bytes +
-    // int4 [2][H] border sums; narrow rows int4 edgeSum [2][EDGE_BATCH]
-    constexpr int EB = IQO_SYMB_EDGE_BATCH;
+    // int4 [2][H] border sums; narrow rows int4 edgeSum [2][kSymbEdgeBatch]
+    constexpr int EB = kSymbEdgeBatch;
     static_assert((EB & (EB - 1)) == 0 && EB <= 64, "edge batch: power of two <= 64");
     static_assert(H <= 8, "line-scheme flush: 4 rows per 8-B store, two stores");
     // Lanczos-5 (20 X taps): 5 border columns per side, so the edge lane parks all 8 of its sums
@@ -1055,20 +1160,14 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     const int wib = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
     const int wpr = a.wavesPerRow;                 // = waves of this workgroup
     const int band = static_cast<int>(bx), wcol = wib;
-    const int y0 = a.rowBegin + band * rpb;  // rpb: rows per band of this workgroup's band size
-    const int y1 = min(y0 + rpb, a.rowEnd);
-    if (y0 >= y1)
+    const int dbg = IQO_DBG(a);
+    const SymBand<NY> B(a, band, rpb, dbg);  // rpb: rows per band of this workgroup's band size
+    if (B.empty())
         return;  // whole workgroup
-
-    const int np = a.np, opw = 8 * np;
-    const int x0 = max(0, min(wcol * opw, L.dstW - opw));
-    const int cb = 2 * x0 - 16 + 16 * lane;
-    const int outX = x0 + (lane - 1) * 8;
-    const bool produce = lane >= 1 && lane <= np && outX < L.dstW;
-    const int voff = (lane <= np + 1 && cb >= 0 && cb < L.srcW) ? cb : kOobOffset;  // prologue loads
-    const int ldsCol = lane <= np + 1 ? 16 + cb : 0;  // this lane's 16 bytes in an LDS ring row
-    const bool edgeL = x0 == 0 && !(IQO_DBG(a) & 4), edgeR = x0 + opw >= L.dstW && !(IQO_DBG(a) & 4);
-    const bool laneL = outX == 0, laneR = outX == L.dstW - 8;
+    const SymLane G(a, wcol, lane, dbg);  // (G.voff: the prologue loads)
+    const bool edgeL = G.edgeL, edgeR = G.edgeR, laneL = G.laneL, laneR = G.laneR, produce = G.produce;
+    const int outX = G.outX, dir = B.dir, nRows = B.nRows;
+    const int ldsCol = lane <= a.np + 1 ? 16 + G.cb : 0;  // this lane's 16 bytes in an LDS ring row
     // Border columns, line scheme (rows of >= 256 outputs, >= 16 producing lanes): the lanes holding
     // the row's first and last 128 output bytes (the edge lanes among them) do not store; they park
     // their 8 bytes per row in LDS, the edge lane also its 4 raw border sums, and once per trip of H
@@ -1088,42 +1187,19 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     const __amdgpu_buffer_rsrc_t srcR =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(srcFrame), 0, a.srcBytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t dstR = __builtin_amdgcn_make_buffer_rsrc(dstFrame, 0, a.dstBytes, 0x00020000);
-    const int srcSt = static_cast<int>(a.io.srcSt), dstSt = static_cast<int>(a.io.dstSt);
-    const int srcRow0 = a.io.srcRow0;
-    const int dbg = IQO_DBG(a);
-    const int svoff = (dbg & 2) ? kOobOffset : voff;
+    const int dstSt = static_cast<int>(a.io.dstSt);
+    const int svoff = (dbg & 2) ? kOobOffset : G.voff;
     const int stoff = (produce && !(dbg & 1) && !regL && !regR) ? outX : kOobOffset;
-#ifdef IQO_SYMB_STAUX
-    constexpr int STNT = IQO_SYMB_STAUX;  // variant builds: store cache policy bits (1 sc0, 2 nt, 16 sc1)
-#else
-    constexpr int STNT = (IQO_SYMB_NT & 2) ? 2 : 0;  // store cache policy (aux: nt)
-#endif
-    // Odd bands walk bottom-up: a band boundary's halo rows are then read by both bands at the
-    // same time (both at their start or both at their end) and the second read hits the
-    // Infinity Cache instead of HBM.  The window arithmetic is symmetric, so only the row order
-    // changes: walk index t of iteration i is source row rowAt(i, t).
-    const int dir = ((band & 1) && !(dbg & 32)) ? -1 : 1;
-    const int rFirst = 2 * y0 + L.offY;                 // first source row the band reads
-    const int rLast = 2 * (y1 - 1) + L.offY + NY - 1;  // last source row the band reads
-    const int nRows = y1 - y0;
+    constexpr int STNT = kSymbStoreAux;
     const uint32_t bias = opaque(1u << 19);            // rounding bias (VOP3P src2 of the first dot)
-    uint32_t cvx[NX / 2];  // X coefficient pairs in VGPRs (the VOP2 DPP dot needs a VGPR src1)
-#pragma unroll
-    for (int p = 0; p < NX / 2; ++p)
-        cvx[p] = opaque(cxo_at(L, p));
+    uint32_t cvx[NX / 2];
+    sym_cvx<NX>(L, cvx);
 
     // shared LDS ring: iteration i's two walk rows live in slot i mod K; chunk c (1 KiB of
     // source columns [1024c, 1024c + 1024) at LDS column 16 + 1024c) is DMA'd by wave c mod wpr
     const uint32_t ldsBase = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
         (__attribute__((address_space(3))) uint8_t *)lds));
     const uint8_t *ringLane = ring + ldsCol;
-    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : kOobOffset; };
-    // iteration i (output row y0 + i, or y1 - 1 - i walking up) brings walk rows NY-2 and NY-1
-    auto rowAt = [&](int i, int t) { return dir > 0 ? rFirst + 2 * i + t : rLast - 2 * i - t; };
-    // the DMA rows of iteration j are linear in j and inside [rFirst, rLast] exactly when j < nRows
-    // (the last iteration brings the band's last two rows), so their offsets are one running
-    // value instead of two range checks per row
-    const int dmaSoff0 = (rowAt(0, NY - 2) - srcRow0) * srcSt, dmaStep = 2 * dir * srcSt, dmaNext = dir * srcSt;
     // Cache policy by row class: the band's first NY-2 walk rows (the VGPR prologue loads) and its
     // last NY-2 (DMA iterations j >= nRows - (NY-2)/2) are the halo rows a neighbouring band reads
     // too, so they keep the default policy and stay in L2; the rows of every other DMA iteration
@@ -1132,10 +1208,9 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     const int ntEnd = nRows - (NY - 2) / 2;
     auto dma_iter = [&](int j, int slot) {
         const uint32_t s = ldsBase + static_cast<uint32_t>(slot * slotBytes);
-        const bool in = j < nRows;
-        const bool nt = (IQO_SYMB_NT & 1) || j < ntEnd;  // uniform
-        const int so0 = in ? dmaSoff0 + j * dmaStep : kOobOffset;
-        const int so1 = in ? dmaSoff0 + j * dmaStep + dmaNext : kOobOffset;
+        const bool nt = kSymbNtPrivateRows && j < ntEnd;  // uniform
+        int so0, so1;
+        B.dma_soff(j, so0, so1);
 #pragma unroll
         for (int jj = 0; jj < CPW; ++jj) {
             const int c = wcol + jj * wpr;
@@ -1144,7 +1219,6 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
             const int v = (real && col < L.srcW && !(dbg & 2)) ? col : kOobOffset;
             const uint32_t d0 = real ? s + 16 + 1024 * c : ldsBase + sinkLds;
             const uint32_t d1 = real ? d0 + rowPitch : d0;
-#if IQO_SYMB_DMA1
             // one form: the wave's mask is all ones unless this is the row's last, partial chunk
             // (uniform and the same in every row, so the compiler hoists it out of the row loop)
             const uint64_t m = (real && c == a.chunks - 1) ? lastMask : ~0ull;
@@ -1152,23 +1226,6 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
                 dma_pair_masked<true>(d0, d1, v, srcR, so0, so1, m);
             else
                 dma_pair_masked<false>(d0, d1, v, srcR, so0, so1, m);
-#else
-            if (real && c == a.chunks - 1 && lastLanes < 64) {  // uniform
-                if (nt) {
-                    dma_row_masked_nt(d0, v, srcR, so0, lastMask);
-                    dma_row_masked_nt(d1, v, srcR, so1, lastMask);
-                } else {
-                    dma_row_masked(d0, v, srcR, so0, lastMask);
-                    dma_row_masked(d1, v, srcR, so1, lastMask);
-                }
-            } else if (nt) {
-                dma_row_nt(d0, v, srcR, so0);
-                dma_row_nt(d1, v, srcR, so1);
-            } else {
-                dma_row(d0, v, srcR, so0);
-                dma_row(d1, v, srcR, so1);
-            }
-#endif
         }
     };
     auto read_iter = [&](int slot, uint4 &r0, uint4 &r1) {
@@ -1177,39 +1234,16 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         r1 = *reinterpret_cast<const uint4 *>(p + rowPitch);
     };
 
-    // odd-aligned u16 pairs Q_1..Q_8 of one row: (b1,b2) (b3,b4) ... (b15,b16), b16 = right
-    // neighbour's byte 0
-    auto unpack_odd = [&](uint4 v, uint32_t (&q)[8]) {
-        const uint32_t r = static_cast<uint32_t>(
-            __builtin_amdgcn_mov_dpp(static_cast<int>(v.x), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
-        q[0] = __builtin_amdgcn_perm(0u, v.x, 0x0c020c01u);
-        q[1] = __builtin_amdgcn_perm(v.y, v.x, 0x0c040c03u);
-        q[2] = __builtin_amdgcn_perm(0u, v.y, 0x0c020c01u);
-        q[3] = __builtin_amdgcn_perm(v.z, v.y, 0x0c040c03u);
-        q[4] = __builtin_amdgcn_perm(0u, v.z, 0x0c020c01u);
-        q[5] = __builtin_amdgcn_perm(v.w, v.z, 0x0c040c03u);
-        q[6] = __builtin_amdgcn_perm(0u, v.w, 0x0c020c01u);
-        q[7] = __builtin_amdgcn_perm(r, v.w, 0x0c040c03u);
-    };
-
-    // Border columns of rows [yb, yb + n) from the parked sums: floor(max(S, 0) / D) with the
-    // exact multiply-high constants of plan.cpp magic_x (identity for the interior columns of the
-    // edge lane), clamped to a byte, one dword per row and side -- stored after the row's main
-    // store, so it overwrites those 4 bytes.
+    // Narrow-row scheme: border columns of rows [yb, yb + n) from the parked sums (edge_word), one
+    // dword per row and side -- stored after the row's main store, so it overwrites those 4 bytes.
     auto flush_edges = [&](int yb, int n) {
-        auto fix = [&](int sv, int k) {
-            const uint32_t qq = __umulhi(static_cast<uint32_t>(max(sv, 0)), L.xM[k]) >> L.xT[k];
-            return min(qq, 255u);
-        };
         const int rowOff = (yb + dir * lane - a.io.dstRow0) * dstSt;
         if (edgeL) {
-            const int4 e = edgeSum[0][lane & (EB - 1)];
-            const uint32_t w = fix(e.x, 0) | (fix(e.y, 1) << 8) | (fix(e.z, 2) << 16) | (fix(e.w, 3) << 24);
+            const uint32_t w = edge_word(L, edgeSum[0][lane & (EB - 1)], 0);
             __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 65) ? rowOff : kOobOffset, 0, 0);
         }
         if (edgeR) {
-            const int4 e = edgeSum[1][lane & (EB - 1)];
-            const uint32_t w = fix(e.x, 4) | (fix(e.y, 5) << 8) | (fix(e.z, 6) << 16) | (fix(e.w, 7) << 24);
+            const uint32_t w = edge_word(L, edgeSum[1][lane & (EB - 1)], 1);
             __builtin_amdgcn_raw_buffer_store_b32(w, dstR, lane < n && !(dbg & 65) ? rowOff + L.dstW - 4 : kOobOffset,
                                                   0, 0);
         }
@@ -1219,10 +1253,6 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
     // parked border sums into the first (left) / last (right) 4 parked bytes, then 16 lanes per row
     // store the 128-byte pieces, 4 rows per instruction.  LDS accesses of one wave complete in order.
     auto flush_lines = [&](int yb, int n) {
-        auto fix = [&](int sv, int k) {
-            const uint32_t qq = __umulhi(static_cast<uint32_t>(max(sv, 0)), L.xM[k]) >> L.xT[k];
-            return min(qq, 255u);
-        };
         // the lane index through an opaque register: the per-lane addresses below are recomputed
         // here instead of being hoisted out of the row loop, where they would stay live beside the
         // row window (spills)
@@ -1247,9 +1277,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
                                         (fix8(e1.w, k0 + 7) << 24);
                     *reinterpret_cast<u32x2 *>(lineBuf + (side * H + lane) * 128 + (side ? 120 : 0)) = u32x2{w0, w1};
                 } else {
-                    const int4 e = lineSum[side * H + lane];
-                    const uint32_t w = fix(e.x, 4 * side) | (fix(e.y, 4 * side + 1) << 8) |
-                                       (fix(e.z, 4 * side + 2) << 16) | (fix(e.w, 4 * side + 3) << 24);
+                    const uint32_t w = edge_word(L, lineSum[side * H + lane], side);
                     *reinterpret_cast<uint32_t *>(lineBuf + (side * H + lane) * 128 + (side ? 124 : 0)) = w;
                 }
             }
@@ -1264,22 +1292,8 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         }
     };
 
-    // window: at iteration i the NY walk rows rowAt(i, t) (t < NY) live in slots (2i + t) mod NY;
-    // iteration i brings the last two (t = NY-2, NY-1)
     uint32_t win[NY][8];
-    {
-        // walk rows 0 .. NY-3 of iteration 0 go straight to VGPRs (window slots 0 .. NY-3); the
-        // default cache policy: the neighbouring band reads the same halo rows
-        uint4 w0[NY - 2];
-#pragma unroll
-        for (int t = 0; t < NY - 2; ++t) {
-            u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(srcR, svoff, row_soff(rowAt(0, t)), 0);
-            w0[t] = make_uint4(q.x, q.y, q.z, q.w);
-        }
-#pragma unroll
-        for (int t = 0; t < NY - 2; ++t)
-            unpack_odd(w0[t], win[t]);
-    }
+    sym_window_prologue(win, srcR, svoff, B);
     // zero pad left of every ring row (the left halo lane of the first strip reads it)
     for (int r = static_cast<int>(threadIdx.x); r < 2 * K; r += static_cast<int>(blockDim.x))
         *reinterpret_cast<uint4 *>(ring + r * rowPitch) = make_uint4(0u, 0u, 0u, 0u);
@@ -1306,7 +1320,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         const int i = base + v;  // iteration = output row y0 + i
         if (i >= nRows)
             return;  // past the band end (uniform)
-        const int yy = dir > 0 ? y0 + i : y1 - 1 - i;
+        const int yy = B.outRow(i);
         // this wave's DMA(i+1) retired (WAITLA younger vm ops); the barrier publishes slot i+1
         // and retires every wave's reads of slot i-1, which DMA(i+K-1) refills
         wait_vmcnt<WAITLA>();
@@ -1321,109 +1335,15 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         n0 = m0;
         n1 = m1;
 
-        // vertical: pair p = slots (2v + p, 2v + NY - 1 - p) mod NY
         uint32_t acc[8];
-        // Folded Y taps (FOLD, chosen by the host from the plan's own table, symb_yfold): where one
-        // outer tap is twice its neighbour, c_{q+1} = 2 c_q, the two pair sums enter as
-        // X = P_q + 2 P_{q+1} -- v_add_lshl_u32 and v_add3_u32 on the packed halves, which stay
-        // below 2^16 (P <= 510, X <= 1530), so nothing carries between them -- and c_q X replaces
-        // c_q P_q + c_{q+1} P_{q+1}: the same sum modulo 2^16 per half, one VALU instruction less per
-        // register.  q = 1 for the 10-row window (1 -2 -4 9 28), q = 0 for the 12-row one (1 2 -3 -5 9 28).
-        constexpr int FQ = NY == 10 ? 1 : 0;      // first pair of the fold
-        constexpr int PREST = FOLD ? FQ + 2 : 1;  // first pair of the plain multiply-add loop
-        auto fold_sum = [&](int c) {
-            const uint32_t twice = (win[(2 * v + FQ + 1) % NY][c] + win[(2 * v + NY - 2 - FQ) % NY][c]) << 1;
-            return win[(2 * v + FQ) % NY][c] + win[(2 * v + NY - 1 - FQ) % NY][c] + twice;
-        };
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            if constexpr (FOLD && FQ == 0) {
-                acc[c] = pk_mul(fold_sum(c), L.cy[0]);
-            } else {
-                const uint32_t p0 = win[(2 * v) % NY][c] + win[(2 * v + NY - 1) % NY][c];
-                acc[c] = C0ONE ? p0 : pk_mul(p0, L.cy[0]);
-                if constexpr (FOLD)
-                    acc[c] = pk_mad(fold_sum(c), L.cy[FQ], acc[c]);
-            }
-        }
-#if IQO_SYMB_EXP == 1 // timing experiment (variant build, wrong output): pair sums only, no MACs
-#pragma unroll
-        for (int p = 1; p < H; ++p)
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                acc[c] += win[(2 * v + p) % NY][c];
-#elif IQO_SYMB_EXP == 3  // timing experiment: v_dot2c in place of v_pk_mad_u16
-#pragma unroll
-        for (int p = 1; p < H; ++p)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t pp = win[(2 * v + p) % NY][c] + win[(2 * v + NY - 1 - p) % NY][c];
-                acc[c] = static_cast<uint32_t>(sdot2(pp, L.cy[p], static_cast<int>(acc[c])));
-            }
-#elif IQO_SYMB_EXP == 4  // timing experiment: v_dot4 in place of v_pk_mad_u16
-#pragma unroll
-        for (int p = 1; p < H; ++p)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t pp = win[(2 * v + p) % NY][c] + win[(2 * v + NY - 1 - p) % NY][c];
-                asm("v_dot4_i32_i8 %0, %1, %2, %0" : "+v"(acc[c]) : "s"(L.cy[p]), "v"(pp));
-            }
-#else
-#pragma unroll
-        for (int p = PREST; p < H; ++p)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t pp = win[(2 * v + p) % NY][c] + win[(2 * v + NY - 1 - p) % NY][c];
-                acc[c] = pk_mad(pp, L.cy[p], acc[c]);
-            }
-#endif
-        if ((yy < L.mainBeginY || yy >= L.mainEndY) && !(dbg & 8)) {
-            // border row (uniform, rare): rows outside the image were read as zero
-            const bool top = yy < L.mainBeginY;
-            const int bi = top ? yy : yy - L.mainEndY;
-            const uint32_t m = top ? L.yTopM[bi] : L.yBotM[bi];
-            const int sh = top ? L.yTopS[bi] : L.yBotS[bi];
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                acc[c] = ydiv2(acc[c], m, sh);
-        }
-
-        // horizontal: the neighbour pairs enter the dot products through the DPP source modifier
-        // of v_dot2c_i32_i16 (no separate v_mov_dpp); each output starts with an own pair (VOP3P
-        // form, the bias VGPR as src2).  s_nop 1: DPP reads of VGPRs the vertical pass just wrote.
+        sym_vertical<NY, C0ONE, FOLD>(win, uc, L.cy, acc);
+        sym_border_row(acc, yy, L, dbg);
         int sum[8];
         asm volatile("s_nop 1" ::: "memory");
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            int pFirst = -1;  // first tap whose pair is this lane's own
-#pragma unroll
-            for (int p = 0; p < NX / 2; ++p) {
-                const int j = k + p + JLO;
-                if (pFirst < 0 && j >= 1 && j <= 8)
-                    pFirst = p;
-            }
-            int sacc;
-            asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(sacc) : "s"(cxo_at(L, pFirst)), "v"(acc[k + pFirst + JLO - 1]),
-                "v"(bias));
-#pragma unroll
-            for (int p = 0; p < NX / 2; ++p) {
-                const int j = k + p + JLO;
-                if (p == pFirst || (IQO_SYMB_EXP == 2 && (p & 1)))  // experiment 2: half the taps (timing only)
-                    continue;
-                if (j <= 0)
-                    asm("v_dot2c_i32_i16_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf"
-                        : "+v"(sacc) : "v"(acc[j + 7]), "v"(cvx[p]));
-                else if (j >= 9)
-                    asm("v_dot2c_i32_i16_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf"
-                        : "+v"(sacc) : "v"(acc[j - 9]), "v"(cvx[p]));
-                else
-                    sacc = sdot2(acc[j - 1], cxo_at(L, p), sacc);
-            }
-            sum[k] = sacc;
-        }
-        u32x2 o;
-        o.x = pack_hi(pack_lo(sum[0], sum[1]), sum[2], sum[3]);
-        o.y = pack_hi(pack_lo(sum[4], sum[5]), sum[6], sum[7]);
+        for (int k = 0; k < 8; ++k)
+            sum[k] = sym_dot_dpp<NX, OFFX>(k, acc, cvx, bias, L);
+        const u32x2 o = sym_pack(sum);
         __builtin_amdgcn_raw_buffer_store_b64(o, dstR, stoff, (yy - a.io.dstRow0) * dstSt, STNT);
         if (LINE && (edgeL || edgeR)) {
             // line scheme: slot v of the trip (its first row is iteration base, slot 0)
@@ -1468,7 +1388,7 @@ __device__ __forceinline__ void lanczos_symb_kernel_body(const LanczosArgs &a, c
         // the band's last trip was partial: its nRows % H rows are still parked
         const int baseLast = nRows - nRows % H;
         __builtin_amdgcn_wave_barrier();
-        flush_lines(dir > 0 ? y0 + baseLast : y1 - 1 - baseLast, nRows % H);
+        flush_lines(B.outRow(baseLast), nRows % H);
     }
 
     wait_vmcnt<0>();  // no LDS-DMA may still be writing when the wave (and its LDS) retires
@@ -1552,9 +1472,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
     static_assert(K == H && CPW >= 1, "ring depth = window period");
     constexpr int WAIT = 1 + (K - 2) * (2 * CPW + 1);
     constexpr int WAITLA = 1 + (K - 3) * (2 * CPW + 1);
-    constexpr int JLO = (OFFX + 1) / 2;
-    constexpr int EB = 16;                      // rows of parked border-column sums per flush
-    constexpr int PITCH = 2048;                 // ring row: 128 virtual lanes x 16 B
+    constexpr int EB = kSymbEdgeBatch;          // rows of parked border-column sums per flush
+    constexpr int PITCH = 2048;               // ring row: 128 virtual lanes x 16 B
     constexpr int SLOT = 2 * PITCH;
     constexpr int OOB = kOobOffset;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -1566,10 +1485,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
     const int lane = static_cast<int>(threadIdx.x) & 63;
     const int wib = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
     const int band = static_cast<int>(blockIdx.x);
-    const int y0 = a.rowBegin + band * a.rowsPerBand;
-    const int y1 = min(y0 + a.rowsPerBand, a.rowEnd);
-    if (y0 >= y1)
+    // variant builds: 1 no stores, 2 no source loads (timing only); the other flags stay off here
+    const int dbg = IQO_DBG(a) & 3;
+    const SymBand<NY> B(a, band, a.rowsPerBand, dbg);
+    if (B.empty())
         return;  // whole workgroup
+    const int dir = B.dir, nRows = B.nRows;
     const int np = a.np, fpw = a.fpw;
     const int f0 = static_cast<int>(blockIdx.y) * fpw;
     const int nF = min(fpw, a.frames - f0);     // frames of this workgroup
@@ -1587,35 +1508,23 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
     // this lane's frame (prologue loads, stores); the DMAs address each frame separately
     const __amdgpu_buffer_rsrc_t srcL =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(srcBase + Fc * sFrameSt), 0, a.srcBytes, 0x00020000);
-    const int srcSt = static_cast<int>(a.io.srcSt), dstSt = static_cast<int>(a.io.dstSt);
-    const int srcRow0 = a.io.srcRow0;
-    const int dbg = IQO_DBG(a);  // variant builds: 1 no stores, 2 no source loads (timing only)
+    const int dstSt = static_cast<int>(a.io.dstSt);
     const int voff = mine && !(dbg & 2) ? 16 * k : OOB;
     const uint32_t ldsLane = static_cast<uint32_t>(16 * v);
-    const int dir = (band & 1) ? -1 : 1;
-    const int rFirst = 2 * y0 + L.offY;
-    const int rLast = 2 * (y1 - 1) + L.offY + NY - 1;
-    const int nRows = y1 - y0;
     const uint32_t bias = opaque(1u << 19);
     uint32_t cvx[NX / 2];
-#pragma unroll
-    for (int p = 0; p < NX / 2; ++p)
-        cvx[p] = opaque(L.cxo[p]);
+    sym_cvx<NX>(L, cvx);
 
     const uint32_t ldsBase = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
         (__attribute__((address_space(3))) uint8_t *)lds));
     const uint8_t *ringLane = ring + ldsLane;
-    auto row_soff = [&](int r) { return (r >= rFirst && r <= rLast) ? (r - srcRow0) * srcSt : OOB; };
-    auto rowAt = [&](int i, int t) { return dir > 0 ? rFirst + 2 * i + t : rLast - 2 * i - t; };
-    const int dmaSoff0 = (rowAt(0, NY - 2) - srcRow0) * srcSt, dmaStep = 2 * dir * srcSt, dmaNext = dir * srcSt;
     const uint64_t rowMask = np >= 64 ? ~0ull : (1ull << np) - 1ull;  // the lanes of one frame row
     // DMA of iteration j: frame slot c = wib + 2 jj (its rows at virtual lanes 1 + (np + 1) c ...);
     // slots past the workgroup's frames DMA into the sink so every wave's vm count is the same
     auto dma_iter = [&](int j, int slot) {
         const uint32_t s = ldsBase + static_cast<uint32_t>(slot * SLOT);
-        const bool in = j < nRows;
-        const int so0 = in ? dmaSoff0 + j * dmaStep : OOB;
-        const int so1 = in ? dmaSoff0 + j * dmaStep + dmaNext : OOB;
+        int so0, so1;
+        B.dma_soff(j, so0, so1);
 #pragma unroll
         for (int jj = 0; jj < CPW; ++jj) {
             const int c = wib + 2 * jj;
@@ -1634,56 +1543,28 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
         r0 = *reinterpret_cast<const uint4 *>(p);
         r1 = *reinterpret_cast<const uint4 *>(p + PITCH);
     };
-    auto unpack_odd = [&](uint4 w, uint32_t (&q)[8]) {
-        const uint32_t r = static_cast<uint32_t>(
-            __builtin_amdgcn_mov_dpp(static_cast<int>(w.x), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
-        q[0] = __builtin_amdgcn_perm(0u, w.x, 0x0c020c01u);
-        q[1] = __builtin_amdgcn_perm(w.y, w.x, 0x0c040c03u);
-        q[2] = __builtin_amdgcn_perm(0u, w.y, 0x0c020c01u);
-        q[3] = __builtin_amdgcn_perm(w.z, w.y, 0x0c040c03u);
-        q[4] = __builtin_amdgcn_perm(0u, w.z, 0x0c020c01u);
-        q[5] = __builtin_amdgcn_perm(w.w, w.z, 0x0c040c03u);
-        q[6] = __builtin_amdgcn_perm(0u, w.w, 0x0c020c01u);
-        q[7] = __builtin_amdgcn_perm(r, w.w, 0x0c040c03u);
-    };
     // border columns of rows [yb, yb + n) of the frames whose edge lanes this wave holds: lane i
     // rewrites row yb + dir i of one (frame, side) per pass
     const int vLo = 62 * wib + 1, vHi = 62 * wib + 62;  // this wave's producing virtual lanes
     auto flush_edges = [&](int yb, int n) {
-        auto fix = [&](int sv, int kk) {
-            const uint32_t qq = __umulhi(static_cast<uint32_t>(max(sv, 0)), L.xM[kk]) >> L.xT[kk];
-            return min(qq, 255u);
-        };
         const int rowOff = (yb + dir * lane - a.io.dstRow0) * dstSt;
         for (int G = 0; G < nF; ++G) {
             const int vL = 1 + (np + 1) * G, vR = vL + np - 1;
             uint8_t *dstF = dstBase + G * dFrameSt;
             const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(dstF, 0, a.dstBytes, 0x00020000);
             if (vL >= vLo && vL <= vHi) {
-                const int4 e = edgeSum[(G * 2 + 0) * EB + (lane & (EB - 1))];
-                const uint32_t w = fix(e.x, 0) | (fix(e.y, 1) << 8) | (fix(e.z, 2) << 16) | (fix(e.w, 3) << 24);
+                const uint32_t w = edge_word(L, edgeSum[(G * 2 + 0) * EB + (lane & (EB - 1))], 0);
                 __builtin_amdgcn_raw_buffer_store_b32(w, dr, lane < n && !(dbg & 1) ? rowOff : OOB, 0, 0);
             }
             if (vR >= vLo && vR <= vHi) {
-                const int4 e = edgeSum[(G * 2 + 1) * EB + (lane & (EB - 1))];
-                const uint32_t w = fix(e.x, 4) | (fix(e.y, 5) << 8) | (fix(e.z, 6) << 16) | (fix(e.w, 7) << 24);
+                const uint32_t w = edge_word(L, edgeSum[(G * 2 + 1) * EB + (lane & (EB - 1))], 1);
                 __builtin_amdgcn_raw_buffer_store_b32(w, dr, lane < n && !(dbg & 1) ? rowOff + L.dstW - 4 : OOB, 0, 0);
             }
         }
     };
 
     uint32_t win[NY][8];
-    {
-        uint4 w0[NY - 2];
-#pragma unroll
-        for (int t = 0; t < NY - 2; ++t) {
-            u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(srcL, voff, row_soff(rowAt(0, t)), 0);
-            w0[t] = make_uint4(q.x, q.y, q.z, q.w);
-        }
-#pragma unroll
-        for (int t = 0; t < NY - 2; ++t)
-            unpack_odd(w0[t], win[t]);
-    }
+    sym_window_prologue(win, srcL, voff, B);
     // zero every ring byte the DMAs never write (frame gaps, both ends) once
     for (int i = static_cast<int>(threadIdx.x); i < K * 2 * 128; i += static_cast<int>(blockDim.x)) {
         const int vv = i & 127;
@@ -1711,7 +1592,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
         const int i = base + vv;
         if (i >= nRows)
             return;
-        const int yy = dir > 0 ? y0 + i : y1 - 1 - i;
+        const int yy = B.outRow(i);
         wait_vmcnt<WAITLA>();
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -1724,61 +1605,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void l
         n0 = m0;
         n1 = m1;
         uint32_t acc[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t p0 = win[(2 * vv) % NY][c] + win[(2 * vv + NY - 1) % NY][c];
-            acc[c] = C0ONE ? p0 : pk_mul(p0, L.cy[0]);
-        }
-#pragma unroll
-        for (int p = 1; p < H; ++p)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t pp = win[(2 * vv + p) % NY][c] + win[(2 * vv + NY - 1 - p) % NY][c];
-                acc[c] = pk_mad(pp, L.cy[p], acc[c]);
-            }
-        if (yy < L.mainBeginY || yy >= L.mainEndY) {
-            const bool top = yy < L.mainBeginY;
-            const int bi = top ? yy : yy - L.mainEndY;
-            const uint32_t m = top ? L.yTopM[bi] : L.yBotM[bi];
-            const int sh = top ? L.yTopS[bi] : L.yBotS[bi];
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                acc[c] = ydiv2(acc[c], m, sh);
-        }
+        sym_vertical<NY, C0ONE, false>(win, uc, L.cy, acc);
+        sym_border_row(acc, yy, L, dbg);
         int sum[8];
         asm volatile("s_nop 1" ::: "memory");
 #pragma unroll
-        for (int kx = 0; kx < 8; ++kx) {
-            int pFirst = -1;
-#pragma unroll
-            for (int p = 0; p < NX / 2; ++p) {
-                const int j = kx + p + JLO;
-                if (pFirst < 0 && j >= 1 && j <= 8)
-                    pFirst = p;
-            }
-            int sacc;
-            asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(sacc) : "s"(L.cxo[pFirst]), "v"(acc[kx + pFirst + JLO - 1]),
-                "v"(bias));
-#pragma unroll
-            for (int p = 0; p < NX / 2; ++p) {
-                const int j = kx + p + JLO;
-                if (p == pFirst)
-                    continue;
-                if (j <= 0)
-                    asm("v_dot2c_i32_i16_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf"
-                        : "+v"(sacc) : "v"(acc[j + 7]), "v"(cvx[p]));
-                else if (j >= 9)
-                    asm("v_dot2c_i32_i16_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf"
-                        : "+v"(sacc) : "v"(acc[j - 9]), "v"(cvx[p]));
-                else
-                    sacc = sdot2(acc[j - 1], L.cxo[p], sacc);
-            }
-            sum[kx] = sacc;
-        }
-        u32x2 o;
-        o.x = pack_hi(pack_lo(sum[0], sum[1]), sum[2], sum[3]);
-        o.y = pack_hi(pack_lo(sum[4], sum[5]), sum[6], sum[7]);
-        __builtin_amdgcn_raw_buffer_store_b64(o, dstL, stoff, (yy - a.io.dstRow0) * dstSt, 0);
+        for (int kx = 0; kx < 8; ++kx)
+            sum[kx] = sym_dot_dpp<NX, OFFX>(kx, acc, cvx, bias, L);
+        __builtin_amdgcn_raw_buffer_store_b64(sym_pack(sum), dstL, stoff, (yy - a.io.dstRow0) * dstSt, 0);
         // border columns: park the edge lanes' raw sums, flush every EB rows (every wave holds an
         // edge lane of some frame, so the branch is per frame inside flush_edges)
         const int slot = i & (EB - 1);
@@ -2777,7 +2611,7 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
         const bool one = (l.cy[0] & 0xffffu) == 1u;
         fpw = std::min(fpwMax, io.frames);
         const int scpw = (fpw + 1) / 2;
-        ldsBytes = l.NY / 2 * 4096 + scpw * 2 * 2 * IQO_SYMB_EDGE_BATCH * 16 + 1024;
+        ldsBytes = l.NY / 2 * 4096 + scpw * 2 * 2 * kSymbEdgeBatch * 16 + 1024;
         block = 128;
 #define IQO_STACK_C(NY_, NX_, OX_, ONE_)                                                                \
     (scpw == 1 ? reinterpret_cast<const void *>(lanczos_stack_kernel<NY_, NX_, OX_, NY_ / 2, 1, ONE_>)         \
@@ -2797,12 +2631,9 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
         if (l.NY == 16 && !line)
             return hipErrorInvalidValue;  // Lanczos-5: 5 border columns need the line scheme's 8 edge sums
         ldsBytes = K * 2 * rowPitch + symb_edge_bytes(l.NY, l.NX) + (cpw * wpr > chunks ? 1024 : 0);
-#ifdef IQO_EXP_WGCU  // experiment builds: fewer workgroups per CU by inflating the LDS allocation
-        if (const char *ev = getenv("IQO_EXP_WGCU"))
-            if (atoi(ev) > 0)
-                ldsBytes = std::max(ldsBytes, 163840 / atoi(ev) - 256);
-#endif
         block = 64 * wpr;
+        // the folded vertical pass where this plan's own Y table has the doubling relation
+        const bool fold = symb_yfold(l);
 #define IQO_SYMB_L(NY_, NX_, OX_, K_, CPW_, ONE_, FOLD_)                                                \
     (line ? reinterpret_cast<const void *>(lanczos_symb_kernel<NY_, NX_, OX_, K_, CPW_, ONE_, true, FOLD_>)      \
           : reinterpret_cast<const void *>(lanczos_symb_kernel<NY_, NX_, OX_, K_, CPW_, ONE_, false, FOLD_>))
@@ -2811,14 +2642,8 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
 #define IQO_SYMB_F(NY_, NX_, OX_, ONE_, FOLD_)                                                          \
     (K == 3 ? IQO_SYMB_K(NY_, NX_, OX_, 3, ONE_, FOLD_) : K == 4 ? IQO_SYMB_K(NY_, NX_, OX_, 4, ONE_, FOLD_) \
             : IQO_SYMB_K(NY_, NX_, OX_, 5, ONE_, FOLD_))
-#define IQO_SYMB(NY_, NX_, OX_, ONE_) IQO_SYMB_F(NY_, NX_, OX_, ONE_, false)
-#if IQO_SYMB_FOLD
-        // the folded vertical pass where this plan's own Y table has the doubling relation
-        const bool fold = symb_yfold(l);
-#define IQO_SYMB_Y(NY_, NX_, OX_, ONE_) (fold ? IQO_SYMB_F(NY_, NX_, OX_, ONE_, true) : IQO_SYMB(NY_, NX_, OX_, ONE_))
-#else
-#define IQO_SYMB_Y(NY_, NX_, OX_, ONE_) IQO_SYMB(NY_, NX_, OX_, ONE_)
-#endif
+#define IQO_SYMB_Y(NY_, NX_, OX_, ONE_)                                                                 \
+    (fold ? IQO_SYMB_F(NY_, NX_, OX_, ONE_, true) : IQO_SYMB_F(NY_, NX_, OX_, ONE_, false))
         if (l.NY == 10 && one)
             kern = IQO_SYMB_Y(10, 12, -5, true);
         else if (l.NY == 10)
@@ -2826,12 +2651,11 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
         else if (l.NY == 12)
             kern = IQO_SYMB_Y(12, 16, -7, false);  // Lanczos-4 2:1 (3 waves per SIMD: the 12-row window)
         else if (l.NY == 16)
-            kern = IQO_SYMB(16, 20, -9, false);  // Lanczos-5 2:1 (2 waves per SIMD: the 16-row window)
+            kern = IQO_SYMB_F(16, 20, -9, false, false);  // Lanczos-5 2:1 (2 waves per SIMD: the 16-row window)
         else
-            kern = IQO_SYMB(8, 8, -3, false);
+            kern = IQO_SYMB_F(8, 8, -3, false, false);
 #undef IQO_SYMB_Y
 #undef IQO_SYMB_F
-#undef IQO_SYMB
 #undef IQO_SYMB_K
 #undef IQO_SYMB_L
     } else if (l.sym) {
@@ -2864,29 +2688,11 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
             const int64_t want = static_cast<int64_t>(l.rounds > 0 ? l.rounds : 6) * (resident / 2);
             bands = static_cast<int>(std::min<int64_t>((want + groups - 1) / groups, std::max(1, rows / 16)));
         } else if (shared && l.rounds >= 0) {
-            // block-shared ring: about `rounds` rounds of resident workgroups (default 6), bands of
-            // >= 16 rows.  On fresh data more, shorter bands beat the one-round makespan optimum
-            // (C2 x128: 8 bands 0.305 ms, 24 0.296, 48 0.294): workgroups that start and finish at
-            // different times spread their requests over the memory channels, and the halo rows of
-            // neighbouring bands (same XCD) come from L2
-            // Round 4: and bands of at most ~22 rows for 1920-wide outputs, up to 48 for narrower ones
-            // (C2 x256: 24 bands 0.525 ms, 48 0.510, 96 0.515, 135 0.530; C1 x4096 (320 columns):
-            // 2 bands 0.385, 5 0.366, 10 0.378).  Shorter bands keep the concurrently read source
-            // window compact; longer ones pay less per-band prologue, which weighs more on narrow rows.
-            // Round 5, at a steady GPU clock (after the power-management transient a streaming
-            // launch starts with, profiles/r05/clock_transient.txt): the Lanczos-2/3 windows (NY <= 10)
-            // want bands of ~12 rows on rows of >= 640 outputs -- C2 x1024 1.936 ms at 50 bands of 22
-            // rows, 1.879 at 90 of 12 (frac 0.686 -> 0.706), x256 0.495 -> 0.480; 1080p -> 540p
-            // Lanczos-2 -2.6 % -- and ~24 on narrower rows (C1 x4096: 5 bands 0.331 ms, 10 bands
-            // 0.318, 20 bands 0.324); the 12- and 16-row windows keep ~22-row bands (Lanczos-4 4K:
-            // 50 bands 0.267 ms, 90 bands 0.270), their per-band halo being larger
-            // (profiles/r05/steady_streamer_bands.txt)
-            // Round 7, with the band's private rows loaded nontemporal: a private row costs less
-            // than a halo row, and the 10-row window (8 halo rows per band) wants bands of 15 rows
-            // -- C2 x1024 1.833 -> 1.790 ms and 1.847 -> 1.817 on two boxes, x256 0.463 -> 0.453;
-            // Lanczos-3 1080p -> 540p and 1440p -> 720p -2 % too -- while the 8-row window keeps 12
-            // (Lanczos-2 4K -> 1080p x512: 12 rows 0.859 ms, 14 0.871, 15 0.887;
-            // profiles/r07/band_sweep.txt)
+            // block-shared ring: at least `rounds` rounds of resident workgroups (default 6), and
+            // bands of at most rowsMax and at least rowsMin rows.  rowsMax: 15 rows for the 10-row
+            // window and 12 for the 8-row one on rows of >= 640 outputs, 24 on narrower rows; the
+            // 12- and 16-row windows 22 rows at 1920 outputs, up to 48 on narrower rows.
+            // (How each figure was measured: DESIGN.md, "The C2 streamer in detail", Bands.)
             const int64_t want = static_cast<int64_t>(l.rounds > 0 ? l.rounds : 6) * (resident / wpr);
             const int64_t byRounds = (want + io.frames - 1) / io.frames;
             const int rowsMax = l.NY <= 10 ? (l.dstW >= 640 ? (l.NY == 10 ? 15 : 12) : 24)

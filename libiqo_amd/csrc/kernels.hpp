@@ -454,7 +454,7 @@ struct LanczosDev {
 #endif
 };
 // Block-shared symmetric streamer: whether the plan's own Y table lets two outer pair sums fold into
-// one multiply-add (kernels.hip lanczos_symb_kernel_body, FOLD): a tap that is twice its neighbour,
+// one multiply-add (kernels.hip sym_vertical, FOLD): a tap that is twice its neighbour,
 // compared as the u16 values the kernel multiplies by -- cy[2] == 2 cy[1] in the 10-row window
 // (Lanczos-3: 1 -2 -4 9 28), cy[1] == 2 cy[0] in the 12-row one (Lanczos-4: 1 2 -3 -5 9 28).
 // Nothing is taken from the degree; a table without the relation runs the unfolded pass.

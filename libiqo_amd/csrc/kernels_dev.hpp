@@ -44,14 +44,9 @@ __device__ __forceinline__ unsigned xcd_spread(unsigned L, unsigned n)
 // a frame's neighbouring bands still share one XCD's L2 while the 8 XCDs work on 8 neighbouring
 // chunks at a time, not on 8 ranges 1/8 of the batch apart as with xcd_spread (C2 x256: 0.479 ->
 // 0.467 ms, x1024 1.871 -> 1.845, profiles/r06/xcd_chunks.txt).  A bijection of [0, n): the blocks
-// past the last whole round of 8 chunks fall back to xcd_spread.  (Variant builds with
-// -DIQO_XCD_SPREAD keep xcd_spread, for A/B.)
+// past the last whole round of 8 chunks fall back to xcd_spread.
 __device__ __forceinline__ unsigned xcd_chunks(unsigned L, unsigned C, unsigned n)
 {
-#ifdef IQO_XCD_SPREAD
-    (void)C;
-    return xcd_spread(L, n);
-#else
     C = C ? C : 1u;
     const unsigned x = L & 7u, idx = L >> 3, full = n / (8u * C);
     if (idx < full * C) {
@@ -60,7 +55,6 @@ __device__ __forceinline__ unsigned xcd_chunks(unsigned L, unsigned C, unsigned 
     }
     const unsigned base = 8u * full * C;
     return base + xcd_spread(L - base, n - base);
-#endif
 }
 
 // 16-byte streaming load with the nontemporal hint (source pixels are read once per band; Area

@@ -1,9 +1,12 @@
 #!/bin/bash
 # Build an experimental library variant: scripts/build_variant.sh NAME "-DFLAG=1 ..."
 # -> libiqo_amd/variants/NAME.so (every .hip translation unit recompiled with the flags, the host
-# objects shared).  -DIQO_VARIANT_DEBUG enables the wrong-output timing flags ("debug_flags").
-# KERNELS_ONLY=1 recompiles kernels.hip alone and links the in-tree build's other objects (flags
-# that only kernels.hip reads, e.g. IQO_SYMB_*).
+# objects shared).  -DIQO_VARIANT_DEBUG enables the wrong-output timing flags ("debug_flags") and
+# the workgroup trace (scripts/probes/wg_trace.py): the one experiment mechanism the sources keep.
+# Any other experiment is a scratch edit of the source built with this script; the macros of the
+# settled streamer experiments are gone ("Retired build-time switches").
+# KERNELS_ONLY=1 recompiles kernels.hip alone and links the in-tree build's other objects (edits
+# or flags that only kernels.hip reads).
 set -e
 cd "$(dirname "$0")/../libiqo_amd"
 make -s build/plan.o build/cpu_generic.o build/resizers.o
