@@ -741,6 +741,90 @@ typedef struct {
 int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
                             iqo_hip_roi_box_layout *out);
 
+/* ---- Crop-and-resize boxes of NV12 / I420 frames straight to RGB bytes or normalised tensors, in one launch
+ * (decoder frames on the device, a detector's boxes, a classifier's input).
+ *
+ * A roi yuv plan fixes method, degree, layout (IQO_ROI_NV12: a Y plane and an interleaved UV plane;
+ * IQO_ROI_I420: Y, U and V planes) and dstW x dstH.  A call brings nFrames frames of frameW x frameH, both
+ * even: the planes of frame 0 as device pointers (dV is not read for NV12), their row strides srcStY and
+ * srcStUV, and ONE srcFrameSt that is applied to every plane pointer, as the iqo_hip_resize_nv12_*_device
+ * entries do; and nRois boxes with x, y, w, h even and w, h >= 2.  Output i is, bit for bit:
+ *
+ *   Y    = iqo::{Lanczos,Area,Linear}Resizer (w,   h   -> dstW, dstH), pixel scale 1, on the box of the Y plane
+ *   U, V = the same resizer                  (w/2, h/2 -> dstW, dstH), pixel scale 1, on the box of U and of V
+ *          (rows y/2 .. (y+h)/2, columns x/2 .. (x+w)/2: chroma centred, filtered to the full output grid)
+ *   RGB  = the integer matrix of `standard` (IQO_CS_*, above) of the three bytes of a pixel
+ *
+ * which is what an NV12 / I420 plan (w, h -> dstW, dstH) with IQO_CHROMA_FULL gives on the cropped frame.  The
+ * box is the whole image for border purposes, in luma and in chroma; no byte outside the rows of the given
+ * planes is read; IQO_ROI_FLIP mirrors the output columns.  Source pointers and strides need no alignment.
+ *
+ *   iqo_hip_resize_rois_yuv_rgb_device   `channels` 3 or 4 bytes per pixel, byte c = order[c] of {0 R, 1 G, 2 B,
+ *                                        3 the constant 255}, rows dstSt and outputs dstRoiSt bytes apart
+ *   iqo_hip_resize_rois_yuv_norm_device  the planar floats of iqo_hip_resize_rois_norm_device of the 3-channel
+ *                                        pixel (R, G, B): norm->order[p] in 0 .. 2
+ *
+ * Validity, box by box (*badRoi names the first offending box).  IQO_HIP_EINVAL: an odd x, y, w or h; w < 2 or
+ * h < 2; a box outside the frame; a frame index >= nFrames; an unknown flag bit; a Lanczos box whose luma axes
+ * (w, h) or chroma axes (w/2, h/2) iqo_hip_plan_lanczos rejects (Lanczos-3 with h = 2 and dstH = 24: chroma
+ * 1 -> 24).  IQO_HIP_EUNSUP: Linear with dstW > w or dstH > h (chroma above 2x: the rule of IQO_CHROMA_FULL, so
+ * every accepted Linear box has a pinned answer); more than IQO_HIP_ROI_MAX_TAPS taps on any of the four axes; a
+ * band row -- the Y, U and V work rows and both sets of Y-tap records, (pitchY + 2 pitchC) x 4 + (nYpY + nYpC) x 8
+ * bytes -- over IQO_HIP_ROI_LDS_BYTES; more than 2^31 workgroups; frameH*srcStY >= 2^31 or
+ * (frameH/2)*srcStUV >= 2^31; a capturing stream.  *badRoi = -1 and IQO_HIP_EINVAL for an argument of the call
+ * itself: odd frameW or frameH, null pointers, srcStY < frameW, srcStUV < frameW (NV12) or frameW/2 (I420), an
+ * unknown standard, channels other than 3 or 4, an order entry outside 0 .. 3, and everything
+ * iqo_hip_resize_rois_device (the norm form: with 3 source channels) rejects of the destination.  On any error
+ * nothing is launched and the destination is untouched; nRois == 0 returns IQO_HIP_OK after the checks.
+ *
+ * The plan works as a roi plan: two pinned arenas with a device arena each, one hipMemcpyAsync, one launch and
+ * one event per call, no allocation in steady state, NOT thread-safe.  Its table cache serves luma and chroma:
+ * a chroma axis of length n shares the table of a luma axis of length n. */
+enum { IQO_ROI_NV12 = 0, IQO_ROI_I420 = 1 };
+typedef struct iqo_hip_roi_yuv_plan iqo_hip_roi_yuv_plan;
+int iqo_hip_plan_rois_yuv(int method, unsigned degree, int layout, size_t dstW, size_t dstH, int device,
+                          iqo_hip_roi_yuv_plan **out);
+void iqo_hip_roi_yuv_plan_destroy(iqo_hip_roi_yuv_plan *plan);
+int iqo_hip_resize_rois_yuv_rgb_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                       size_t nFrames, size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV,
+                                       size_t srcFrameSt, const uint8_t *dY, const uint8_t *dUorUV,
+                                       const uint8_t *dV /* NULL for NV12 */, int standard, int channels,
+                                       const int *order, size_t dstSt, size_t dstRoiSt, uint8_t *dDst, void *stream,
+                                       int *badRoi);
+int iqo_hip_resize_rois_yuv_norm_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                        size_t nFrames, size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV,
+                                        size_t srcFrameSt, const uint8_t *dY, const uint8_t *dUorUV,
+                                        const uint8_t *dV /* NULL for NV12 */, int standard, const iqo_hip_norm *norm,
+                                        size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt, void *dDst, void *stream,
+                                        int *badRoi);
+/* Host-only CPU twins (host pointers, no stream, no device): the same arena walked in plain C++ with the
+ * kernel's integer formulas.  Same status codes and *badRoi. */
+int iqo_host_resize_rois_yuv_rgb(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                 const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcStY,
+                                 size_t srcStUV, size_t srcFrameSt, const uint8_t *y, const uint8_t *uOrUV,
+                                 const uint8_t *v, int standard, int channels, const int *order, size_t dstSt,
+                                 size_t dstRoiSt, uint8_t *dst, int *badRoi);
+int iqo_host_resize_rois_yuv_norm(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                  const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcStY,
+                                  size_t srcStUV, size_t srcFrameSt, const uint8_t *y, const uint8_t *uOrUV,
+                                  const uint8_t *v, int standard, const iqo_hip_norm *norm, size_t dstSt,
+                                  size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi);
+/* Host-only: the arena of such a call on tightly packed frames.  xTables / yTables count every distinct table
+ * once, whether luma, chroma or both use it. */
+int iqo_host_roi_yuv_arena_stats(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                 const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                 iqo_hip_roi_arena_stats *stats, int *badRoi);
+/* Host-only: the layout of a one-box call, the box being the whole of a tightly packed w x h frame. */
+typedef struct {
+    int rows;                /* output rows per workgroup */
+    unsigned workgroups;     /* ceil(dstH / rows) */
+    size_t ldsBytes;         /* rows x ((pitchDw + 2 pitchDwC) x 4 + (nYp + nYpC) x 8) */
+    int nYp, np, pitchDw;    /* luma: Y taps per row (even), X coefficient pairs, work-row pitch in dwords */
+    int nYpC, npC, pitchDwC; /* chroma: the same of the (w/2, h/2) tables */
+} iqo_hip_roi_yuv_box_layout;
+int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
+                                iqo_hip_roi_yuv_box_layout *out);
+
 /* Drop-in classes (iqo::LanczosResizer, AreaResizer, LinearResizer): how many objects this process constructed on the
  * HIP backend, and on the CPU backend (no gfx950 device) plus the resize() calls of HIP objects that fell back to the
  * CPU (a device failure, or a call the HIP path rejected).  IQO_REQUIRE_HIP=1 makes any CPU use abort;

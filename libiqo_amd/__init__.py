@@ -19,7 +19,8 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "host_yuv_to_rgb", "yuv_rgb_workspace_bytes", "CHROMA_REPLICATE", "CHROMA_FULL", "CHROMA_MODES",
            "host_chroma_full_kernel", "host_rgb_to_yuv", "host_rgb_to_yuv420", "rgb_yuv_workspace_bytes",
            "SOURCE_ORDERS", "RoiResizer", "Roi", "RoiArenaStats", "host_resize_rois", "host_roi_arena_stats",
-           "RoiBoxLayout", "host_roi_box_layout", "ROI_MAX_TAPS", "ROI_LDS_BYTES"]
+           "RoiBoxLayout", "host_roi_box_layout", "ROI_MAX_TAPS", "ROI_LDS_BYTES", "YuvRoiResizer", "ROI_LAYOUTS",
+           "RoiYuvBoxLayout", "host_resize_rois_yuv", "host_roi_yuv_arena_stats", "host_roi_yuv_box_layout"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -106,6 +107,14 @@ class RoiBoxLayout(ctypes.Structure):
 
 
 ROI_MAX_TAPS, ROI_LDS_BYTES = 128, 65536  # IQO_HIP_ROI_MAX_TAPS, IQO_HIP_ROI_LDS_BYTES
+ROI_LAYOUTS = {"nv12": 0, "i420": 1}  # IQO_ROI_NV12, IQO_ROI_I420
+
+
+class RoiYuvBoxLayout(ctypes.Structure):
+    """iqo_hip_roi_yuv_box_layout"""
+    _fields_ = [("rows", ctypes.c_int), ("workgroups", ctypes.c_uint), ("ldsBytes", _c_sz), ("nYp", ctypes.c_int),
+                ("np", ctypes.c_int), ("pitchDw", ctypes.c_int), ("nYpC", ctypes.c_int), ("npC", ctypes.c_int),
+                ("pitchDwC", ctypes.c_int)]
 
 
 class IpcHandle(ctypes.Structure):
@@ -223,6 +232,20 @@ def lib():
     L.iqo_host_roi_arena_stats.argtypes = roi_host + [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz,
                                                       ctypes.POINTER(RoiArenaStats), pi]
     L.iqo_host_roi_box_layout.argtypes = roi_host + [_c_sz, _c_sz, ctypes.POINTER(RoiBoxLayout)]
+    # nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, Y, U or UV, V; then the output
+    ryuv_src = [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _vp]
+    ryuv_rgb = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _c_sz, _c_sz, _vp]
+    ryuv_norm = [ctypes.c_int, ctypes.POINTER(Norm), _c_sz, _c_sz, _c_sz, _vp]
+    L.iqo_hip_plan_rois_yuv.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz, ctypes.c_int, pp]
+    L.iqo_hip_roi_yuv_plan_destroy.argtypes = [_vp]
+    L.iqo_hip_roi_yuv_plan_destroy.restype = None
+    L.iqo_hip_resize_rois_yuv_rgb_device.argtypes = [_vp] + ryuv_src + ryuv_rgb + [_vp, pi]
+    L.iqo_hip_resize_rois_yuv_norm_device.argtypes = [_vp] + ryuv_src + ryuv_norm + [_vp, pi]
+    L.iqo_host_resize_rois_yuv_rgb.argtypes = roi_host + ryuv_src + ryuv_rgb + [pi]
+    L.iqo_host_resize_rois_yuv_norm.argtypes = roi_host + ryuv_src + ryuv_norm + [pi]
+    L.iqo_host_roi_yuv_arena_stats.argtypes = roi_host + [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz,
+                                                          ctypes.POINTER(RoiArenaStats), pi]
+    L.iqo_host_roi_yuv_box_layout.argtypes = roi_host + [_c_sz, _c_sz, ctypes.POINTER(RoiYuvBoxLayout)]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -563,6 +586,103 @@ def host_roi_box_layout(method, degree, channels, dstW, dstH, w, h):
         raise err
     return {"rows": bl.rows, "workgroups": bl.workgroups, "lds_bytes": bl.ldsBytes, "nYp": bl.nYp, "NP": bl.np,
             "pitchDw": bl.pitchDw}
+
+
+def _roi_layout(layout):
+    if layout not in ROI_LAYOUTS:
+        raise IqoError("layout must be nv12 or i420")
+    return ROI_LAYOUTS[layout]
+
+
+def _yuv_planes(layout, base, frameW, frameH):
+    """(srcStY, srcStUV, Y, U or UV, V or None) of the tight frame layout at address `base`."""
+    if frameW < 2 or frameH < 2 or frameW % 2 or frameH % 2:
+        return frameW, frameW, base, base, (None if layout == "nv12" else base)  # (the call rejects the size)
+    n = frameW * frameH
+    if layout == "nv12":
+        return frameW, frameW, base, base + n, None
+    return frameW, frameW // 2, base, base + n, base + n + n // 4
+
+
+def _rgb_order(order):
+    if order not in RGB_ORDERS:
+        raise IqoError("order must be one of %s" % ", ".join(sorted(RGB_ORDERS)))
+    o4 = RGB_ORDERS[order]
+    return len(o4), (ctypes.c_int * 4)(*(o4 + (0,) * (4 - len(o4))))
+
+
+def host_resize_rois_yuv(method, degree, dstW, dstH, src, boxes, frameW, frameH, layout="nv12", standard="bt709",
+                         order="rgb", scale=None, bias=None, dtype=None, planes=(0, 1, 2), out=None):
+    """iqo_host_resize_rois_yuv_rgb / _norm on numpy arrays (no GPU): the CPU twin of YuvRoiResizer.resize_rois_rgb
+    and, with scale / bias, of resize_rois_normalized (`planes`: its order).  src: uint8 [F, frameW*frameH*3/2], the
+    tight NV12 / I420 frames (unit byte stride; the frame stride is free).  Returns uint8 [N, dstH, dstW, 3|4], or
+    [N, planes, dstH, dstW] of "float32", "float16" or "bfloat16" (uint16 bit patterns)."""
+    import numpy as np
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    lay, cs = _roi_layout(layout), _standard(standard)
+    if src.dtype != np.uint8 or src.ndim != 2 or src.shape[1] != frameW * frameH * 3 // 2:
+        raise IqoError("expected a uint8 array [F, %d]" % (frameW * frameH * 3 // 2))
+    if src.strides[1] != 1 or src.strides[0] < 1:
+        src = np.ascontiguousarray(src)
+    boxes = [tuple(b) for b in boxes]
+    arr, bad, N = _roi_array(boxes), ctypes.c_int(-1), len(boxes)
+    stY, stUV, y, u, v = _yuv_planes(layout, src.ctypes.data, frameW, frameH)
+    head = (m, degree, lay, dstW, dstH, N, arr, src.shape[0], frameW, frameH, stY, stUV, src.strides[0], y, u, v, cs)
+    if scale is None:
+        C, o4 = _rgb_order(order)
+        shape = (N, dstH, dstW, C)
+        if out is None:
+            out = np.zeros(shape, np.uint8)
+        if out.dtype != np.uint8 or out.shape != shape or (N and (out.strides[2] != C or out.strides[3] != 1)):
+            raise IqoError("out must be a uint8 array %s with contiguous pixels" % (shape,))
+        if N == 0:
+            return out
+        rc = lib().iqo_host_resize_rois_yuv_rgb(*head, C, o4, out.strides[1], out.strides[0], out.ctypes.data,
+                                                ctypes.byref(bad))
+        _check_rois(rc, bad, boxes, "host_resize_rois_yuv")
+        return out
+    dtype = dtype or "float32"
+    codes = {"float32": (OUT_F32, np.float32), "float16": (OUT_F16, np.float16), "bfloat16": (OUT_BF16, np.uint16)}
+    n, nplanes = _norm_of(3, scale, bias, planes, codes[dtype][0])
+    shape = (N, nplanes, dstH, dstW)
+    if out is None:
+        out = np.zeros(shape, codes[dtype][1])
+    e = out.itemsize
+    if out.dtype != codes[dtype][1] or out.shape != shape or (N and out.strides[3] != e):
+        raise IqoError("out must be a %s array %s with unit column stride" % (codes[dtype][1].__name__, shape))
+    if N == 0:
+        return out
+    rc = lib().iqo_host_resize_rois_yuv_norm(*head, ctypes.byref(n), out.strides[2], out.strides[1], out.strides[0],
+                                             out.ctypes.data, ctypes.byref(bad))
+    _check_rois(rc, bad, boxes, "host_resize_rois_yuv")
+    return out
+
+
+def host_roi_yuv_arena_stats(method, degree, dstW, dstH, layout, boxes, nFrames, frameW, frameH):
+    """iqo_host_roi_yuv_arena_stats: host_roi_arena_stats of a YUV box call; "x_tables" / "y_tables" count every
+    distinct table once, whether luma, chroma or both use it."""
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    boxes = [tuple(b) for b in boxes]
+    st, bad = RoiArenaStats(), ctypes.c_int(-1)
+    rc = lib().iqo_host_roi_yuv_arena_stats(m, degree, _roi_layout(layout), dstW, dstH, len(boxes), _roi_array(boxes),
+                                            nFrames, frameW, frameH, ctypes.byref(st), ctypes.byref(bad))
+    _check_rois(rc, bad, boxes, "host_roi_yuv_arena_stats")
+    return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
+            "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
+
+
+def host_roi_yuv_box_layout(method, degree, layout, dstW, dstH, w, h):
+    """iqo_host_roi_yuv_box_layout: {"rows", "workgroups", "lds_bytes"} and {"nYp", "NP", "pitchDw"} of luma and, with
+    a "C" appended, of chroma, as the layout of a call decides for one box of w x h pixels, without a GPU."""
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    bl = RoiYuvBoxLayout()
+    rc = lib().iqo_host_roi_yuv_box_layout(m, degree, _roi_layout(layout), dstW, dstH, w, h, ctypes.byref(bl))
+    if rc != 0:
+        err = IqoError("host_roi_yuv_box_layout: %s (%d) (box %d x %d)" % (lib().iqo_hip_strerror(rc).decode(), rc, w, h))
+        err.status, err.bad_roi = rc, -1  # IQO_HIP_E*; the call names no box index
+        raise err
+    return {"rows": bl.rows, "workgroups": bl.workgroups, "lds_bytes": bl.ldsBytes, "nYp": bl.nYp, "NP": bl.np,
+            "pitchDw": bl.pitchDw, "nYpC": bl.nYpC, "NPC": bl.npC, "pitchDwC": bl.pitchDwC}
 
 
 def _ptr(obj):
@@ -1014,6 +1134,110 @@ class RoiResizer:
                                                    s.stride(1), s.stride(0), _ptr(s), ctypes.byref(n),
                                                    out.stride(2) * e, out.stride(1) * e, out.stride(0) * e, _ptr(out),
                                                    _stream_ptr(stream), ctypes.byref(bad))
+        _check_rois(rc, bad, boxes, "resize_rois_normalized")
+        return out
+
+
+class YuvRoiResizer:
+    """Crop-and-resize a batch of boxes of device-resident NV12 / I420 frames to one dstW x dstH, straight to RGB
+    bytes or normalised tensors, in one launch (iqo_hip_plan_rois_yuv).  Box coordinates and sizes are even.  Every
+    output is bit for bit what Nv12Resizer / Yuv420Resizer(method, degree, w, h, dstW, dstH, chroma="full") gives on
+    the cropped frame.  Calls are asynchronous on the stream; one call at a time per object (not thread-safe); not
+    capturable into a graph."""
+
+    def __init__(self, method, degree, dstW, dstH, layout="nv12", device=None):
+        self.method = _METHODS[method] if isinstance(method, str) else int(method)
+        self.degree, self.dstW, self.dstH, self.layout = int(degree), int(dstW), int(dstH), layout
+        self.device = 0 if device is None else int(device)
+        self._plan = _vp()
+        _check(lib().iqo_hip_plan_rois_yuv(self.method, self.degree, _roi_layout(layout), self.dstW, self.dstH,
+                                           self.device, ctypes.byref(self._plan)), "YuvRoiResizer")
+
+    def __del__(self):
+        p = getattr(self, "_plan", None)
+        if p and _lib is not None:
+            _lib.iqo_hip_roi_yuv_plan_destroy(p)
+            self._plan = _vp()
+
+    def _source(self, src, frameW, frameH):
+        """(nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, Y, U or UV, V) of the tight frame tensor."""
+        import torch
+        n = frameW * frameH * 3 // 2
+        if not (src.dtype == torch.uint8 and src.is_cuda and src.dim() == 2 and src.shape[1] == n):
+            raise IqoError("expected a uint8 device tensor [F, %d]" % n)
+        if src.stride(1) != 1 or src.stride(0) < 1:
+            src = src.contiguous()
+        stY, stUV, y, u, v = _yuv_planes(self.layout, src.data_ptr(), frameW, frameH)
+        return src, (src.shape[0], frameW, frameH, stY, stUV, src.stride(0), y, u, v)
+
+    def resize_rois_rgb_device(self, boxes, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV,
+                               dstSt, dstRoiSt, dDst, standard="bt709", order="rgb", stream=None):
+        """The raw form (iqo_hip_resize_rois_yuv_rgb_device) for planes that lie anywhere: device addresses (or
+        tensors) of frame 0's planes, their row strides and the one frame stride, and the destination's strides, all
+        in bytes.  dV is None for NV12."""
+        boxes = [tuple(b) for b in boxes]
+        C, o4 = _rgb_order(order)
+        bad = ctypes.c_int(-1)
+        rc = lib().iqo_hip_resize_rois_yuv_rgb_device(
+            self._plan, len(boxes), _roi_array(boxes), nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, _ptr(dY),
+            _ptr(dUorUV), None if dV is None else _ptr(dV), _standard(standard), C, o4, dstSt, dstRoiSt, _ptr(dDst),
+            _stream_ptr(stream), ctypes.byref(bad))
+        _check_rois(rc, bad, boxes, "resize_rois_rgb_device")
+
+    def resize_rois_rgb(self, src, boxes, frameW, frameH, standard="bt709", order="rgb", out=None, stream=None):
+        """src: uint8 [F, frameW*frameH*3/2] on the device, the tight frames resize_frames of the YUV resizers takes.
+        boxes: (frame, x, y, w, h) or (frame, x, y, w, h, flip), all even.  Returns / fills out [N, dstH, dstW, C]
+        uint8, C = 3 ("rgb", "bgr") or 4 ("rgba", "bgra"; alpha 255), with contiguous pixels and non-overlapping rows
+        and outputs."""
+        import torch
+        s, args = self._source(src, frameW, frameH)
+        C, _ = _rgb_order(order)
+        boxes = [tuple(b) for b in boxes]
+        N = len(boxes)
+        shape = (N, self.dstH, self.dstW, C)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=s.device)
+        if (out.dtype != torch.uint8 or out.device != s.device or tuple(out.shape) != shape or out.stride(2) != C
+                or out.stride(3) != 1 or out.stride(1) < self.dstW * C
+                or (N > 1 and out.stride(0) < self.dstH * out.stride(1))):
+            raise IqoError("out must be a uint8 tensor %s on %s with contiguous pixels and non-overlapping rows and "
+                           "outputs" % (shape, s.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        self.resize_rois_rgb_device(boxes, *args, out.stride(1), out.stride(0), out, standard, order, stream)
+        return out
+
+    def resize_rois_normalized(self, src, boxes, frameW, frameH, scale, bias, standard="bt709", dtype=None,
+                               order=(0, 1, 2), out=None, stream=None):
+        """As resize_rois_rgb, stored as the normalised planar tensor a model takes: [N, planes, dstH, dstW] of `dtype`
+        (float32, float16 or bfloat16), plane p = float32(byte order[p] of (R, G, B)) * scale[p] + bias[p], each
+        operation rounded to float32, then rounded to `dtype`.  `out` may be a strided view with unit column stride
+        and non-overlapping rows, planes and outputs."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32
+        codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+        if dtype not in codes:
+            raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        s, args = self._source(src, frameW, frameH)
+        boxes = [tuple(b) for b in boxes]
+        N = len(boxes)
+        n, planes = _norm_of(3, scale, bias, order, codes[dtype])
+        shape = (N, planes, self.dstH, self.dstW)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=s.device)
+        if (out.dtype != dtype or out.device != s.device or tuple(out.shape) != shape or out.stride(3) != 1
+                or out.stride(2) < self.dstW or out.stride(1) < self.dstH * out.stride(2)
+                or (N > 1 and out.stride(0) < planes * out.stride(1))):
+            raise IqoError("out must be a %s tensor %s on %s with unit column stride and non-overlapping rows, planes "
+                           "and outputs" % (dtype, shape, s.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(s.device)
+        e, bad = out.element_size(), ctypes.c_int(-1)
+        rc = lib().iqo_hip_resize_rois_yuv_norm_device(self._plan, N, _roi_array(boxes), *args, _standard(standard),
+                                                       ctypes.byref(n), out.stride(2) * e, out.stride(1) * e,
+                                                       out.stride(0) * e, _ptr(out), _stream_ptr(stream),
+                                                       ctypes.byref(bad))
         _check_rois(rc, bad, boxes, "resize_rois_normalized")
         return out
 

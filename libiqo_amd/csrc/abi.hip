@@ -3640,6 +3640,27 @@ void roi_arena_free(iqo_hip_roi_plan::Arena *a)
     a->capWords = 0;
 }
 
+// Makes `a` ready to be filled with `words` words: waits for the launch that last read it, and grows it.
+int roi_arena_reserve(iqo_hip_roi_plan::Arena *a, size_t words)
+{
+    if (a->pending) {
+        if (hipEventSynchronize(a->ev) != hipSuccess)
+            return IQO_HIP_EHIP;
+        a->pending = false;
+    }
+    if (a->capWords < words) {
+        roi_arena_free(a);
+        const size_t cap2 = std::max(words + words / 2, size_t(1) << 16);
+        if (hipHostMalloc(reinterpret_cast<void **>(&a->h), cap2 * 4, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&a->d), cap2 * 4) != hipSuccess) {
+            roi_arena_free(a);
+            return IQO_HIP_ENOMEM;
+        }
+        a->capWords = cap2;
+    }
+    return IQO_HIP_OK;
+}
+
 int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
              size_t srcSt, size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, bool isNorm, size_t dstSt,
              size_t planeSt, size_t dstRoiSt, void *dst, hipStream_t s, int *badRoi)
@@ -3673,21 +3694,9 @@ int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t 
     if (cap != hipStreamCaptureStatusNone)
         return IQO_HIP_EUNSUP;  // the tables are per call: nothing to replay
     iqo_hip_roi_plan::Arena &a = h->arena[h->next];
-    if (a.pending) {  // the launch that last read this arena
-        if (hipEventSynchronize(a.ev) != hipSuccess)
-            return IQO_HIP_EHIP;
-        a.pending = false;
-    }
-    if (a.capWords < l.words) {
-        roi_arena_free(&a);
-        const size_t cap2 = std::max(l.words + l.words / 2, size_t(1) << 16);
-        if (hipHostMalloc(reinterpret_cast<void **>(&a.h), cap2 * 4, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&a.d), cap2 * 4) != hipSuccess) {
-            roi_arena_free(&a);
-            return IQO_HIP_ENOMEM;
-        }
-        a.capWords = cap2;
-    }
+    const int ra = roi_arena_reserve(&a, l.words);
+    if (ra)
+        return ra;
     iqo_amd::roi_fill(h->cache, l, frameW, a.h);
     if (hipMemcpyAsync(a.d, a.h, l.words * 4, hipMemcpyHostToDevice, s) != hipSuccess)
         return IQO_HIP_EHIP;
@@ -3841,6 +3850,334 @@ int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t ds
     out->nYp = static_cast<int>(yt[0]);
     out->np = static_cast<int>(xt[0]);
     out->pitchDw = static_cast<int>(l.rec[iqo_amd::kRPitch]);
+    return IQO_HIP_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB (roi.hpp)
+
+// As iqo_hip_roi_plan, over the YUV arena.
+struct iqo_hip_roi_yuv_plan {
+    iqo_hip_roi_yuv_plan(iqo_amd::Method m, unsigned degree, int layout_, int dstW, int dstH, int device_)
+        : cache(m, degree, dstW, dstH), layout(layout_), device(device_)
+    {
+    }
+    iqo_amd::RoiTableCache cache;
+    iqo_amd::RoiLayout boxes;
+    int layout, device;
+    iqo_hip_roi_plan::Arena arena[2];
+    int next = 0;
+};
+
+namespace {
+
+static_assert(IQO_ROI_NV12 == iqo_amd::kRoiNv12 && IQO_ROI_I420 == iqo_amd::kRoiI420, "iqo_hip.h layouts are roi.hpp's");
+
+// The source and the output of a YUV box call, as the C entries take them.
+struct RoiYuvCall {
+    size_t nRois;
+    const iqo_hip_roi *rois;
+    size_t nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt;
+    const uint8_t *y, *u, *v;
+    int standard, channels;
+    const int *order;          // packed bytes: channels entries
+    const iqo_hip_norm *norm;  // float planes (isNorm)
+    bool isNorm;
+    size_t dstSt, planeSt, dstRoiSt;
+    void *dst;
+};
+
+// The checks of a call's own arguments that roi_yuv_layout does not make; fills *src and *out.
+int roi_yuv_check(int layout, size_t dstW, size_t dstH, const RoiYuvCall &c, bool needPlanes, iqo_amd::RoiYuvSrc *src,
+                  iqo_amd::RoiYuvOut *out)
+{
+    if (layout != IQO_ROI_NV12 && layout != IQO_ROI_I420)
+        return IQO_HIP_EINVAL;
+    if (c.standard < 0 || c.standard >= iqo_amd::kYuvRgbStandards)
+        return IQO_HIP_EINVAL;
+    if (needPlanes && c.nRois && (!c.y || !c.u || (layout == IQO_ROI_I420 && !c.v)))
+        return IQO_HIP_EINVAL;
+    *out = iqo_amd::RoiYuvOut();
+    out->standard = c.standard;
+    if (!c.isNorm) {
+        if ((c.channels != 3 && c.channels != 4) || !c.order)
+            return IQO_HIP_EINVAL;
+        for (int i = 0; i < c.channels; ++i) {
+            if (c.order[i] < 0 || c.order[i] > 3)
+                return IQO_HIP_EINVAL;
+            out->order[i] = c.order[i];
+        }
+        out->channels = c.channels;
+    }
+    if (needPlanes) {
+        const int rc = roi_check_dst(c.isNorm ? 3 : c.channels, dstW, dstH, c.nRois, c.norm, c.isNorm, c.dstSt, c.planeSt,
+                                     c.dstRoiSt, c.dst, &out->n);
+        if (rc)
+            return rc;
+    } else if (!dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20)) {
+        return IQO_HIP_EINVAL;
+    }
+    src->layout = layout;
+    src->nFrames = c.nFrames;
+    src->frameW = c.frameW;
+    src->frameH = c.frameH;
+    src->stY = c.srcStY;
+    src->stUV = c.srcStUV;
+    src->frameSt = c.srcFrameSt;
+    return IQO_HIP_OK;
+}
+
+int host_rois_yuv(int method, unsigned degree, int layout, size_t dstW, size_t dstH, const RoiYuvCall &c,
+                  iqo_hip_roi_arena_stats *stats, int *badRoi)
+{
+    int bad = -1;
+    if (badRoi)
+        *badRoi = -1;
+    if (method < 0 || method > 2)
+        return IQO_HIP_EINVAL;
+    iqo_amd::RoiYuvSrc src;
+    iqo_amd::RoiYuvOut out;
+    const int rc = roi_yuv_check(layout, dstW, dstH, c, !stats, &src, &out);
+    if (rc)
+        return rc;
+    iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
+    iqo_amd::RoiLayout l;
+    const int st = iqo_amd::roi_yuv_layout(&cache, src, c.nRois, reinterpret_cast<const iqo_amd::RoiBox *>(c.rois), &l, &bad);
+    if (st != iqo_amd::kRoiOk) {
+        if (badRoi)
+            *badRoi = bad;
+        return roi_status(st);
+    }
+    if (stats) {
+        stats->arenaBytes = l.words * 4;
+        stats->xTables = l.nXTables;
+        stats->yTables = l.nYTables;
+        stats->workgroups = l.groups;
+        stats->ldsBytes = l.ldsBytes;
+        stats->recordBytes = iqo_amd::kRoiYuvRecWords * 4;
+        return IQO_HIP_OK;
+    }
+    std::vector<uint32_t> arena(l.words);
+    iqo_amd::roi_yuv_fill(cache, l, src, arena.data());
+    iqo_amd::roi_yuv_walk(arena.data(), c.y, c.u, c.v, out, c.dstSt, c.planeSt, c.dstRoiSt, c.dst);
+    return IQO_HIP_OK;
+}
+
+int run_rois_yuv(iqo_hip_roi_yuv_plan *h, const RoiYuvCall &c, hipStream_t s, int *badRoi)
+{
+    if (badRoi)
+        *badRoi = -1;
+    if (!h)
+        return IQO_HIP_EINVAL;
+    iqo_amd::RoiYuvSrc src;
+    iqo_amd::RoiYuvOut out;
+    const int rc = roi_yuv_check(h->layout, static_cast<size_t>(h->cache.dstW()), static_cast<size_t>(h->cache.dstH()), c,
+                                 true, &src, &out);
+    if (rc)
+        return rc;
+    int bad = -1;
+    const int st = iqo_amd::roi_yuv_layout(&h->cache, src, c.nRois, reinterpret_cast<const iqo_amd::RoiBox *>(c.rois),
+                                           &h->boxes, &bad);
+    if (st != iqo_amd::kRoiOk) {
+        if (badRoi)
+            *badRoi = bad;
+        return roi_status(st);
+    }
+    const iqo_amd::RoiLayout &l = h->boxes;
+    if (c.nRois == 0)
+        return IQO_HIP_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess)
+        return IQO_HIP_EHIP;
+    if (cap != hipStreamCaptureStatusNone)
+        return IQO_HIP_EUNSUP;  // the tables are per call: nothing to replay
+    iqo_hip_roi_plan::Arena &a = h->arena[h->next];
+    const int ra = roi_arena_reserve(&a, l.words);
+    if (ra)
+        return ra;
+    iqo_amd::roi_yuv_fill(h->cache, l, src, a.h);
+    if (hipMemcpyAsync(a.d, a.h, l.words * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return IQO_HIP_EHIP;
+    a.pending = true;  // from here on the arena is in flight, whatever follows
+    iqo_amd::RoiYuvDev d;
+    d.arena = a.d;
+    d.y = c.y;
+    d.u = c.u;
+    d.v = c.v;
+    d.dst = static_cast<uint8_t *>(c.dst);
+    d.dstSt = static_cast<int64_t>(c.dstSt);
+    d.dstRoiSt = static_cast<int64_t>(c.dstRoiSt);
+    d.lanczos = h->cache.method() == iqo_amd::kLanczos;
+    d.interleavedUV = h->layout == IQO_ROI_NV12;
+    d.k = iqo_amd::kYuvRgb[c.standard];
+    d.channels = out.channels;
+    d.groups = l.groups;
+    d.ldsBytes = l.ldsBytes;
+    iqo_amd::NormDev n;
+    n.dtype = out.n.dtype;
+    n.planes = out.n.planes;
+    n.planeSt = static_cast<int>(c.planeSt);
+    for (int i = 0; i < 4; ++i) {
+        d.order[i] = out.order[i];
+        n.order[i] = out.n.order[i];
+        n.scale[i] = out.n.scale[i];
+        n.bias[i] = out.n.bias[i];
+    }
+    const hipError_t e = iqo_amd::launch_roi_yuv(d, c.isNorm ? &n : nullptr, s);
+    const hipError_t e2 = hipEventRecord(a.ev, s);
+    h->next ^= 1;
+    if (e == hipErrorInvalidValue)
+        return IQO_HIP_EINVAL;
+    return e == hipSuccess && e2 == hipSuccess ? IQO_HIP_OK : IQO_HIP_EHIP;
+}
+
+} // namespace
+
+extern "C" {
+
+int iqo_hip_plan_rois_yuv(int method, unsigned degree, int layout, size_t dstW, size_t dstH, int device,
+                          iqo_hip_roi_yuv_plan **out)
+{
+    if (!out)
+        return IQO_HIP_EINVAL;
+    *out = nullptr;
+    if (method < 0 || method > 2 || (method == IQO_METHOD_LANCZOS && degree < 1) || !dstW || !dstH ||
+        dstW > (1u << 20) || dstH > (1u << 20) || (layout != IQO_ROI_NV12 && layout != IQO_ROI_I420))
+        return IQO_HIP_EINVAL;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || !is_gfx950(device))
+        return IQO_HIP_ENODEV;
+    DeviceGuard guard(device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    iqo_hip_roi_yuv_plan *h = new (std::nothrow) iqo_hip_roi_yuv_plan(
+        static_cast<iqo_amd::Method>(method), degree, layout, static_cast<int>(dstW), static_cast<int>(dstH), device);
+    if (!h)
+        return IQO_HIP_ENOMEM;
+    for (auto &a : h->arena)
+        if (hipEventCreateWithFlags(&a.ev, hipEventDisableTiming) != hipSuccess) {
+            iqo_hip_roi_yuv_plan_destroy(h);
+            return IQO_HIP_EHIP;
+        }
+    *out = h;
+    return IQO_HIP_OK;
+}
+
+void iqo_hip_roi_yuv_plan_destroy(iqo_hip_roi_yuv_plan *h)
+{
+    if (!h)
+        return;
+    {
+        DeviceGuard guard(h->device);
+        for (auto &a : h->arena) {
+            if (a.pending)
+                (void)hipEventSynchronize(a.ev);
+            if (a.ev)
+                (void)hipEventDestroy(a.ev);
+            roi_arena_free(&a);
+        }
+    }
+    delete h;
+}
+
+int iqo_hip_resize_rois_yuv_rgb_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                       size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                                       const uint8_t *dY, const uint8_t *dUorUV, const uint8_t *dV, int standard,
+                                       int channels, const int *order, size_t dstSt, size_t dstRoiSt, uint8_t *dDst,
+                                       void *stream, int *badRoi)
+{
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV, standard,
+                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dDst};
+    return run_rois_yuv(plan, c, static_cast<hipStream_t>(stream), badRoi);
+}
+
+int iqo_hip_resize_rois_yuv_norm_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                        size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                                        const uint8_t *dY, const uint8_t *dUorUV, const uint8_t *dV, int standard,
+                                        const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt,
+                                        void *dDst, void *stream, int *badRoi)
+{
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV, standard,
+                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dDst};
+    return run_rois_yuv(plan, c, static_cast<hipStream_t>(stream), badRoi);
+}
+
+int iqo_host_resize_rois_yuv_rgb(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                 const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcStY,
+                                 size_t srcStUV, size_t srcFrameSt, const uint8_t *y, const uint8_t *uOrUV,
+                                 const uint8_t *v, int standard, int channels, const int *order, size_t dstSt,
+                                 size_t dstRoiSt, uint8_t *dst, int *badRoi)
+{
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, y, uOrUV, v, standard,
+                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dst};
+    return host_rois_yuv(method, degree, layout, dstW, dstH, c, nullptr, badRoi);
+}
+
+int iqo_host_resize_rois_yuv_norm(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                  const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcStY,
+                                  size_t srcStUV, size_t srcFrameSt, const uint8_t *y, const uint8_t *uOrUV,
+                                  const uint8_t *v, int standard, const iqo_hip_norm *norm, size_t dstSt,
+                                  size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi)
+{
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, y, uOrUV, v, standard,
+                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dst};
+    return host_rois_yuv(method, degree, layout, dstW, dstH, c, nullptr, badRoi);
+}
+
+int iqo_host_roi_yuv_arena_stats(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                 const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                 iqo_hip_roi_arena_stats *stats, int *badRoi)
+{
+    if (!stats)
+        return IQO_HIP_EINVAL;
+    const size_t stUV = layout == IQO_ROI_NV12 ? frameW : frameW / 2;
+    // (no planes and no destination: tightly packed frames, and the output form plays no part in the arena)
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, frameW, stUV, frameW * frameH * 3 / 2, nullptr, nullptr,
+                          nullptr, 0, 3, nullptr, nullptr, true, 0, 0, 0, nullptr};
+    return host_rois_yuv(method, degree, layout, dstW, dstH, c, stats, badRoi);
+}
+
+int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
+                                iqo_hip_roi_yuv_box_layout *out)
+{
+    if (!out || method < 0 || method > 2 || !dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20) || !w || !h ||
+        w > (1u << 24) || h > (1u << 24))
+        return IQO_HIP_EINVAL;
+    // the box as the whole of one tightly packed frame: roi_yuv_layout on a one-box call, as the device call
+    const iqo_amd::RoiBox box = {0, 0, 0, static_cast<int>(w), static_cast<int>(h), 0};
+    iqo_amd::RoiYuvSrc src;
+    src.layout = layout;
+    src.nFrames = 1;
+    src.frameW = src.stY = w;
+    src.frameH = h;
+    src.stUV = layout == IQO_ROI_NV12 ? w : w / 2;
+    src.frameSt = w * h * 3 / 2;
+    iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
+    iqo_amd::RoiLayout l;
+    int bad = -1;
+    const int st = iqo_amd::roi_yuv_layout(&cache, src, 1, &box, &l, &bad);
+    if (st != iqo_amd::kRoiOk)
+        return roi_status(st);
+    const uint32_t *r = l.rec.data();
+    auto tab = [&](int word) {  // the table at arena word offset r[word]
+        for (const auto &t : l.tables)
+            if (t.second == r[word])
+                return t.first->data();
+        return static_cast<const uint32_t *>(nullptr);
+    };
+    out->rows = static_cast<int>(r[iqo_amd::kYRows]);
+    out->workgroups = r[iqo_amd::kYGroups];
+    out->ldsBytes = l.ldsBytes;
+    out->nYp = static_cast<int>(tab(iqo_amd::kYYTab)[0]);
+    out->np = static_cast<int>(tab(iqo_amd::kYXTab)[0]);
+    out->pitchDw = static_cast<int>(r[iqo_amd::kYPitch]);
+    out->nYpC = static_cast<int>(tab(iqo_amd::kYYTabC)[0]);
+    out->npC = static_cast<int>(tab(iqo_amd::kYXTabC)[0]);
+    out->pitchDwC = static_cast<int>(r[iqo_amd::kYPitchC]);
     return IQO_HIP_OK;
 }
 

@@ -169,6 +169,23 @@ struct RoiDev {
 };
 hipError_t launch_roi(const RoiDev &d, const NormDev *norm, hipStream_t s);
 
+// --- boxes of NV12 / I420 frames straight to RGB (kernels_roi_yuv.hip roi_yuv_kernel): as launch_roi over
+// the YUV arena of roi.hpp, which also carries the layout and the planes' row strides.  y, u, v: frame 0's
+// planes (interleaved UV: u, and v is not read).  dst: packed bytes, `channels` 3 or 4 per pixel, byte c =
+// order[c] of {0 R, 1 G, 2 B, 3 the constant 255}; with `norm` the float planes of NormDev of (R, G, B).
+struct RoiYuvDev {
+    const uint32_t *arena;
+    const uint8_t *y, *u, *v;
+    uint8_t *dst;
+    int64_t dstSt, dstRoiSt;
+    bool lanczos, interleavedUV;
+    YuvRgbCoef k;                // the standard's six integers
+    int channels, order[4];
+    unsigned groups;
+    size_t ldsBytes;
+};
+hipError_t launch_roi_yuv(const RoiYuvDev &d, const NormDev *norm, hipStream_t s);
+
 // --- YUV 4:2:0 planes -> RGB (kernels_color.hip): the second pass of the NV12 / I420 "resize to RGB"
 // entries.  Reads resized planes from a workspace (Y dstW x dstH; chroma cw x ch, replicated to the
 // output grid: pixel (y, x) takes sample (min(y >> 1, ch - 1), min(x >> 1, cw - 1))), applies the

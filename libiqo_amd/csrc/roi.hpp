@@ -1,6 +1,8 @@
 // roi.hpp -- crop-and-resize of a batch of boxes to one output size (iqo_hip_resize_rois_device):
 // the per-call ARENA the kernel (kernels_roi.hip roi_kernel) and its CPU twin (roi_walk) both read,
 // the per-plan cache of axis tables that fills it, and the twin itself.  Pure C++ (no HIP).
+// (roi.cpp includes the HIP runtime header only where the HIP compiler builds it, so that colorspace.hpp's
+// __host__ __device__ markers parse in its device pass; a plain C++ compiler builds both files as they are.)
 //
 // Box i of a call is a rectangle (x, y, w, h) of frame `frame`; its output is what the planar resize
 // (w, h) -> (dstW, dstH) gives on the cropped image, channel by channel.  Each axis is independent
@@ -131,5 +133,74 @@ struct RoiNorm {
 // y * dstSt + x * elem.
 void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
               void *dst, const RoiNorm &n);
+
+// ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB
+//
+// iqo_hip_resize_rois_yuv_*_device (kernels_roi_yuv.hip roi_yuv_kernel, CPU twin roi_yuv_walk).  Box i is a
+// rectangle with even x, y, w, h of a 4:2:0 frame.  Its Y is the planar resize (w, h) -> (dstW, dstH) of the
+// cropped luma, its U and V the planar resize (w/2, h/2) -> (dstW, dstH) of the cropped chroma (the
+// full-grid chroma of IQO_CHROMA_FULL), and a pixel is colorspace.hpp yuv_to_rgb of the three.  A box so
+// needs four of the tables above: X of w and of w/2, Y of h and of h/2, from the one RoiTableCache -- keyed
+// by (axis, length), so a chroma axis shares the table of a luma axis of its length.
+//
+// The call has an arena format of its own: the same tables, with
+//   header   kRoiHdrWords words      see RoiYuvHdr
+//   records  nRois x kRoiYuvRecWords see RoiYuvRec
+constexpr int kRoiYuvRecWords = 24;
+constexpr uint32_t kRoiYuvMagic = 0x494f5931u;  // "IOY1"
+enum { kRoiNv12 = 0, kRoiI420 = 1 };            // iqo_hip.h IQO_ROI_NV12 / IQO_ROI_I420
+
+// header words: kHMagic .. kHDstH, kHLanczos, kHRecOff and kHWords as RoiHdr, and
+enum RoiYuvHdr {
+    kHYLayout = 5,      // kRoiNv12 / kRoiI420
+    kHYRowBytes = 7,    // bytes of a row of the Y plane: frameW
+    kHYRowBytesC = 10,  // bytes of a row of a chroma plane: frameW (NV12) or frameW / 2 (I420)
+    kHYStY = 11,        // row strides of the Y plane and of the chroma plane(s), bytes
+    kHYStC = 12
+};
+enum RoiYuvRec {
+    kYFrame = 0,
+    kYOffLo,   // byte offset of the box's first luma sample from the Y base: frame * frameSt + y * srcStY + x
+    kYOffHi,
+    kYOffCLo,  // ... of its first chroma sample from the UV base (NV12: + x) or the U and V bases (I420: + x / 2):
+    kYOffCHi,  //     frame * frameSt + (y / 2) * srcStUV + ...
+    kYX,
+    kYY,
+    kYW,
+    kYH,
+    kYFlags,
+    kYXTab,    // word offsets of the luma tables (w -> dstW, h -> dstH)
+    kYYTab,
+    kYXTabC,   // ... and of the chroma tables (w / 2 -> dstW, h / 2 -> dstH)
+    kYYTabC,
+    kYRows,
+    kYFirst,
+    kYGroups,
+    kYPitch,   // work-row pitches of the Y row and of the U and V rows (dwords), the X tables'
+    kYPitchC
+};
+
+// The source of a YUV call.  frameSt applies to every plane pointer.
+struct RoiYuvSrc {
+    int layout = kRoiNv12;
+    size_t nFrames = 0, frameW = 0, frameH = 0, stY = 0, stUV = 0, frameSt = 0;
+};
+
+// roi_layout / roi_fill of the YUV arena.  out->channels holds the layout; out->nXTables / nYTables count
+// every distinct table once, whether luma, chroma or both use it.
+int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, RoiLayout *out, int *bad);
+void roi_yuv_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena);
+
+// The output of a YUV call: a colorspace.hpp standard, then packed bytes (n.dtype == 0: `channels` 3 or 4,
+// byte c = order[c] of {R, G, B, 255}) or the float planes of n (n.order[p] of {R, G, B}).
+struct RoiYuvOut {
+    int standard = 0, channels = 3;
+    int order[4] = {0, 1, 2, 3};
+    RoiNorm n;
+};
+
+// CPU twin of roi_yuv_kernel.  NV12: u is the UV plane and v is not read.  Destination as roi_walk.
+void roi_yuv_walk(const uint32_t *arena, const uint8_t *y, const uint8_t *u, const uint8_t *v, const RoiYuvOut &o,
+                  size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst);
 
 } // namespace iqo_amd
