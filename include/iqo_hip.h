@@ -608,6 +608,60 @@ int iqo_host_instance_for(int method, unsigned degree, size_t srcW, size_t srcH,
                           size_t pxScale, const iqo_hip_option *options, size_t nOptions, size_t srcAlign,
                           size_t dstAlign, iqo_hip_instance *desc);
 
+/* The grid of one launch, by number: how many workgroups a call starts and how a workgroup's flat id
+ * becomes the (column, band, frame) it resizes.  Reported by the launch function itself, run in a query
+ * mode that stops before the launch, so the figures are the launch's own.
+ *
+ * A "unit" is what a kernel decodes its place from: a wave (walker, the exact-ratio kernels: 4 per
+ * workgroup), a tile (tile, packed tile) or a whole workgroup (ryx / ryg / ryu, the block-shared Lanczos
+ * streamer).  The frame-folding families put units of all frames into one id range and permute the
+ * workgroup id L of `blocks` ids for XCD locality:
+ *   IQO_GRID_MAP_SPREAD    XCD x = L mod 8 takes a contiguous eighth of [0, blocks): with q = blocks / 8,
+ *                          r = blocks mod 8, i = L / 8: x < r ? x (q + 1) + i : r (q + 1) + (x - r) q + i
+ *   IQO_GRID_MAP_CHUNKS    chunks of `chunk` = C ids (about one frame's) dealt round-robin over the XCDs:
+ *                          with full = blocks / (8 C), an id with i < full C maps to
+ *                          (8 (i / C) + x) C + i mod C; the ids from 8 full C on map by SPREAD among
+ *                          themselves
+ *   IQO_GRID_MAP_XCD_TAIL  block-shared streamer, frames a multiple of 8 and >= 16: XCD x resizes frames
+ *                          x, x + 8, ... in `bands` bands each and its last frame in `tailBands` shorter
+ *                          ones; gridX = 8 ((frames / 8 - 1) bands + tailBands)
+ * Unit u then belongs to frame u / unitsPerFrame; unit ids from `units` on (the last workgroup's spare
+ * waves) do nothing.  IQO_GRID_MAP_NONE: the frames are gridY (general, per-wave streamers, area_int,
+ * linear_up2, the stacked streamer with framesPerBlock frames per workgroup), the unit fields are 0. */
+enum { IQO_GRID_MAP_NONE = 0, IQO_GRID_MAP_SPREAD = 1, IQO_GRID_MAP_CHUNKS = 2, IQO_GRID_MAP_XCD_TAIL = 3 };
+typedef struct iqo_hip_launch_grid {
+    int family;                      /* IQO_KERNEL_* */
+    int map;                         /* IQO_GRID_MAP_* */
+    unsigned gridX, gridY, gridZ, block;
+    unsigned blocks;                 /* ids the map permutes (map none: gridX) */
+    unsigned chunk;                  /* C of IQO_GRID_MAP_CHUNKS, else 0 */
+    unsigned unitsPerFrame, unitsPerBlock;
+    unsigned units;                  /* the kernel's wave / tile / workgroup count argument */
+    int bands, wavesPerRow;          /* 0: the family has none (tile families: bands = tile rows) */
+    unsigned framesPerBlock;         /* 1, stacked streamer: frames side by side in a workgroup */
+    int tailBands;                   /* IQO_GRID_MAP_XCD_TAIL only */
+    unsigned frames;                 /* frames of this launch: min(nFrames, 65535 or "chunk_frames") */
+} iqo_hip_launch_grid;
+
+/* The first launch of a call of nFrames frames over output rows [dstRow0, dstRow0 + dstRows) of `plan`
+ * with its CURRENT options, aligned base and strides.  Band counts chosen automatically ask the plan's
+ * device for the kernel's occupancy, as the call does.  No launch.  IQO_HIP_EINVAL: null arguments, no
+ * rows or frames, rows outside the plan, or a call the launcher would reject. */
+int iqo_hip_plan_launch_grid(const iqo_hip_plan *plan, size_t nFrames, size_t dstRow0, size_t dstRows,
+                             iqo_hip_launch_grid *desc);
+
+/* Host-only twin (no GPU needed), as iqo_host_instance_for: a full-frame call of a shape of `channels`
+ * (1: planar, 2 .. 4: packed) with nOptions options.  Without a device an automatic band count takes the
+ * occupancy as one workgroup per CU of 256 CUs, a lower bound of the real one: where the count it yields
+ * is the one set by the rows (every small shape), the device gives the same. */
+int iqo_host_launch_grid(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW,
+                         size_t dstH, size_t pxScale, const iqo_hip_option *options, size_t nOptions,
+                         size_t nFrames, iqo_hip_launch_grid *desc);
+
+/* Workgroups of a launch of the second-pass kernels (YUV -> RGB, RGB -> YUV, planes -> floats): 256 items
+ * each; a call of more than IQO_HIP_GRID_STRIDE_BLOCKS * 256 items strides over the rest. */
+#define IQO_HIP_GRID_STRIDE_BLOCKS 2048u
+
 /* Host-only: every instantiation of a family, in table order (IQO_KERNEL_RYG: ryg_kernel's, then
  * ryu_kernel's).  The count is 0 for a family with a single kernel and for an unknown family;
  * iqo_host_instance_at is IQO_HIP_EINVAL for a null descriptor or an index outside 0 .. count - 1. */

@@ -20,7 +20,8 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "host_chroma_full_kernel", "host_rgb_to_yuv", "host_rgb_to_yuv420", "rgb_yuv_workspace_bytes",
            "SOURCE_ORDERS", "RoiResizer", "Roi", "RoiArenaStats", "host_resize_rois", "host_roi_arena_stats",
            "RoiBoxLayout", "host_roi_box_layout", "ROI_MAX_TAPS", "ROI_LDS_BYTES", "YuvRoiResizer", "ROI_LAYOUTS",
-           "RoiYuvBoxLayout", "host_resize_rois_yuv", "host_roi_yuv_arena_stats", "host_roi_yuv_box_layout"]
+           "RoiYuvBoxLayout", "host_resize_rois_yuv", "host_roi_yuv_arena_stats", "host_roi_yuv_box_layout", "LaunchGrid",
+           "host_launch_grid", "GRID_MAPS", "GRID_STRIDE_BLOCKS"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LIBIQO_AMD_LIB selects an alternative build of the same library (A/B experiments only)
@@ -55,6 +56,28 @@ class Instance(ctypes.Structure):
     """iqo_hip_instance: kernel family, sub-kernel tag and the template parameters by name (0: not a parameter
     of that kernel)."""
     _fields_ = [("family", ctypes.c_int), ("sub", ctypes.c_int)] + [(k, ctypes.c_int) for k in INSTANCE_PARAMS]
+
+
+# IQO_GRID_MAP_*: how a frame-folding kernel turns a flat workgroup id into a logical one
+GRID_MAPS = {0: "none", 1: "spread", 2: "chunks", 3: "xcd_tail"}
+# IQO_HIP_GRID_STRIDE_BLOCKS: workgroups (of 256 items) of a second-pass launch; more items are strided over
+GRID_STRIDE_BLOCKS = 2048
+
+
+class LaunchGrid(ctypes.Structure):
+    """iqo_hip_launch_grid: the grid of one launch and the numbers its block map decodes with."""
+    _fields_ = [("family", ctypes.c_int), ("map", ctypes.c_int), ("gridX", ctypes.c_uint), ("gridY", ctypes.c_uint),
+                ("gridZ", ctypes.c_uint), ("block", ctypes.c_uint), ("blocks", ctypes.c_uint), ("chunk", ctypes.c_uint),
+                ("unitsPerFrame", ctypes.c_uint), ("unitsPerBlock", ctypes.c_uint), ("units", ctypes.c_uint),
+                ("bands", ctypes.c_int), ("wavesPerRow", ctypes.c_int), ("framesPerBlock", ctypes.c_uint),
+                ("tailBands", ctypes.c_int), ("frames", ctypes.c_uint)]
+
+
+def _grid_dict(d):
+    out = {k: getattr(d, k) for k, _ in LaunchGrid._fields_}
+    out["family"] = KERNELS.get(d.family, d.family)
+    out["map"] = GRID_MAPS[d.map]
+    return out
 
 
 class _Option(ctypes.Structure):
@@ -171,6 +194,9 @@ def lib():
     L.iqo_hip_plan_instance.argtypes = [_vp, _c_sz, _c_sz, ctypes.POINTER(Instance)]
     L.iqo_host_instance_for.argtypes = L.iqo_host_kernel_for.argtypes + [ctypes.POINTER(_Option), _c_sz, _c_sz, _c_sz,
                                                                          ctypes.POINTER(Instance)]
+    L.iqo_hip_plan_launch_grid.argtypes = [_vp, _c_sz, _c_sz, _c_sz, ctypes.POINTER(LaunchGrid)]
+    L.iqo_host_launch_grid.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz,
+                                       ctypes.POINTER(_Option), _c_sz, _c_sz, ctypes.POINTER(LaunchGrid)]
     L.iqo_host_instance_count.argtypes = [ctypes.c_int]
     L.iqo_host_instance_at.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Instance)]
     L.iqo_host_band_src_rows.argtypes = [ctypes.c_int, ctypes.c_uint, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz,
@@ -338,6 +364,16 @@ def host_instance_for(method, degree, srcW, srcH, dstW, dstH, pxScale=1, options
     _check(lib().iqo_host_instance_for(_METHODS[method], degree, srcW, srcH, dstW, dstH, pxScale, opts, len(options),
                                        src_align, dst_align, ctypes.byref(d)), "host_instance_for")
     return _instance_dict(d)
+
+
+def host_launch_grid(method, degree, srcW, srcH, dstW, dstH, n_frames, pxScale=1, channels=1, options=()):
+    """The grid of the first launch of a full-frame call of n_frames frames of this shape after `options`, as a
+    dict of iqo_hip_launch_grid's fields with the family and the map by name -- host only, no GPU."""
+    opts = (_Option * max(1, len(options)))(*[_Option(k.encode(), int(v)) for k, v in options])
+    d = LaunchGrid()
+    _check(lib().iqo_host_launch_grid(_METHODS[method], degree, channels, srcW, srcH, dstW, dstH, pxScale, opts,
+                                      len(options), n_frames, ctypes.byref(d)), "host_launch_grid")
+    return _grid_dict(d)
 
 
 def host_instances(kernel):
@@ -799,6 +835,14 @@ class _Resizer:
         d = Instance()
         _check(lib().iqo_hip_plan_instance(self._plan, src_align, dst_align, ctypes.byref(d)), "instance")
         return _instance_dict(d)
+
+    def launch_grid(self, n_frames, dst_row0=0, dst_rows=None):
+        """The grid of the first launch of a call of n_frames frames over dst_rows output rows from dst_row0 (all
+        of them by default) with the plan's current options (host_launch_grid's form)."""
+        d = LaunchGrid()
+        rows = self.dstH - dst_row0 if dst_rows is None else dst_rows
+        _check(lib().iqo_hip_plan_launch_grid(self._plan, n_frames, dst_row0, rows, ctypes.byref(d)), "launch_grid")
+        return _grid_dict(d)
 
     def prepare(self):
         """Upload the device tables now (before graph capture / async-only use)."""

@@ -1616,6 +1616,105 @@ bool plane_layout_accepted(const iqo_hip_plan *h, int kernel, bool wholeSource, 
     return layout_accepted(h, kernel, 0, h->p.dstH, 0, wholeSource ? h->p.srcH : s1, srcSt, dstSt);
 }
 
+// The one dispatch from a kernel family to its launcher, for output rows [rb, re) of `io`.  query: the
+// launcher fills the grid it would launch and launches nothing (kernels.hpp LaunchGrid).
+hipError_t launch_family(const iqo_hip_plan *h, int kernel, const iqo_amd::Io &io, int rb, int re, hipStream_t s,
+                         iqo_amd::LaunchGrid *query)
+{
+    switch (kernel) {
+    case IQO_KERNEL_LANCZOS_STREAM: return iqo_amd::launch_lanczos_stream(lanczos_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_AREA_INT: return iqo_amd::launch_area_int(area_dev(h), io, rb, re, s, query);
+    case IQO_KERNEL_LINEAR_UP2: return iqo_amd::launch_linear_up2(linear_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_TILE: return iqo_amd::launch_tile(tile_dev(h), io, rb, re, s, query);
+    case IQO_KERNEL_WALK: return iqo_amd::launch_walk(walk_dev(h), io, rb, re, h->bands, s, 0, -1, 1, query);
+    case IQO_KERNEL_LANCZOS_UP2: return iqo_amd::launch_up2(up2_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_LANCZOS_D32: return iqo_amd::launch_d32(d32_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_LANCZOS_D31: return iqo_amd::launch_d31(d31_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_RYX: return iqo_amd::launch_ryx(ryx_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_RYG: {
+        iqo_amd::RygDev d = ryg_dev(h);
+        if (query) {
+            // a plan without device tables yet (host-only, or before the first call): the tables launch_ryg
+            // reads its two decisions off stand in as placeholders, which a query never dereferences
+            static const int4 kNoTable{};
+            if (!d.rowRec)
+                d.rowRec = &kNoTable;
+            if (d.nl == 1 && h->hasRyu && h->useRyu && !d.posRec)
+                d.posRec = &kNoTable;
+            if (d.run && !d.colRun)
+                d.colRun = reinterpret_cast<const uint32_t *>(&kNoTable);
+        }
+        return iqo_amd::launch_ryg(d, io, rb, re, h->bands, s, query);
+    }
+    case IQO_KERNEL_AREA_D32: return iqo_amd::launch_a32(a32_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_LANCZOS_U23: return iqo_amd::launch_u23(u23_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_LINEAR_U23: return iqo_amd::launch_l23(l23_dev(h), io, rb, re, h->bands, s, query);
+    case IQO_KERNEL_PACKED_TILE: return iqo_amd::launch_packed_tile(packed_tile_dev(h), h->channels, io, rb, re, s, query);
+    case IQO_KERNEL_PACKED_GENERAL: return iqo_amd::launch_packed_general(general_dev(h), h->channels, io, rb, re, s, query);
+    default: return iqo_amd::launch_general(general_dev(h), io, rb, re, s, query);
+    }
+}
+
+// Frames of run_band's first launch: at most 65535 (grid y), fewer with the option "chunk_frames".
+size_t frames_per_launch(const iqo_hip_plan *h, size_t nFrames)
+{
+    size_t chunk = 65535;
+    if (h->chunkFrames > 0) {
+        chunk = std::min(chunk, static_cast<size_t>(h->chunkFrames));
+        const size_t n = (nFrames + chunk - 1) / chunk;  // equal launches, not one straggler
+        chunk = (nFrames + n - 1) / n;
+    }
+    return chunk;
+}
+
+// iqo_hip_plan_launch_grid / iqo_host_launch_grid: the grid of the first launch of an aligned, tightly packed
+// run_band call of nFrames frames over output rows [r0, r0 + rows), from the launcher itself.
+int plan_launch_grid(const iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, iqo_hip_launch_grid *out)
+{
+    static_assert(IQO_GRID_MAP_NONE == iqo_amd::kMapNone && IQO_GRID_MAP_SPREAD == iqo_amd::kMapSpread &&
+                      IQO_GRID_MAP_CHUNKS == iqo_amd::kMapChunks && IQO_GRID_MAP_XCD_TAIL == iqo_amd::kMapXcdTail &&
+                      IQO_HIP_GRID_STRIDE_BLOCKS == iqo_amd::kGridStrideBlocks,
+                  "kernels.hpp kMap* / kGridStrideBlocks are iqo_hip.h's");
+    const Plan &p = h->p;
+    const size_t dstH = static_cast<size_t>(p.dstH);
+    if (r0 > dstH || rows > dstH - r0 || rows == 0 || nFrames == 0)
+        return IQO_HIP_EINVAL;
+    const int kernel = plan_kernel(h);
+    if (!ratio_prefetch_ok(h, kernel))
+        return IQO_HIP_EINVAL;
+    const int rb = static_cast<int>(r0), re = static_cast<int>(r0 + rows);
+    int s0, s1;
+    iqo_amd::band_src_rows(p, rb, re, &s0, &s1);
+    const size_t C = static_cast<size_t>(h->channels), frames = std::min(frames_per_launch(h, nFrames), nFrames);
+    const size_t srcSt = (static_cast<size_t>(p.srcW) * C + 15) & ~size_t(15), dstSt = (static_cast<size_t>(p.dstW) * C + 15) & ~size_t(15);
+    const iqo_amd::Io io = make_io(frames, nullptr, srcSt, srcSt * static_cast<size_t>(p.srcH), 0, s1, nullptr, dstSt,
+                                   dstSt * dstH, rb);
+    iqo_amd::LaunchGrid g;
+    const hipError_t e = launch_family(h, kernel, io, rb, re, nullptr, &g);
+    if (e == hipErrorNotSupported)
+        return IQO_HIP_EUNSUP;
+    if (e != hipSuccess)
+        return IQO_HIP_EINVAL;
+    *out = iqo_hip_launch_grid{};
+    out->family = kernel;
+    out->map = g.map;
+    out->gridX = g.gridX;
+    out->gridY = g.gridY;
+    out->gridZ = g.gridZ;
+    out->block = g.block;
+    out->blocks = g.blocks;
+    out->chunk = g.chunk;
+    out->unitsPerFrame = g.unitsPerFrame;
+    out->unitsPerBlock = g.unitsPerBlock;
+    out->units = g.units;
+    out->bands = g.bands;
+    out->wavesPerRow = g.wavesPerRow;
+    out->framesPerBlock = g.framesPerBlock;
+    out->tailBands = g.tailBands;
+    out->frames = static_cast<unsigned>(frames);
+    return IQO_HIP_OK;
+}
+
 int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t srcRow0, size_t srcSt,
              size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstFrameSt, uint8_t *dst, hipStream_t s)
 {
@@ -1651,50 +1750,13 @@ int run_band(iqo_hip_plan *h, size_t nFrames, size_t r0, size_t rows, size_t src
     // Frames per launch: at most 65535 (grid y).  The option "chunk_frames" splits further into
     // equal launches (measured: no gain on MI355X for C2 at 256 frames, a loss for C3 at 48 --
     // the per-frame slowdown of C2 past ~130 frames per call is not a per-launch effect).
-    size_t chunk = 65535;
-    if (h->chunkFrames > 0) {
-        chunk = std::min(chunk, static_cast<size_t>(h->chunkFrames));
-        const size_t n = (nFrames + chunk - 1) / chunk;  // equal launches, not one straggler
-        chunk = (nFrames + n - 1) / n;
-    }
+    const size_t chunk = frames_per_launch(h, nFrames);
     if (!ratio_prefetch_ok(h, kernel))
         return IQO_HIP_EINVAL;
     for (size_t f0 = 0; f0 < nFrames; f0 += chunk) {
         const iqo_amd::Io io = make_io(std::min(chunk, nFrames - f0), src + f0 * srcFrameSt, srcSt, srcFrameSt, srcRow0,
                                        s1, dst + f0 * dstFrameSt, dstSt, dstFrameSt, rb);
-        hipError_t e = hipSuccess;
-        if (kernel == IQO_KERNEL_LANCZOS_STREAM)
-            e = iqo_amd::launch_lanczos_stream(lanczos_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_AREA_INT)
-            e = iqo_amd::launch_area_int(area_dev(h), io, rb, re, s);
-        else if (kernel == IQO_KERNEL_LINEAR_UP2)
-            e = iqo_amd::launch_linear_up2(linear_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_TILE)
-            e = iqo_amd::launch_tile(tile_dev(h), io, rb, re, s);
-        else if (kernel == IQO_KERNEL_WALK)
-            e = iqo_amd::launch_walk(walk_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_LANCZOS_UP2)
-            e = iqo_amd::launch_up2(up2_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_LANCZOS_D32)
-            e = iqo_amd::launch_d32(d32_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_LANCZOS_D31)
-            e = iqo_amd::launch_d31(d31_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_RYX)
-            e = iqo_amd::launch_ryx(ryx_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_RYG)
-            e = iqo_amd::launch_ryg(ryg_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_AREA_D32)
-            e = iqo_amd::launch_a32(a32_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_LANCZOS_U23)
-            e = iqo_amd::launch_u23(u23_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_LINEAR_U23)
-            e = iqo_amd::launch_l23(l23_dev(h), io, rb, re, h->bands, s);
-        else if (kernel == IQO_KERNEL_PACKED_TILE)
-            e = iqo_amd::launch_packed_tile(packed_tile_dev(h), h->channels, io, rb, re, s);
-        else if (kernel == IQO_KERNEL_PACKED_GENERAL)
-            e = iqo_amd::launch_packed_general(general_dev(h), h->channels, io, rb, re, s);
-        else
-            e = iqo_amd::launch_general(general_dev(h), io, rb, re, s);
+        const hipError_t e = launch_family(h, kernel, io, rb, re, s, nullptr);
         // the launchers reject a parameter set they have no instantiation for before launching
         // (hipErrorInvalidValue / hipErrorNotSupported): a plan / kernel mismatch, reported as such
         // (the drop-in classes report those on every call instead of falling back for good)
@@ -1856,6 +1918,16 @@ int iqo_hip_plan_instance(const iqo_hip_plan *h, size_t srcAlign, size_t dstAlig
     if (!h || !desc || !valid_align(srcAlign) || !valid_align(dstAlign))
         return IQO_HIP_EINVAL;
     return plan_instance(h, Layout{srcAlign, dstAlign}, desc);
+}
+
+int iqo_hip_plan_launch_grid(const iqo_hip_plan *h, size_t nFrames, size_t dstRow0, size_t dstRows, iqo_hip_launch_grid *desc)
+{
+    if (!h || !desc)
+        return IQO_HIP_EINVAL;
+    DeviceGuard guard(h->device);  // (the automatic band counts ask the plan's device for its occupancy)
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    return plan_launch_grid(h, nFrames, dstRow0, dstRows, desc);
 }
 
 int iqo_hip_plan_prepare(iqo_hip_plan *h)
@@ -3413,6 +3485,26 @@ int iqo_host_instance_for(int method, unsigned degree, size_t srcW, size_t srcH,
             return rc;
     }
     return plan_instance(&h, Layout{srcAlign, dstAlign}, desc);
+}
+
+int iqo_host_launch_grid(int method, unsigned degree, int channels, size_t srcW, size_t srcH, size_t dstW, size_t dstH,
+                         size_t pxScale, const iqo_hip_option *options, size_t nOptions, size_t nFrames,
+                         iqo_hip_launch_grid *desc)
+{
+    if (method < 0 || method > 2 || channels < 1 || channels > 4 || !desc || (nOptions && !options))
+        return IQO_HIP_EINVAL;
+    iqo_hip_plan h;  // host half of a plan only: no device memory
+    std::string err;
+    if (!iqo_amd::build_plan(static_cast<iqo_amd::Method>(method), degree, srcW, srcH, dstW, dstH, pxScale, &h.p, &err))
+        return IQO_HIP_EINVAL;
+    h.channels = channels;
+    build_host_tables(&h);
+    for (size_t i = 0; i < nOptions; ++i) {
+        const int rc = iqo_hip_plan_set_option(&h, options[i].key, options[i].value);
+        if (rc)
+            return rc;
+    }
+    return plan_launch_grid(&h, nFrames, 0, dstH, desc);
 }
 
 int iqo_host_lanczos_yfold(int method, unsigned degree, size_t srcW, size_t srcH, size_t dstW, size_t dstH, size_t pxScale)

@@ -2385,12 +2385,16 @@ __global__ __launch_bounds__(256) void yuv420_plane_kernel(Yuv3Args<A, A> a)
 // ================================================================ launchers
 
 
-hipError_t launch_general(const GeneralDev &g, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
+hipError_t launch_general(const GeneralDev &g, const Io &io, int rowBegin, int rowEnd, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
     GeneralArgs a{g, io, rowBegin};
     dim3 grid(static_cast<unsigned>(rowEnd - rowBegin), static_cast<unsigned>(io.frames));
+    if (query) {
+        *query = plain_grid(kFamGeneral, grid, 256, 0, 0);
+        return hipSuccess;
+    }
     size_t lds = static_cast<size_t>(g.ldsInts) * sizeof(int);
     hipLaunchKernelGGL(general_kernel, grid, dim3(256), lds, s, a);
     return hipGetLastError();
@@ -2468,7 +2472,7 @@ InstanceList tile_walk_instances(int family)
     return family == kFamTile ? tile_instances() : family == kFamWalk ? walk_instances() : InstanceList{nullptr, 0};
 }
 
-hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
+hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2489,12 +2493,16 @@ hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd,
     if (!inst)
         return hipErrorInvalidValue;
     const void *kern = inst->kern;
+    if (query) {
+        *query = block_grid(kFamTile, kMapChunks, static_cast<unsigned>(nTx * nTy), static_cast<unsigned>(nTiles), 256, nTy);
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, grid, dim3(256), args, lds, s);
 }
 
 hipError_t launch_walk(const WalkDev &w, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s,
-                       int stripLo, int strips, int stripStride)
+                       int stripLo, int strips, int stripStride, LaunchGrid *query)
 {
     if (strips < 0)
         strips = w.nS;
@@ -2530,6 +2538,10 @@ hipError_t launch_walk(const WalkDev &w, const Io &io, int rowBegin, int rowEnd,
         return hipErrorInvalidValue;
     WalkArgs a{w, io, rowBegin, rowEnd, rpb, bands, static_cast<int>(sb), static_cast<int>(db),
                static_cast<unsigned>(nWaves), stripLo, strips, stripStride};
+    if (query) {
+        *query = wave_grid(kFamWalk, bands, strips, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, lds, s);
 }
@@ -2554,6 +2566,7 @@ struct Prep {
     const void *kern = nullptr;
     int kind = 0;  // Lanczos: 0 accumulator ring, 1 block-shared symmetric, 2 per-wave symmetric
     int pd = 0;    // prefetch / ring depth the instantiation was chosen for
+    LaunchGrid q;  // what a grid query of this launch reports
 };
 
 hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int rowEnd, int bands, Prep<LanczosArgs> *P)
@@ -2738,11 +2751,29 @@ hipError_t prep_lanczos(const LanczosDev &l, const Io &io, int rowBegin, int row
     P->kern = kern;
     P->kind = stack ? 3 : shared ? 1 : (l.sym ? 2 : 0);
     P->pd = pd;
+    // block-shared: the kernel folds (band, frame) into one id and maps it by chunks of one frame's bands,
+    // or, tail split, decodes its own 1-D grid; stacked and per-wave: plain 2-D grids
+    LaunchGrid &q = P->q;
+    q = plain_grid(kFamLanczosStream, P->grid, block, bands, wpr);
+    q.framesPerBlock = static_cast<unsigned>(fpw);
+    if (shared && !stack) {
+        q.unitsPerFrame = static_cast<unsigned>(bands);
+        q.unitsPerBlock = 1;
+        if (a.tailBands > 0) {
+            q.map = kMapXcdTail;
+            q.units = q.blocks;
+            q.tailBands = a.tailBands;
+        } else {
+            q.map = kMapChunks;
+            q.chunk = static_cast<unsigned>(bands);
+            q.units = q.blocks = P->grid.x * P->grid.y;
+        }
+    }
     return hipSuccess;
 }
 
 hipError_t launch_lanczos_stream(const LanczosDev &l, const Io &io, int rowBegin, int rowEnd, int bands,
-                                 hipStream_t s)
+                                 hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2750,6 +2781,10 @@ hipError_t launch_lanczos_stream(const LanczosDev &l, const Io &io, int rowBegin
     hipError_t e = prep_lanczos(l, io, rowBegin, rowEnd, bands, &P);
     if (e != hipSuccess)
         return e;
+    if (query) {
+        *query = P.q;
+        return hipSuccess;
+    }
     void *args[] = {&P.a};
     return hipLaunchKernel(P.kern, P.grid, dim3(static_cast<unsigned>(P.block)), args, static_cast<size_t>(P.lds), s);
 }
@@ -2784,12 +2819,16 @@ hipError_t prep_area(const AreaDev &g, const Io &io, int rowBegin, int rowEnd, P
     return hipSuccess;
 }
 
-hipError_t launch_area_int(const AreaDev &g, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
+hipError_t launch_area_int(const AreaDev &g, const Io &io, int rowBegin, int rowEnd, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
     Prep<AreaArgs> P;
     (void)prep_area(g, io, rowBegin, rowEnd, &P);
+    if (query) {
+        *query = plain_grid(kFamAreaInt, P.grid, 256, 0, 0);
+        return hipSuccess;
+    }
     void *args[] = {&P.a};
     return hipLaunchKernel(P.kern, P.grid, dim3(256), args, 0, s);
 }
@@ -2853,7 +2892,7 @@ hipError_t prep_linear(const LinearDev &g, const Io &io, int rowBegin, int rowEn
 }
 
 hipError_t launch_linear_up2(const LinearDev &g, const Io &io, int rowBegin, int rowEnd, int bands,
-                             hipStream_t s)
+                             hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2861,6 +2900,10 @@ hipError_t launch_linear_up2(const LinearDev &g, const Io &io, int rowBegin, int
     hipError_t e = prep_linear(g, io, rowBegin, rowEnd, bands, &P);
     if (e != hipSuccess)
         return e;
+    if (query) {
+        *query = plain_grid(kFamLinearUp2, P.grid, 256, P.a.bands, P.a.wavesPerRow);
+        return hipSuccess;
+    }
     void *args[] = {&P.a};
     return hipLaunchKernel(P.kern, P.grid, dim3(256), args, 0, s);
 }

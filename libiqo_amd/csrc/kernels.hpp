@@ -83,6 +83,28 @@ inline bool layout_ok(int family, const Io &io, int rowEnd, int64_t srcRowBytes,
     *db = m.dstSpanMax ? static_cast<int64_t>(rowEnd - 1 - io.dstRow0) * io.dstSt + dstRowBytes : 0;  // stores are relative to dstRow0
     return *sb <= m.srcSpanMax && *db <= m.dstSpanMax;
 }
+// --- the grid of one launch, by number (iqo_hip.h iqo_hip_launch_grid).  Every launcher below takes a
+// trailing `LaunchGrid *query`: non-null, it runs the arithmetic it launches with -- instantiation, lanes,
+// bands, units, grid -- fills *query and launches nothing, so the report cannot drift from the launch.
+// A "unit" is what the kernel decodes (column, band, frame) from: a wave (walker, exact-ratio kernels), a
+// tile (tile, packed tile) or a workgroup (ryx / ryg / ryu, the block-shared and stacked streamers).
+constexpr int kMapNone = 0, kMapSpread = 1, kMapChunks = 2, kMapXcdTail = 3;  // iqo_hip.h IQO_GRID_MAP_*
+struct LaunchGrid {
+    int family = 0;
+    int map = kMapNone;          // how a flat block id becomes a logical one (kernels_dev.hpp xcd_*)
+    unsigned gridX = 0, gridY = 1, gridZ = 1, block = 0;
+    unsigned blocks = 0;         // n of the map: the flat ids it permutes (map none: gridX)
+    unsigned chunk = 0;          // C of xcd_chunks (0: the map has none)
+    unsigned unitsPerFrame = 0, unitsPerBlock = 0;
+    unsigned units = 0;          // the kernel's nWaves / nTiles / nBlocks argument
+    int bands = 0, wavesPerRow = 0;  // 0: the family has none
+    unsigned framesPerBlock = 1; // stacked streamer: frames side by side in one workgroup
+    int tailBands = 0;           // kMapXcdTail: bands of each XCD's last frame (the others: `bands`)
+};
+// Blocks of a grid-stride launch of the second-pass kernels (kernels_color.hip, kernels_norm.hip): a launch
+// of more than kGridStrideBlocks * 256 items strides over the rest (iqo_hip.h IQO_HIP_GRID_STRIDE_BLOCKS).
+constexpr unsigned kGridStrideBlocks = 2048;
+
 struct Instance {
     int family, sub;
     int LZ, P, Q, T, NP, PD, ADJ, CPT, UC, NL, RUN, KM, VY, NV, NT, F, VARIANT;
@@ -106,7 +128,7 @@ struct GeneralDev {
     int nChunks;
     int ldsInts;                 // work-row capacity (ints) of the largest chunk
 };
-hipError_t launch_general(const GeneralDev &g, const Io &io, int rowBegin, int rowEnd, hipStream_t s);
+hipError_t launch_general(const GeneralDev &g, const Io &io, int rowBegin, int rowEnd, hipStream_t s, LaunchGrid *query = nullptr);
 // --- separable tile kernel (general ratios): tables from plan.cpp build_tile_tables.
 struct TileDev {
     bool lanczos;                // int16 work + signed dots (else u16 work, Area / Linear)
@@ -121,7 +143,7 @@ struct TileDev {
     int nQp;                     // quads of the padded tile width
     const int4 *spans;           // {lo8, groups, any border column, 0} per column tile
 };
-hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s);
+hipError_t launch_tile(const TileDev &t, const Io &io, int rowBegin, int rowEnd, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *tile_instance(const TileDev &t);      // null: no instantiation (launch_tile rejects it)
 
 
@@ -129,12 +151,12 @@ const Instance *tile_instance(const TileDev &t);      // null: no instantiation 
 // (kernels_packed.hip).  Widths in GeneralDev / TileDev stay in PIXELS; Io strides are bytes.
 // packed_general_kernel: general_kernel per channel.
 hipError_t launch_packed_general(const GeneralDev &g, int channels, const Io &io, int rowBegin, int rowEnd,
-                                 hipStream_t s);
+                                 hipStream_t s, LaunchGrid *query = nullptr);
 // packed_tile_kernel: the planar tile tables (rows, rowTap, cols, colCoef, colA, nQp) with the
 // packed tiling of plan.hpp PackedTables in CT, TH, pitchDw (one channel segment), log2nQ, srcRows,
 // spitch and spans ({lo8 pixel, 8-pixel groups, any border column, 0} per column tile).
 hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd,
-                              hipStream_t s);
+                              hipStream_t s, LaunchGrid *query = nullptr);
 
 // --- normalised planar float output of the two packed kernels (their NORM instantiations): plane p
 // of the output is cvt(fl32(fl32((float)u8(order[p]) * scale[p]) + bias[p])) of the byte the U8 path
@@ -149,9 +171,9 @@ struct NormDev {
     float scale[4], bias[4];
 };
 hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const Io &io, const NormDev &n, int rowBegin,
-                                      int rowEnd, hipStream_t s);
+                                      int rowEnd, hipStream_t s, LaunchGrid *query = nullptr);
 hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io, const NormDev &n, int rowBegin,
-                                   int rowEnd, hipStream_t s);
+                                   int rowEnd, hipStream_t s, LaunchGrid *query = nullptr);
 
 // --- batched crop-and-resize (kernels_roi.hip roi_kernel): one launch over the workgroups of a call's
 // arena (roi.hpp), which lies in device memory at `arena` and names every box, its tables and its
@@ -271,7 +293,7 @@ struct WalkDev {
 };
 // strips stripLo + i * stripStride (i < strips; strips < 0: all of them)
 hipError_t launch_walk(const WalkDev &w, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s,
-                       int stripLo = 0, int strips = -1, int stripStride = 1);
+                       int stripLo = 0, int strips = -1, int stripStride = 1, LaunchGrid *query = nullptr);
 const Instance *walk_instance(const WalkDev &w);
 
 // --- exact 2x Lanczos-2/3 upscale, main rows x middle columns (plan.hpp Up2Tables).
@@ -290,7 +312,7 @@ struct Up2Dev {
     uint32_t yM[2][16];          //   magic_y (top: row y, bottom: row y - m1)
     int yS[2][16];
 };
-hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *up2_instance(const Up2Dev &u);
 
 // Exact 3:2 Lanczos-3 downscale (plan.hpp D32Tables): main rows x all columns.
@@ -307,7 +329,7 @@ struct D32Dev {
     uint32_t yM[2][8];           //   magic_y (top: row y, bottom: row y - m1)
     int yS[2][8];
 };
-hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *d32_instance(const D32Dev &d);
 
 // Exact 3:1 Lanczos-2/3 downscale (plan.hpp D31Tables): every row and column.
@@ -324,7 +346,7 @@ struct D31Dev {
     uint32_t yM[2][8];           //   magic_y (top: row y, bottom: row y - m1)
     int yS[2][8];
 };
-hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *d31_instance(const D31Dev &d);
 
 // Exact vertical ratio, tabled columns (plan.hpp RyxTables): every row and column.
@@ -353,7 +375,7 @@ struct RyxDev {
     // starting on the same parity), so the kernel reads them once as scalars (kernels.hip UC)
     int uc = 0;
 };
-hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *ryx_instance(const RyxDev &d);
 
 // General-row variant (plan.hpp build_ryg; kernels.hip ryg_kernel): ryx's tabled columns and column
@@ -390,9 +412,10 @@ struct RygDev {
     const uint32_t *colRun = nullptr;
     int run = 0;
 };
-hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 // byPos: rows by window position (ryu_kernel) -- launch_ryg: d.nl == 1 && d.posRec; a host-only plan has no
-// device tables and passes what ryg_dev decided (abi.hip plan_instance).  run: the run mode in use (0: none).
+// device tables and passes what ryg_dev decided (abi.hip plan_instance; a grid query of such a plan hands
+// launch_ryg placeholder table pointers in their place, which a query never dereferences).  run: the run mode in use (0: none).
 const Instance *ryg_instance(const RygDev &d, bool byPos, int run);
 
 // Exact 2:3 Lanczos-3 upscale (plan.hpp U23Tables).
@@ -408,7 +431,7 @@ struct U23Dev {
     uint32_t yM[2][8];
     int yS[2][8];
 };
-hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *u23_instance(const U23Dev &d);
 
 // Exact 2:3 Linear upscale (plan.hpp L23Tables).
@@ -419,7 +442,7 @@ struct L23Dev {
     uint32_t cy[3][2];           // (c, c) u16 splats of phase j's two taps
     uint32_t cx[3];              // phase j's (c_0, c_1) u16 pair
 };
-hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *l23_instance(const L23Dev &d);
 
 // Exact 3:2 Area downscale (plan.hpp A32Tables).
@@ -430,7 +453,7 @@ struct A32Dev {
     uint32_t cy[2][2];           // (c, c) u16 splats of phase p's two taps
     uint32_t cx[2];              // phase p's (c_0, c_1) u16 pair
 };
-hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s);
+hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query = nullptr);
 const Instance *a32_instance(const A32Dev &d);
 
 // --- Lanczos row-band streamer (integer ratio, single phase).
@@ -484,7 +507,7 @@ inline bool symb_yfold(const LanczosDev &l)
 }
 bool lanczos_stream_supported(int KY, int KX, int NY, int NXP, int offX);
 hipError_t launch_lanczos_stream(const LanczosDev &l, const Io &io, int rowBegin, int rowEnd, int bands,
-                                 hipStream_t s);
+                                 hipStream_t s, LaunchGrid *query = nullptr);
 int lanczos_stream_block(int srcW);
 
 // --- Area integer-ratio kernel.
@@ -495,7 +518,7 @@ struct AreaDev {
     int lin;                     // 1: Linear at exactly 2:1 (linear_d2_body: taps 2i+1, 2i+2, edge
     int srcH;                    //    rows / columns replicated); cy[0..1] / cx[0] its two taps
 };
-hipError_t launch_area_int(const AreaDev &a, const Io &io, int rowBegin, int rowEnd, hipStream_t s);
+hipError_t launch_area_int(const AreaDev &a, const Io &io, int rowBegin, int rowEnd, hipStream_t s, LaunchGrid *query = nullptr);
 
 // --- exact 2x bilinear upsampler.
 struct LinearDev {
@@ -507,7 +530,7 @@ struct LinearDev {
     int np;                      // producing lanes per wave (0 = auto)
 };
 hipError_t launch_linear_up2(const LinearDev &l, const Io &io, int rowBegin, int rowEnd, int bands,
-                             hipStream_t s);
+                             hipStream_t s, LaunchGrid *query = nullptr);
 
 // --- YUV 4:2:0: the Y, U and V planes of a batch in ONE launch (grid.z = plane) when both plane
 // kinds have a fused instantiation; hipErrorNotSupported otherwise (launch plane by plane).

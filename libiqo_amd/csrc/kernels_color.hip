@@ -261,9 +261,8 @@ __global__ __launch_bounds__(256) void yuv_rgb_kernel(std::conditional_t<NORM, Y
     }
 }
 
-// Grid: 256-thread blocks over the items, capped at 8 blocks per CU of a 256-CU device; the
-// kernel strides over the rest.
-constexpr unsigned kMaxBlocks = 2048;
+// Grid: 256-thread blocks over the items, capped at kernels.hpp kGridStrideBlocks (8 blocks per CU of a
+// 256-CU device); the kernel strides over the rest.
 
 // c444: the chroma planes are on the output grid (cw x ch = dstW x dstH) and a thread loads as many
 // chroma samples per component as pixels -- 16 bytes of UV, or 8 each of U and V, for 8 pixels.
@@ -321,7 +320,7 @@ hipError_t launch_yuv_rgb_bytes(const YuvRgbDev &d, bool interleavedUV, bool chr
         a.sel[1] = o1 | (o2 << 8) | ((o0 + 4) << 16) | ((o1 + 4) << 24);
         a.sel[2] = o2 | ((o0 + 4) << 8) | ((o1 + 4) << 16) | ((o2 + 4) << 24);
     }
-    const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
+    const unsigned blocks = std::min((a.items + 255u) / 256u, kGridStrideBlocks);
     const void *kern = kernel_of<false, 8>(interleavedUV, chroma444);
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(blocks), dim3(256), args, 0, s);
@@ -342,7 +341,7 @@ hipError_t launch_yuv_rgb_norm(const YuvRgbDev &d, bool interleavedUV, bool chro
     a.nG = (d.dstW + px - 1) / px;
     a.items = static_cast<unsigned>(d.frames) * static_cast<unsigned>(d.dstH) * static_cast<unsigned>(a.nG);
     a.n = n;
-    const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
+    const unsigned blocks = std::min((a.items + 255u) / 256u, kGridStrideBlocks);
     const void *kern = px == 4 ? kernel_of<true, 4>(interleavedUV, chroma444) : kernel_of<true, 8>(interleavedUV, chroma444);
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(blocks), dim3(256), args, 0, s);
@@ -526,7 +525,7 @@ hipError_t launch_rgb_yuv(const RgbYuvDev &d, int channels, bool interleavedUV, 
             a.sel[j] = (off[j] + static_cast<uint32_t>(d.order[0])) | ((off[j] + static_cast<uint32_t>(d.order[1])) << 8) |
                        ((off[j] + static_cast<uint32_t>(d.order[2])) << 16) | (0x0cu << 24);
     }
-    const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
+    const unsigned blocks = std::min((a.items + 255u) / 256u, kGridStrideBlocks);
     const void *kern = channels == 4 ? (interleavedUV ? reinterpret_cast<const void *>(rgb_yuv_kernel<4, true>)
                                                       : reinterpret_cast<const void *>(rgb_yuv_kernel<4, false>))
                                      : (interleavedUV ? reinterpret_cast<const void *>(rgb_yuv_kernel<3, true>)

@@ -334,6 +334,50 @@ __device__ __forceinline__ T pick4(const T (&v)[4], int p)
     return waves;
 }
 
+// LaunchGrid (kernels.hpp) of the two frame-folding grid shapes.  Waves: 4 per 256-thread block, the
+// block id permuted by xcd_chunks with C = one frame's blocks, rounded up.  Blocks: one unit per block.
+[[maybe_unused]] LaunchGrid wave_grid(int family, int bands, int wavesPerRow, unsigned nWaves)
+{
+    LaunchGrid g;
+    g.family = family;
+    g.map = kMapChunks;
+    g.gridX = g.blocks = (nWaves + 3u) / 4u;
+    g.block = 256;
+    g.unitsPerFrame = static_cast<unsigned>(bands) * static_cast<unsigned>(wavesPerRow);
+    g.chunk = (g.unitsPerFrame + 3u) / 4u;
+    g.unitsPerBlock = 4;
+    g.units = nWaves;
+    g.bands = bands;
+    g.wavesPerRow = wavesPerRow;
+    return g;
+}
+[[maybe_unused]] LaunchGrid block_grid(int family, int map, unsigned perFrame, unsigned nBlocks, int threads, int bands)
+{
+    LaunchGrid g;
+    g.family = family;
+    g.map = map;
+    g.gridX = g.blocks = g.units = nBlocks;
+    g.block = static_cast<unsigned>(threads);
+    g.unitsPerFrame = perFrame;
+    g.chunk = map == kMapChunks ? perFrame : 0;
+    g.unitsPerBlock = 1;
+    g.bands = bands;
+    return g;
+}
+// ... and of a family that keeps the frames in gridDim.y (no map)
+[[maybe_unused]] LaunchGrid plain_grid(int family, dim3 grid, int block, int bands, int wavesPerRow)
+{
+    LaunchGrid g;
+    g.family = family;
+    g.gridX = g.blocks = grid.x;
+    g.gridY = grid.y;
+    g.gridZ = grid.z;
+    g.block = static_cast<unsigned>(block);
+    g.bands = bands;
+    g.wavesPerRow = wavesPerRow;
+    return g;
+}
+
 // Row bands per frame for a band-walking kernel: minimise the makespan in rows walked,
 // (waves in flight rounds) x (rows per band + halo rows re-read at every band start), so that
 // the grid fills whole rounds of the resident waves instead of leaving a straggler round.

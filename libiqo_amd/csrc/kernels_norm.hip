@@ -108,9 +108,8 @@ __global__ __launch_bounds__(256) void planes_norm_kernel(PlanesNormArgs a)
     }
 }
 
-// Grid: 256-thread blocks over the items, capped at 8 blocks per CU of a 256-CU device; the
-// kernel strides over the rest.
-constexpr unsigned kMaxBlocks = 2048;
+// Grid: 256-thread blocks over the items, capped at kernels.hpp kGridStrideBlocks (8 blocks per CU of a
+// 256-CU device); the kernel strides over the rest.
 
 // a thread loads 8 bytes whole at a multiple of 8 from the plane's row start (fp32: 4 at a multiple of 4)
 bool dev_ok(const PlanesNormDev &d)
@@ -142,7 +141,7 @@ hipError_t launch_planes_norm(const PlanesNormDev &d, const NormDev &n, hipStrea
     a.nG = (d.dstW + px - 1) / px;
     a.items = static_cast<unsigned>(d.frames) * static_cast<unsigned>(d.dstH) * static_cast<unsigned>(a.nG);
     a.n = n;
-    const unsigned blocks = std::min((a.items + 255u) / 256u, kMaxBlocks);
+    const unsigned blocks = std::min((a.items + 255u) / 256u, kGridStrideBlocks);
     const void *kern = px == 4 ? reinterpret_cast<const void *>(planes_norm_kernel<4>)
                                : reinterpret_cast<const void *>(planes_norm_kernel<8>);
     void *args[] = {&a};

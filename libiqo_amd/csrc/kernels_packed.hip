@@ -588,7 +588,7 @@ bool norm_ok(const NormDev &n, int channels)
 // ================================================================ launchers
 
 hipError_t launch_packed_general(const GeneralDev &g, int channels, const Io &io, int rowBegin, int rowEnd,
-                                 hipStream_t s)
+                                 hipStream_t s, LaunchGrid *query)
 {
     if (channels < 2 || channels > 4)
         return hipErrorInvalidValue;
@@ -596,13 +596,17 @@ hipError_t launch_packed_general(const GeneralDev &g, int channels, const Io &io
         return hipSuccess;
     PackedGeneralArgs a{g, io, rowBegin, channels};
     dim3 grid(static_cast<unsigned>(rowEnd - rowBegin), static_cast<unsigned>(io.frames), static_cast<unsigned>(channels));
+    if (query) {
+        *query = plain_grid(kFamPackedGeneral, grid, 256, 0, 0);
+        return hipSuccess;
+    }
     size_t lds = static_cast<size_t>(g.ldsInts) * sizeof(int);
     hipLaunchKernelGGL(packed_general_kernel, grid, dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const Io &io, const NormDev &n, int rowBegin,
-                                      int rowEnd, hipStream_t s)
+                                      int rowEnd, hipStream_t s, LaunchGrid *query)
 {
     if (channels < 2 || channels > 4 || !norm_ok(n, channels))
         return hipErrorInvalidValue;
@@ -612,6 +616,10 @@ hipError_t launch_packed_general_norm(const GeneralDev &g, int channels, const I
     static_cast<PackedGeneralArgs &>(a) = PackedGeneralArgs{g, io, rowBegin, channels};
     a.n = n;
     dim3 grid(static_cast<unsigned>(rowEnd - rowBegin), static_cast<unsigned>(io.frames), static_cast<unsigned>(n.planes));
+    if (query) {
+        *query = plain_grid(kFamPackedGeneral, grid, 256, 0, 0);
+        return hipSuccess;
+    }
     size_t lds = static_cast<size_t>(g.ldsInts) * sizeof(int);
     hipLaunchKernelGGL(packed_general_norm_kernel, grid, dim3(256), lds, s, a);
     return hipGetLastError();
@@ -621,7 +629,7 @@ namespace {
 
 // norm == nullptr: the U8 kernel; else its NORM instantiation on the float frame io.dst
 hipError_t launch_ptile(const TileDev &t, int channels, const Io &io, const NormDev *norm, int rowBegin, int rowEnd,
-                        hipStream_t s)
+                        hipStream_t s, LaunchGrid *query)
 {
     if (channels < 2 || channels > 4 || (norm && !norm_ok(*norm, channels)))
         return hipErrorInvalidValue;
@@ -650,6 +658,10 @@ hipError_t launch_ptile(const TileDev &t, int channels, const Io &io, const Norm
     const void *kern = norm ? packed_tile_any<true>(channels, t.lanczos, t.NP) : packed_tile_any<false>(channels, t.lanczos, t.NP);
     if (!kern)
         return hipErrorInvalidValue;
+    if (query) {
+        *query = block_grid(kFamPackedTile, kMapChunks, static_cast<unsigned>(nTx * nTy), static_cast<unsigned>(nTiles), 256, nTy);
+        return hipSuccess;
+    }
     PackedTileNormArgs an;
     void *args[] = {&a};
     if (norm) {
@@ -662,15 +674,16 @@ hipError_t launch_ptile(const TileDev &t, int channels, const Io &io, const Norm
 
 } // namespace
 
-hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd, hipStream_t s)
+hipError_t launch_packed_tile(const TileDev &t, int channels, const Io &io, int rowBegin, int rowEnd, hipStream_t s,
+                              LaunchGrid *query)
 {
-    return launch_ptile(t, channels, io, nullptr, rowBegin, rowEnd, s);
+    return launch_ptile(t, channels, io, nullptr, rowBegin, rowEnd, s, query);
 }
 
 hipError_t launch_packed_tile_norm(const TileDev &t, int channels, const Io &io, const NormDev &n, int rowBegin,
-                                   int rowEnd, hipStream_t s)
+                                   int rowEnd, hipStream_t s, LaunchGrid *query)
 {
-    return launch_ptile(t, channels, io, &n, rowBegin, rowEnd, s);
+    return launch_ptile(t, channels, io, &n, rowBegin, rowEnd, s, query);
 }
 
 } // namespace iqo_amd

@@ -2538,7 +2538,7 @@ const Instance *ryg_instance(const RygDev &d, bool byPos, int run)
 
 // ================================================================ launchers
 
-hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2578,11 +2578,15 @@ hipError_t launch_up2(const Up2Dev &u, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     Up2Args a{u, io, rowBegin, rowEnd, rpb, bands, wpr, np, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nWaves)};
+    if (query) {
+        *query = wave_grid(kFamUp2, bands, wpr, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, 0, s);
 }
 
-hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2618,11 +2622,15 @@ hipError_t launch_d32(const D32Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     D32Args a{d, io, rowBegin, rowEnd, evenBegin, rpb, bands, wpr, np, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nWaves)};
+    if (query) {
+        *query = wave_grid(kFamD32, bands, wpr, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, 0, s);
 }
 
-hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2656,11 +2664,15 @@ hipError_t launch_d31(const D31Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     D31Args a{d, io, rowBegin, rowEnd, rpb, bands, wpr, np, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nWaves)};
+    if (query) {
+        *query = wave_grid(kFamD31, bands, wpr, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, 0, s);
 }
 
-hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2715,6 +2727,10 @@ hipError_t launch_ryx(const RyxDev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     RyxArgs a{d, io, rowBegin, rowEnd, groupBegin, rpb, bands, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nBlocks)};
+    if (query) {
+        *query = block_grid(kFamRyx, kMapChunks, static_cast<unsigned>(bands * d.parts), static_cast<unsigned>(nBlocks), threads, bands);
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>(nBlocks)), dim3(static_cast<unsigned>(threads)), args,
                            static_cast<size_t>(ldsBytes), s);
@@ -2727,7 +2743,7 @@ static hipError_t iqo_ryg_einval(int where)
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2782,12 +2798,17 @@ hipError_t launch_ryg(const RygDev &d, const Io &io, int rowBegin, int rowEnd, i
         return iqo_ryg_einval(8);
     RygArgs a{d, io, rowBegin, rowEnd, rpb, bands, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nBlocks)};
+    if (query) {  // (ryg_kernel keeps xcd_spread, ryu_kernel maps by chunks)
+        *query = block_grid(kFamRyg, byPos ? kMapChunks : kMapSpread, static_cast<unsigned>(bands * d.parts),
+                            static_cast<unsigned>(nBlocks), threads, bands);
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>(nBlocks)), dim3(static_cast<unsigned>(threads)), args,
                            static_cast<size_t>(ldsBytes), s);
 }
 
-hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2819,11 +2840,15 @@ hipError_t launch_u23(const U23Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     U23Args a{d, io, rowBegin, rowEnd, row3Begin, rpb, bands, wpr, np, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nWaves)};
+    if (query) {
+        *query = wave_grid(kFamU23, bands, wpr, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, 0, s);
 }
 
-hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2855,11 +2880,15 @@ hipError_t launch_l23(const L23Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     L23Args a{d, io, rowBegin, rowEnd, row3Begin, rpb, bands, wpr, np, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nWaves)};
+    if (query) {
+        *query = wave_grid(kFamL23, bands, wpr, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, 0, s);
 }
 
-hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s)
+hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, int bands, hipStream_t s, LaunchGrid *query)
 {
     if (rowEnd <= rowBegin || io.frames <= 0)
         return hipSuccess;
@@ -2892,6 +2921,10 @@ hipError_t launch_a32(const A32Dev &d, const Io &io, int rowBegin, int rowEnd, i
         return hipErrorInvalidValue;
     A32Args a{d, io, rowBegin, rowEnd, evenBegin, rpb, bands, wpr, np, static_cast<int>(sb), static_cast<int>(db),
               static_cast<unsigned>(nWaves)};
+    if (query) {
+        *query = wave_grid(kFamA32, bands, wpr, static_cast<unsigned>(nWaves));
+        return hipSuccess;
+    }
     void *args[] = {&a};
     return hipLaunchKernel(kern, dim3(static_cast<unsigned>((nWaves + 3) / 4)), dim3(256), args, 0, s);
 }
