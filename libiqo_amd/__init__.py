@@ -531,9 +531,10 @@ def _roi_array(boxes):
     return arr
 
 
-def _check_rois(rc, bad, boxes, what):
+def _check_rois(rc, bad, boxes, what, where=None):
     if rc != 0:
-        where = " (box %d: %s)" % (bad.value, tuple(boxes[bad.value])) if 0 <= bad.value < len(boxes) else ""
+        if where is None:
+            where = " (box %d: %s)" % (bad.value, tuple(boxes[bad.value])) if 0 <= bad.value < len(boxes) else ""
         err = IqoError("%s: %s (%d)%s" % (what, lib().iqo_hip_strerror(rc).decode(), rc, where))
         err.status, err.bad_roi = rc, bad.value  # IQO_HIP_E*, the first offending box (-1: the call itself)
         raise err
@@ -549,6 +550,42 @@ def _norm_of(C, scale, bias, order, code):
     for i in range(planes):
         n.order[i], n.scale[i], n.bias[i] = order[i], scale[i], bias[i]
     return n, planes
+
+
+def _host_roi_out_u8(shape, C, out):
+    """`out`, or a new array: uint8 of `shape` with contiguous pixels."""
+    import numpy as np
+    if out is None:
+        out = np.zeros(shape, np.uint8)
+    if out.dtype != np.uint8 or out.shape != shape or (shape[0] and (out.strides[2] != C or
+                                                                     (len(shape) == 4 and out.strides[3] != 1))):
+        raise IqoError("out must be a uint8 array %s with contiguous pixels" % (shape,))
+    return out
+
+
+def _host_roi_out_norm(C, scale, bias, order, dtype, N, dstH, dstW, out):
+    """(iqo_hip_norm, `out` or a new array [N, planes, dstH, dstW] of `dtype` with unit column stride)."""
+    import numpy as np
+    codes = {"float32": (OUT_F32, np.float32), "float16": (OUT_F16, np.float16), "bfloat16": (OUT_BF16, np.uint16)}
+    code, np_dtype = codes[dtype or "float32"]
+    n, planes = _norm_of(C, scale, bias, order, code)
+    shape = (N, planes, dstH, dstW)
+    if out is None:
+        out = np.zeros(shape, np_dtype)
+    if out.dtype != np_dtype or out.shape != shape or (N and out.strides[3] != out.itemsize):
+        raise IqoError("out must be a %s array %s with unit column stride" % (np_dtype.__name__, shape))
+    return n, out
+
+
+def _host_arena_stats(entry, method, degree, variant, dstW, dstH, boxes, nFrames, frameW, frameH):
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    boxes = [tuple(b) for b in boxes]
+    st, bad = RoiArenaStats(), ctypes.c_int(-1)
+    rc = getattr(lib(), "iqo_" + entry)(m, degree, variant, dstW, dstH, len(boxes), _roi_array(boxes), nFrames, frameW,
+                                        frameH, ctypes.byref(st), ctypes.byref(bad))
+    _check_rois(rc, bad, boxes, entry)
+    return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
+            "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
 
 
 def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=None, dtype=None, order=None, out=None):
@@ -569,26 +606,13 @@ def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=No
     arr, bad, N = _roi_array(boxes), ctypes.c_int(-1), len(boxes)
     head = (m, degree, C, dstW, dstH, N, arr, F, W, H, src.strides[1], src.strides[0], src.ctypes.data)
     if scale is None:
-        shape = (N, dstH, dstW) if src.ndim == 3 else (N, dstH, dstW, C)
-        if out is None:
-            out = np.zeros(shape, np.uint8)
-        if out.dtype != np.uint8 or out.shape != shape or (N and (out.strides[2] != C or
-                                                                  (src.ndim == 4 and out.strides[3] != 1))):
-            raise IqoError("out must be a uint8 array %s with contiguous pixels" % (shape,))
+        out = _host_roi_out_u8((N, dstH, dstW) if src.ndim == 3 else (N, dstH, dstW, C), C, out)
         if N == 0:  # (numpy gives an empty array no usable strides)
             return out
         rc = lib().iqo_host_resize_rois(*head, out.strides[1], out.strides[0], out.ctypes.data, ctypes.byref(bad))
         _check_rois(rc, bad, boxes, "host_resize_rois")
         return out
-    dtype = dtype or "float32"
-    codes = {"float32": (OUT_F32, np.float32), "float16": (OUT_F16, np.float16), "bfloat16": (OUT_BF16, np.uint16)}
-    n, planes = _norm_of(C, scale, bias, order, codes[dtype][0])
-    shape = (N, planes, dstH, dstW)
-    if out is None:
-        out = np.zeros(shape, codes[dtype][1])
-    e = out.itemsize
-    if out.dtype != codes[dtype][1] or out.shape != shape or (N and out.strides[3] != e):
-        raise IqoError("out must be a %s array %s with unit column stride" % (codes[dtype][1].__name__, shape))
+    n, out = _host_roi_out_norm(C, scale, bias, order, dtype, N, dstH, dstW, out)
     if N == 0:
         return out
     rc = lib().iqo_host_resize_rois_norm(*head, ctypes.byref(n), out.strides[2], out.strides[1], out.strides[0],
@@ -600,14 +624,7 @@ def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=No
 def host_roi_arena_stats(method, degree, dstW, dstH, channels, boxes, nFrames, frameW, frameH):
     """iqo_host_roi_arena_stats: {"arena_bytes", "x_tables", "y_tables", "workgroups", "lds_bytes", "record_bytes"}
     of the call's arena, without a GPU."""
-    m = _METHODS[method] if isinstance(method, str) else int(method)
-    boxes = [tuple(b) for b in boxes]
-    st, bad = RoiArenaStats(), ctypes.c_int(-1)
-    rc = lib().iqo_host_roi_arena_stats(m, degree, channels, dstW, dstH, len(boxes), _roi_array(boxes), nFrames, frameW,
-                                        frameH, ctypes.byref(st), ctypes.byref(bad))
-    _check_rois(rc, bad, boxes, "host_roi_arena_stats")
-    return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
-            "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
+    return _host_arena_stats("host_roi_arena_stats", method, degree, channels, dstW, dstH, boxes, nFrames, frameW, frameH)
 
 
 def host_roi_box_layout(method, degree, channels, dstW, dstH, w, h):
@@ -616,10 +633,7 @@ def host_roi_box_layout(method, degree, channels, dstW, dstH, w, h):
     m = _METHODS[method] if isinstance(method, str) else int(method)
     bl = RoiBoxLayout()
     rc = lib().iqo_host_roi_box_layout(m, degree, channels, dstW, dstH, w, h, ctypes.byref(bl))
-    if rc != 0:
-        err = IqoError("host_roi_box_layout: %s (%d) (box %d x %d)" % (lib().iqo_hip_strerror(rc).decode(), rc, w, h))
-        err.status, err.bad_roi = rc, -1  # IQO_HIP_E*; the call names no box index
-        raise err
+    _check_rois(rc, ctypes.c_int(-1), (), "host_roi_box_layout", " (box %d x %d)" % (w, h))  # (names no box index)
     return {"rows": bl.rows, "workgroups": bl.workgroups, "lds_bytes": bl.ldsBytes, "nYp": bl.nYp, "NP": bl.np,
             "pitchDw": bl.pitchDw}
 
@@ -666,26 +680,14 @@ def host_resize_rois_yuv(method, degree, dstW, dstH, src, boxes, frameW, frameH,
     head = (m, degree, lay, dstW, dstH, N, arr, src.shape[0], frameW, frameH, stY, stUV, src.strides[0], y, u, v, cs)
     if scale is None:
         C, o4 = _rgb_order(order)
-        shape = (N, dstH, dstW, C)
-        if out is None:
-            out = np.zeros(shape, np.uint8)
-        if out.dtype != np.uint8 or out.shape != shape or (N and (out.strides[2] != C or out.strides[3] != 1)):
-            raise IqoError("out must be a uint8 array %s with contiguous pixels" % (shape,))
+        out = _host_roi_out_u8((N, dstH, dstW, C), C, out)
         if N == 0:
             return out
         rc = lib().iqo_host_resize_rois_yuv_rgb(*head, C, o4, out.strides[1], out.strides[0], out.ctypes.data,
                                                 ctypes.byref(bad))
         _check_rois(rc, bad, boxes, "host_resize_rois_yuv")
         return out
-    dtype = dtype or "float32"
-    codes = {"float32": (OUT_F32, np.float32), "float16": (OUT_F16, np.float16), "bfloat16": (OUT_BF16, np.uint16)}
-    n, nplanes = _norm_of(3, scale, bias, planes, codes[dtype][0])
-    shape = (N, nplanes, dstH, dstW)
-    if out is None:
-        out = np.zeros(shape, codes[dtype][1])
-    e = out.itemsize
-    if out.dtype != codes[dtype][1] or out.shape != shape or (N and out.strides[3] != e):
-        raise IqoError("out must be a %s array %s with unit column stride" % (codes[dtype][1].__name__, shape))
+    n, out = _host_roi_out_norm(3, scale, bias, planes, dtype, N, dstH, dstW, out)
     if N == 0:
         return out
     rc = lib().iqo_host_resize_rois_yuv_norm(*head, ctypes.byref(n), out.strides[2], out.strides[1], out.strides[0],
@@ -697,14 +699,8 @@ def host_resize_rois_yuv(method, degree, dstW, dstH, src, boxes, frameW, frameH,
 def host_roi_yuv_arena_stats(method, degree, dstW, dstH, layout, boxes, nFrames, frameW, frameH):
     """iqo_host_roi_yuv_arena_stats: host_roi_arena_stats of a YUV box call; "x_tables" / "y_tables" count every
     distinct table once, whether luma, chroma or both use it."""
-    m = _METHODS[method] if isinstance(method, str) else int(method)
-    boxes = [tuple(b) for b in boxes]
-    st, bad = RoiArenaStats(), ctypes.c_int(-1)
-    rc = lib().iqo_host_roi_yuv_arena_stats(m, degree, _roi_layout(layout), dstW, dstH, len(boxes), _roi_array(boxes),
-                                            nFrames, frameW, frameH, ctypes.byref(st), ctypes.byref(bad))
-    _check_rois(rc, bad, boxes, "host_roi_yuv_arena_stats")
-    return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
-            "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
+    return _host_arena_stats("host_roi_yuv_arena_stats", method, degree, _roi_layout(layout), dstW, dstH, boxes, nFrames,
+                             frameW, frameH)
 
 
 def host_roi_yuv_box_layout(method, degree, layout, dstW, dstH, w, h):
@@ -713,10 +709,7 @@ def host_roi_yuv_box_layout(method, degree, layout, dstW, dstH, w, h):
     m = _METHODS[method] if isinstance(method, str) else int(method)
     bl = RoiYuvBoxLayout()
     rc = lib().iqo_host_roi_yuv_box_layout(m, degree, _roi_layout(layout), dstW, dstH, w, h, ctypes.byref(bl))
-    if rc != 0:
-        err = IqoError("host_roi_yuv_box_layout: %s (%d) (box %d x %d)" % (lib().iqo_hip_strerror(rc).decode(), rc, w, h))
-        err.status, err.bad_roi = rc, -1  # IQO_HIP_E*; the call names no box index
-        raise err
+    _check_rois(rc, ctypes.c_int(-1), (), "host_roi_yuv_box_layout", " (box %d x %d)" % (w, h))
     return {"rows": bl.rows, "workgroups": bl.workgroups, "lds_bytes": bl.ldsBytes, "nYp": bl.nYp, "NP": bl.np,
             "pitchDw": bl.pitchDw, "nYpC": bl.nYpC, "NPC": bl.npC, "pitchDwC": bl.pitchDwC}
 
@@ -1089,25 +1082,73 @@ def make_resizer(method, degree, srcW, srcH, dstW, dstH, pxScale=1, device=None,
     raise ValueError(method)
 
 
-class RoiResizer:
+def _out_code(dtype):
+    """(dtype, IQO_OUT_*) of a torch float dtype; None: float32."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+    if dtype not in codes:
+        raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    return dtype, codes[dtype]
+
+
+def _roi_out_u8(shape, C, s, out):
+    """`out`, or a new tensor on s's device: uint8 [N, dstH, dstW(, C)]."""
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=s.device)
+    N, dstH, dstW = shape[:3]
+    if (out.dtype != torch.uint8 or out.device != s.device or tuple(out.shape) != shape or out.stride(2) != C
+            or (out.dim() == 4 and out.stride(3) != 1) or out.stride(1) < dstW * C
+            or (N > 1 and out.stride(0) < dstH * out.stride(1))):
+        raise IqoError("out must be a uint8 tensor %s on %s with contiguous pixels and non-overlapping rows and "
+                       "outputs" % (shape, s.device))
+    return out
+
+
+def _roi_out_norm(shape, dtype, s, out):
+    """`out`, or a new tensor on s's device: `dtype` [N, planes, dstH, dstW]."""
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=s.device)
+    N, planes, dstH, dstW = shape
+    if (out.dtype != dtype or out.device != s.device or tuple(out.shape) != shape or out.stride(3) != 1
+            or out.stride(2) < dstW or out.stride(1) < dstH * out.stride(2)
+            or (N > 1 and out.stride(0) < planes * out.stride(1))):
+        raise IqoError("out must be a %s tensor %s on %s with unit column stride and non-overlapping rows, planes "
+                       "and outputs" % (dtype, shape, s.device))
+    return out
+
+
+class _RoiPlan:
+    """The plan handle of RoiResizer and YuvRoiResizer, released by the entry a class names in _destroy."""
+
+    def __init__(self, method, degree, dstW, dstH, device):
+        self.method = _METHODS[method] if isinstance(method, str) else int(method)
+        self.degree, self.dstW, self.dstH = int(degree), int(dstW), int(dstH)
+        self.device = 0 if device is None else int(device)
+        self._plan = _vp()
+
+    def __del__(self):
+        p = getattr(self, "_plan", None)
+        if p and _lib is not None:
+            getattr(_lib, self._destroy)(p)
+            self._plan = _vp()
+
+
+class RoiResizer(_RoiPlan):
     """Crop-and-resize a batch of boxes of device-resident frames to one dstW x dstH in one launch
     (iqo_hip_plan_rois).  method: "lanczos" / "area" / "linear" (or 0 / 1 / 2); channels 1, 3 or 4.  Every output is
     bit for bit the {Lanczos,Area,Linear}Resizer result on the cropped image.  Calls are asynchronous on the stream;
     one call at a time per object (not thread-safe); not capturable into a graph."""
 
+    _destroy = "iqo_hip_roi_plan_destroy"
+
     def __init__(self, method, degree, dstW, dstH, channels=1, device=None):
-        self.method = _METHODS[method] if isinstance(method, str) else int(method)
-        self.degree, self.dstW, self.dstH, self.channels = int(degree), int(dstW), int(dstH), int(channels)
-        self.device = 0 if device is None else int(device)
-        self._plan = _vp()
+        _RoiPlan.__init__(self, method, degree, dstW, dstH, device)
+        self.channels = int(channels)
         _check(lib().iqo_hip_plan_rois(self.method, self.degree, self.channels, self.dstW, self.dstH, self.device,
                                        ctypes.byref(self._plan)), "RoiResizer")
-
-    def __del__(self):
-        p = getattr(self, "_plan", None)
-        if p and _lib is not None:
-            _lib.iqo_hip_roi_plan_destroy(p)
-            self._plan = _vp()
 
     def _source(self, src):
         """src [F, H, W] (channels 1) or [F, H, W, C] uint8 on the device, read where it lies when the pixel bytes
@@ -1130,14 +1171,7 @@ class RoiResizer:
         s = self._source(src)
         C, boxes = self.channels, [tuple(b) for b in boxes]
         N = len(boxes)
-        shape = (N, self.dstH, self.dstW) if s.dim() == 3 else (N, self.dstH, self.dstW, C)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=s.device)
-        if (out.dtype != torch.uint8 or out.device != s.device or tuple(out.shape) != shape or out.stride(2) != C
-                or (out.dim() == 4 and out.stride(3) != 1) or out.stride(1) < self.dstW * C
-                or (N > 1 and out.stride(0) < self.dstH * out.stride(1))):
-            raise IqoError("out must be a uint8 tensor %s on %s with contiguous pixels and non-overlapping rows and "
-                           "outputs" % (shape, s.device))
+        out = _roi_out_u8((N, self.dstH, self.dstW) if s.dim() == 3 else (N, self.dstH, self.dstW, C), C, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
         bad = ctypes.c_int(-1)
@@ -1154,23 +1188,12 @@ class RoiResizer:
         (channels 1: order (0, 0, 0) gives grey -> 3 planes).  `out` may be a strided view with unit column stride
         and non-overlapping rows, planes and outputs."""
         import torch
-        if dtype is None:
-            dtype = torch.float32
-        codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
-        if dtype not in codes:
-            raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        dtype, code = _out_code(dtype)
         s = self._source(src)
         boxes = [tuple(b) for b in boxes]
         N = len(boxes)
-        n, planes = _norm_of(self.channels, scale, bias, order, codes[dtype])
-        shape = (N, planes, self.dstH, self.dstW)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=s.device)
-        if (out.dtype != dtype or out.device != s.device or tuple(out.shape) != shape or out.stride(3) != 1
-                or out.stride(2) < self.dstW or out.stride(1) < self.dstH * out.stride(2)
-                or (N > 1 and out.stride(0) < planes * out.stride(1))):
-            raise IqoError("out must be a %s tensor %s on %s with unit column stride and non-overlapping rows, planes "
-                           "and outputs" % (dtype, shape, s.device))
+        n, planes = _norm_of(self.channels, scale, bias, order, code)
+        out = _roi_out_norm((N, planes, self.dstH, self.dstW), dtype, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
         e, bad = out.element_size(), ctypes.c_int(-1)
@@ -1182,26 +1205,20 @@ class RoiResizer:
         return out
 
 
-class YuvRoiResizer:
+class YuvRoiResizer(_RoiPlan):
     """Crop-and-resize a batch of boxes of device-resident NV12 / I420 frames to one dstW x dstH, straight to RGB
     bytes or normalised tensors, in one launch (iqo_hip_plan_rois_yuv).  Box coordinates and sizes are even.  Every
     output is bit for bit what Nv12Resizer / Yuv420Resizer(method, degree, w, h, dstW, dstH, chroma="full") gives on
     the cropped frame.  Calls are asynchronous on the stream; one call at a time per object (not thread-safe); not
     capturable into a graph."""
 
+    _destroy = "iqo_hip_roi_yuv_plan_destroy"
+
     def __init__(self, method, degree, dstW, dstH, layout="nv12", device=None):
-        self.method = _METHODS[method] if isinstance(method, str) else int(method)
-        self.degree, self.dstW, self.dstH, self.layout = int(degree), int(dstW), int(dstH), layout
-        self.device = 0 if device is None else int(device)
-        self._plan = _vp()
+        _RoiPlan.__init__(self, method, degree, dstW, dstH, device)
+        self.layout = layout
         _check(lib().iqo_hip_plan_rois_yuv(self.method, self.degree, _roi_layout(layout), self.dstW, self.dstH,
                                            self.device, ctypes.byref(self._plan)), "YuvRoiResizer")
-
-    def __del__(self):
-        p = getattr(self, "_plan", None)
-        if p and _lib is not None:
-            _lib.iqo_hip_roi_yuv_plan_destroy(p)
-            self._plan = _vp()
 
     def _source(self, src, frameW, frameH):
         """(nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, Y, U or UV, V) of the tight frame tensor."""
@@ -1238,14 +1255,7 @@ class YuvRoiResizer:
         C, _ = _rgb_order(order)
         boxes = [tuple(b) for b in boxes]
         N = len(boxes)
-        shape = (N, self.dstH, self.dstW, C)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=s.device)
-        if (out.dtype != torch.uint8 or out.device != s.device or tuple(out.shape) != shape or out.stride(2) != C
-                or out.stride(3) != 1 or out.stride(1) < self.dstW * C
-                or (N > 1 and out.stride(0) < self.dstH * out.stride(1))):
-            raise IqoError("out must be a uint8 tensor %s on %s with contiguous pixels and non-overlapping rows and "
-                           "outputs" % (shape, s.device))
+        out = _roi_out_u8((N, self.dstH, self.dstW, C), C, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
         self.resize_rois_rgb_device(boxes, *args, out.stride(1), out.stride(0), out, standard, order, stream)
@@ -1258,23 +1268,12 @@ class YuvRoiResizer:
         operation rounded to float32, then rounded to `dtype`.  `out` may be a strided view with unit column stride
         and non-overlapping rows, planes and outputs."""
         import torch
-        if dtype is None:
-            dtype = torch.float32
-        codes = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
-        if dtype not in codes:
-            raise IqoError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        dtype, code = _out_code(dtype)
         s, args = self._source(src, frameW, frameH)
         boxes = [tuple(b) for b in boxes]
         N = len(boxes)
-        n, planes = _norm_of(3, scale, bias, order, codes[dtype])
-        shape = (N, planes, self.dstH, self.dstW)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=s.device)
-        if (out.dtype != dtype or out.device != s.device or tuple(out.shape) != shape or out.stride(3) != 1
-                or out.stride(2) < self.dstW or out.stride(1) < self.dstH * out.stride(2)
-                or (N > 1 and out.stride(0) < planes * out.stride(1))):
-            raise IqoError("out must be a %s tensor %s on %s with unit column stride and non-overlapping rows, planes "
-                           "and outputs" % (dtype, shape, s.device))
+        n, planes = _norm_of(3, scale, bias, order, code)
+        out = _roi_out_norm((N, planes, self.dstH, self.dstW), dtype, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
         e, bad = out.element_size(), ctypes.c_int(-1)

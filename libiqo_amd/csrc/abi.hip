@@ -3614,16 +3614,16 @@ int iqo_host_yuv420_fused(int method, unsigned degree, size_t srcW, size_t srcH,
 
 // ---------------------------------------------------------------- batched crop-and-resize (roi.hpp)
 
-// Two arenas per plan, used alternately: pinned host words, their device copy and the event recorded
-// after the launch that reads the device copy.
-struct iqo_hip_roi_plan {
-    iqo_hip_roi_plan(iqo_amd::Method m, unsigned degree, int channels_, int dstW, int dstH, int device_)
-        : cache(m, degree, dstW, dstH), channels(channels_), device(device_)
+// What a plan of either box family holds.  Two arenas, used alternately: pinned host words, their device copy
+// and the event recorded after the launch that reads the device copy.
+struct RoiPlanCore {
+    RoiPlanCore(int method, unsigned degree, size_t dstW, size_t dstH, int device_)
+        : cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH)), device(device_)
     {
     }
     iqo_amd::RoiTableCache cache;
     iqo_amd::RoiLayout layout;
-    int channels, device;
+    int device;
     struct Arena {
         uint32_t *h = nullptr, *d = nullptr;
         size_t capWords = 0;
@@ -3632,21 +3632,42 @@ struct iqo_hip_roi_plan {
     } arena[2];
     int next = 0;
 };
+struct iqo_hip_roi_plan {
+    RoiPlanCore core;
+    int channels;
+};
+struct iqo_hip_roi_yuv_plan {
+    RoiPlanCore core;
+    int layout;
+};
 
 namespace {
 
 static_assert(sizeof(iqo_hip_roi) == sizeof(iqo_amd::RoiBox), "iqo_hip_roi is roi.hpp RoiBox");
 static_assert(IQO_HIP_ROI_MAX_TAPS == iqo_amd::kRoiMaxTaps && IQO_HIP_ROI_LDS_BYTES == iqo_amd::kRoiLdsMax,
               "iqo_hip.h roi limits are roi.hpp's");
+static_assert(IQO_ROI_NV12 == iqo_amd::kRoiNv12 && IQO_ROI_I420 == iqo_amd::kRoiI420, "iqo_hip.h layouts are roi.hpp's");
 
 int roi_status(int st) { return st == iqo_amd::kRoiOk ? IQO_HIP_OK : st == iqo_amd::kRoiInvalid ? IQO_HIP_EINVAL : IQO_HIP_EUNSUP; }
+
+// A layout call that failed at box `bad`
+int roi_fail(int st, int bad, int *badRoi)
+{
+    if (badRoi)
+        *badRoi = bad;
+    return roi_status(st);
+}
+
+bool roi_dst_dims_ok(size_t dstW, size_t dstH) { return dstW && dstH && dstW <= (1u << 20) && dstH <= (1u << 20); }
+
+const iqo_amd::RoiBox *roi_boxes(const iqo_hip_roi *rois) { return reinterpret_cast<const iqo_amd::RoiBox *>(rois); }
 
 // The destination checks of both forms (norm == nullptr: interleaved bytes); fills *rn for the twin.
 int roi_check_dst(int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_norm *norm, bool isNorm,
                   size_t dstSt, size_t planeSt, size_t dstRoiSt, const void *dst, iqo_amd::RoiNorm *rn)
 {
     *rn = iqo_amd::RoiNorm();
-    if ((!dst && nRois) || !dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20))
+    if ((!dst && nRois) || !roi_dst_dims_ok(dstW, dstH))
         return IQO_HIP_EINVAL;
     if (!isNorm) {
         if (dstSt < dstW * static_cast<size_t>(channels) || (nRois > 1 && dstRoiSt / dstH < dstSt))
@@ -3676,53 +3697,31 @@ int roi_check_dst(int channels, size_t dstW, size_t dstH, size_t nRois, const iq
     return IQO_HIP_OK;
 }
 
-int host_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_roi *rois,
-              size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
-              const iqo_hip_norm *norm, bool isNorm, size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst,
-              iqo_hip_roi_arena_stats *stats, int *badRoi)
+iqo_amd::NormDev norm_dev(const iqo_amd::RoiNorm &rn, size_t planeSt)
 {
-    int bad = -1;
-    if (badRoi)
-        *badRoi = -1;
-    if (method < 0 || method > 2)
-        return IQO_HIP_EINVAL;
-    if (channels != 1 && channels != 3 && channels != 4)
-        return IQO_HIP_EUNSUP;
-    iqo_amd::RoiNorm rn;
-    if (!stats) {
-        if (!src && nRois)
-            return IQO_HIP_EINVAL;
-        const int rc = roi_check_dst(channels, dstW, dstH, nRois, norm, isNorm, dstSt, planeSt, dstRoiSt, dst, &rn);
-        if (rc)
-            return rc;
-    } else if (!dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20)) {
-        return IQO_HIP_EINVAL;
+    iqo_amd::NormDev n;
+    n.dtype = rn.dtype;
+    n.planes = rn.planes;
+    n.planeSt = static_cast<int>(planeSt);
+    for (int i = 0; i < 4; ++i) {
+        n.order[i] = rn.order[i];
+        n.scale[i] = rn.scale[i];
+        n.bias[i] = rn.bias[i];
     }
-    iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
-    iqo_amd::RoiLayout l;
-    const int st = iqo_amd::roi_layout(&cache, channels, nRois, reinterpret_cast<const iqo_amd::RoiBox *>(rois), nFrames,
-                                       frameW, frameH, srcSt, srcFrameSt, &l, &bad);
-    if (st != iqo_amd::kRoiOk) {
-        if (badRoi)
-            *badRoi = bad;
-        return roi_status(st);
-    }
-    if (stats) {
-        stats->arenaBytes = l.words * 4;
-        stats->xTables = l.nXTables;
-        stats->yTables = l.nYTables;
-        stats->workgroups = l.groups;
-        stats->ldsBytes = l.ldsBytes;
-        stats->recordBytes = iqo_amd::kRoiRecWords * 4;
-        return IQO_HIP_OK;
-    }
-    std::vector<uint32_t> arena(l.words);
-    iqo_amd::roi_fill(cache, l, frameW, arena.data());
-    iqo_amd::roi_walk(arena.data(), src, srcSt, dstSt, planeSt, dstRoiSt, dst, rn);
-    return IQO_HIP_OK;
+    return n;
 }
 
-void roi_arena_free(iqo_hip_roi_plan::Arena *a)
+void roi_stats(const iqo_amd::RoiLayout &l, int recWords, iqo_hip_roi_arena_stats *stats)
+{
+    stats->arenaBytes = l.words * 4;
+    stats->xTables = l.nXTables;
+    stats->yTables = l.nYTables;
+    stats->workgroups = l.groups;
+    stats->ldsBytes = l.ldsBytes;
+    stats->recordBytes = static_cast<size_t>(recWords) * 4;
+}
+
+void roi_arena_free(RoiPlanCore::Arena *a)
 {
     if (a->h)
         (void)hipHostFree(a->h);
@@ -3733,7 +3732,7 @@ void roi_arena_free(iqo_hip_roi_plan::Arena *a)
 }
 
 // Makes `a` ready to be filled with `words` words: waits for the launch that last read it, and grows it.
-int roi_arena_reserve(iqo_hip_roi_plan::Arena *a, size_t words)
+int roi_arena_reserve(RoiPlanCore::Arena *a, size_t words)
 {
     if (a->pending) {
         if (hipEventSynchronize(a->ev) != hipSuccess)
@@ -3753,117 +3752,14 @@ int roi_arena_reserve(iqo_hip_roi_plan::Arena *a, size_t words)
     return IQO_HIP_OK;
 }
 
-int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
-             size_t srcSt, size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, bool isNorm, size_t dstSt,
-             size_t planeSt, size_t dstRoiSt, void *dst, hipStream_t s, int *badRoi)
-{
-    if (badRoi)
-        *badRoi = -1;
-    if (!h || (!src && nRois))
-        return IQO_HIP_EINVAL;
-    iqo_amd::RoiNorm rn;
-    const int rc = roi_check_dst(h->channels, static_cast<size_t>(h->cache.dstW()), static_cast<size_t>(h->cache.dstH()),
-                                 nRois, norm, isNorm, dstSt, planeSt, dstRoiSt, dst, &rn);
-    if (rc)
-        return rc;
-    int bad = -1;
-    const int st = iqo_amd::roi_layout(&h->cache, h->channels, nRois, reinterpret_cast<const iqo_amd::RoiBox *>(rois),
-                                       nFrames, frameW, frameH, srcSt, srcFrameSt, &h->layout, &bad);
-    if (st != iqo_amd::kRoiOk) {
-        if (badRoi)
-            *badRoi = bad;
-        return roi_status(st);
-    }
-    const iqo_amd::RoiLayout &l = h->layout;
-    if (nRois == 0)
-        return IQO_HIP_OK;
-    DeviceGuard guard(h->device);
-    if (!guard.ok())
-        return IQO_HIP_ENODEV;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess)
-        return IQO_HIP_EHIP;
-    if (cap != hipStreamCaptureStatusNone)
-        return IQO_HIP_EUNSUP;  // the tables are per call: nothing to replay
-    iqo_hip_roi_plan::Arena &a = h->arena[h->next];
-    const int ra = roi_arena_reserve(&a, l.words);
-    if (ra)
-        return ra;
-    iqo_amd::roi_fill(h->cache, l, frameW, a.h);
-    if (hipMemcpyAsync(a.d, a.h, l.words * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return IQO_HIP_EHIP;
-    a.pending = true;  // from here on the arena is in flight, whatever follows
-    iqo_amd::RoiDev d;
-    d.arena = a.d;
-    d.src = src;
-    d.dst = static_cast<uint8_t *>(dst);
-    d.srcSt = static_cast<int64_t>(srcSt);
-    d.dstSt = static_cast<int64_t>(dstSt);
-    d.dstRoiSt = static_cast<int64_t>(dstRoiSt);
-    d.lanczos = h->cache.method() == iqo_amd::kLanczos;
-    d.channels = h->channels;
-    d.groups = l.groups;
-    d.ldsBytes = l.ldsBytes;
-    iqo_amd::NormDev n;
-    if (isNorm) {
-        n.dtype = rn.dtype;
-        n.planes = rn.planes;
-        n.planeSt = static_cast<int>(planeSt);
-        for (int i = 0; i < 4; ++i) {
-            n.order[i] = rn.order[i];
-            n.scale[i] = rn.scale[i];
-            n.bias[i] = rn.bias[i];
-        }
-    }
-    const hipError_t e = iqo_amd::launch_roi(d, isNorm ? &n : nullptr, s);
-    const hipError_t e2 = hipEventRecord(a.ev, s);
-    h->next ^= 1;
-    if (e == hipErrorInvalidValue)
-        return IQO_HIP_EINVAL;
-    return e == hipSuccess && e2 == hipSuccess ? IQO_HIP_OK : IQO_HIP_EHIP;
-}
-
-} // namespace
-
-extern "C" {
-
-int iqo_hip_plan_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, int device,
-                      iqo_hip_roi_plan **out)
-{
-    if (!out)
-        return IQO_HIP_EINVAL;
-    *out = nullptr;
-    if (method < 0 || method > 2 || (method == IQO_METHOD_LANCZOS && degree < 1) || !dstW || !dstH ||
-        dstW > (1u << 20) || dstH > (1u << 20))
-        return IQO_HIP_EINVAL;
-    if (channels != 1 && channels != 3 && channels != 4)
-        return IQO_HIP_EUNSUP;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || !is_gfx950(device))
-        return IQO_HIP_ENODEV;
-    DeviceGuard guard(device);
-    if (!guard.ok())
-        return IQO_HIP_ENODEV;
-    iqo_hip_roi_plan *h = new (std::nothrow) iqo_hip_roi_plan(static_cast<iqo_amd::Method>(method), degree, channels,
-                                                              static_cast<int>(dstW), static_cast<int>(dstH), device);
-    if (!h)
-        return IQO_HIP_ENOMEM;
-    for (auto &a : h->arena)
-        if (hipEventCreateWithFlags(&a.ev, hipEventDisableTiming) != hipSuccess) {
-            iqo_hip_roi_plan_destroy(h);
-            return IQO_HIP_EHIP;
-        }
-    *out = h;
-    return IQO_HIP_OK;
-}
-
-void iqo_hip_roi_plan_destroy(iqo_hip_roi_plan *h)
+template <typename Plan>
+void roi_plan_destroy(Plan *h)
 {
     if (!h)
         return;
     {
-        DeviceGuard guard(h->device);
-        for (auto &a : h->arena) {
+        DeviceGuard guard(h->core.device);
+        for (auto &a : h->core.arena) {
             if (a.pending)
                 (void)hipEventSynchronize(a.ev);
             if (a.ev)
@@ -3873,6 +3769,158 @@ void iqo_hip_roi_plan_destroy(iqo_hip_roi_plan *h)
     }
     delete h;
 }
+
+// A plan of either family; `variant` (channels / layout) was found to be `variantStatus` by the caller.
+template <typename Plan>
+int roi_plan_create(int method, unsigned degree, int variant, int variantStatus, size_t dstW, size_t dstH, int device,
+                    Plan **out)
+{
+    if (!out)
+        return IQO_HIP_EINVAL;
+    *out = nullptr;
+    if (method < 0 || method > 2 || (method == IQO_METHOD_LANCZOS && degree < 1) || !roi_dst_dims_ok(dstW, dstH))
+        return IQO_HIP_EINVAL;
+    if (variantStatus)
+        return variantStatus;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || !is_gfx950(device))
+        return IQO_HIP_ENODEV;
+    DeviceGuard guard(device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    Plan *h = new (std::nothrow) Plan{RoiPlanCore(method, degree, dstW, dstH, device), variant};
+    if (!h)
+        return IQO_HIP_ENOMEM;
+    for (auto &a : h->core.arena)
+        if (hipEventCreateWithFlags(&a.ev, hipEventDisableTiming) != hipSuccess) {
+            roi_plan_destroy(h);
+            return IQO_HIP_EHIP;
+        }
+    *out = h;
+    return IQO_HIP_OK;
+}
+
+// The laid-out call of p->layout on stream s: fill(host words) writes the arena, launch(device words) starts the
+// kernel on its copy.
+template <typename Fill, typename Launch>
+int roi_submit(RoiPlanCore *p, Fill fill, Launch launch, hipStream_t s)
+{
+    const size_t words = p->layout.words;
+    DeviceGuard guard(p->device);
+    if (!guard.ok())
+        return IQO_HIP_ENODEV;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess)
+        return IQO_HIP_EHIP;
+    if (cap != hipStreamCaptureStatusNone)
+        return IQO_HIP_EUNSUP;  // the tables are per call: nothing to replay
+    RoiPlanCore::Arena &a = p->arena[p->next];
+    const int ra = roi_arena_reserve(&a, words);
+    if (ra)
+        return ra;
+    fill(a.h);
+    if (hipMemcpyAsync(a.d, a.h, words * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return IQO_HIP_EHIP;
+    a.pending = true;  // from here on the arena is in flight, whatever follows
+    const hipError_t e = launch(a.d);
+    const hipError_t e2 = hipEventRecord(a.ev, s);
+    p->next ^= 1;
+    if (e == hipErrorInvalidValue)
+        return IQO_HIP_EINVAL;
+    return e == hipSuccess && e2 == hipSuccess ? IQO_HIP_OK : IQO_HIP_EHIP;
+}
+
+int host_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_roi *rois,
+              size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
+              const iqo_hip_norm *norm, bool isNorm, size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst,
+              iqo_hip_roi_arena_stats *stats, int *badRoi)
+{
+    int bad = -1;
+    if (badRoi)
+        *badRoi = -1;
+    if (method < 0 || method > 2)
+        return IQO_HIP_EINVAL;
+    if (channels != 1 && channels != 3 && channels != 4)
+        return IQO_HIP_EUNSUP;
+    iqo_amd::RoiNorm rn;
+    if (!stats) {
+        if (!src && nRois)
+            return IQO_HIP_EINVAL;
+        const int rc = roi_check_dst(channels, dstW, dstH, nRois, norm, isNorm, dstSt, planeSt, dstRoiSt, dst, &rn);
+        if (rc)
+            return rc;
+    } else if (!roi_dst_dims_ok(dstW, dstH)) {
+        return IQO_HIP_EINVAL;
+    }
+    iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
+    iqo_amd::RoiLayout l;
+    const int st = iqo_amd::roi_layout(&cache, channels, nRois, roi_boxes(rois), nFrames, frameW, frameH, srcSt, srcFrameSt,
+                                       &l, &bad);
+    if (st != iqo_amd::kRoiOk)
+        return roi_fail(st, bad, badRoi);
+    if (stats) {
+        roi_stats(l, iqo_amd::kRoiRecWords, stats);
+        return IQO_HIP_OK;
+    }
+    std::vector<uint32_t> arena(l.words);
+    iqo_amd::roi_fill(cache, l, frameW, arena.data());
+    iqo_amd::roi_walk(arena.data(), src, srcSt, dstSt, planeSt, dstRoiSt, dst, rn);
+    return IQO_HIP_OK;
+}
+
+int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+             size_t srcSt, size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, bool isNorm, size_t dstSt,
+             size_t planeSt, size_t dstRoiSt, void *dst, hipStream_t s, int *badRoi)
+{
+    if (badRoi)
+        *badRoi = -1;
+    if (!h || (!src && nRois))
+        return IQO_HIP_EINVAL;
+    RoiPlanCore &p = h->core;
+    iqo_amd::RoiNorm rn;
+    const int rc = roi_check_dst(h->channels, static_cast<size_t>(p.cache.dstW()), static_cast<size_t>(p.cache.dstH()), nRois,
+                                 norm, isNorm, dstSt, planeSt, dstRoiSt, dst, &rn);
+    if (rc)
+        return rc;
+    int bad = -1;
+    const int st = iqo_amd::roi_layout(&p.cache, h->channels, nRois, roi_boxes(rois), nFrames, frameW, frameH, srcSt,
+                                       srcFrameSt, &p.layout, &bad);
+    if (st != iqo_amd::kRoiOk)
+        return roi_fail(st, bad, badRoi);
+    if (nRois == 0)
+        return IQO_HIP_OK;
+    return roi_submit(
+        &p, [&](uint32_t *words) { iqo_amd::roi_fill(p.cache, p.layout, frameW, words); },
+        [&](const uint32_t *words) {
+            iqo_amd::RoiDev d;
+            d.arena = words;
+            d.src = src;
+            d.dst = static_cast<uint8_t *>(dst);
+            d.srcSt = static_cast<int64_t>(srcSt);
+            d.dstSt = static_cast<int64_t>(dstSt);
+            d.dstRoiSt = static_cast<int64_t>(dstRoiSt);
+            d.lanczos = p.cache.method() == iqo_amd::kLanczos;
+            d.channels = h->channels;
+            d.groups = p.layout.groups;
+            d.ldsBytes = p.layout.ldsBytes;
+            const iqo_amd::NormDev n = norm_dev(rn, planeSt);
+            return iqo_amd::launch_roi(d, isNorm ? &n : nullptr, s);
+        },
+        s);
+}
+
+} // namespace
+
+extern "C" {
+
+int iqo_hip_plan_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, int device,
+                      iqo_hip_roi_plan **out)
+{
+    const bool ok = channels == 1 || channels == 3 || channels == 4;
+    return roi_plan_create(method, degree, channels, ok ? IQO_HIP_OK : IQO_HIP_EUNSUP, dstW, dstH, device, out);
+}
+
+void iqo_hip_roi_plan_destroy(iqo_hip_roi_plan *h) { roi_plan_destroy(h); }
 
 int iqo_hip_resize_rois_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
                                size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrc,
@@ -3922,8 +3970,7 @@ int iqo_host_roi_arena_stats(int method, unsigned degree, int channels, size_t d
 int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
                             iqo_hip_roi_box_layout *out)
 {
-    if (!out || method < 0 || method > 2 || !dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20) || !w || !h ||
-        w > (1u << 24) || h > (1u << 24))
+    if (!out || method < 0 || method > 2 || !roi_dst_dims_ok(dstW, dstH) || !w || !h || w > (1u << 24) || h > (1u << 24))
         return IQO_HIP_EINVAL;
     // the box as the whole of one tightly packed frame: roi_layout on a one-box call, as the device call
     const size_t C = channels > 0 ? static_cast<size_t>(channels) : 1;
@@ -3949,22 +3996,7 @@ int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t ds
 
 // ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB (roi.hpp)
 
-// As iqo_hip_roi_plan, over the YUV arena.
-struct iqo_hip_roi_yuv_plan {
-    iqo_hip_roi_yuv_plan(iqo_amd::Method m, unsigned degree, int layout_, int dstW, int dstH, int device_)
-        : cache(m, degree, dstW, dstH), layout(layout_), device(device_)
-    {
-    }
-    iqo_amd::RoiTableCache cache;
-    iqo_amd::RoiLayout boxes;
-    int layout, device;
-    iqo_hip_roi_plan::Arena arena[2];
-    int next = 0;
-};
-
 namespace {
-
-static_assert(IQO_ROI_NV12 == iqo_amd::kRoiNv12 && IQO_ROI_I420 == iqo_amd::kRoiI420, "iqo_hip.h layouts are roi.hpp's");
 
 // The source and the output of a YUV box call, as the C entries take them.
 struct RoiYuvCall {
@@ -4007,7 +4039,7 @@ int roi_yuv_check(int layout, size_t dstW, size_t dstH, const RoiYuvCall &c, boo
                                      c.dstRoiSt, c.dst, &out->n);
         if (rc)
             return rc;
-    } else if (!dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20)) {
+    } else if (!roi_dst_dims_ok(dstW, dstH)) {
         return IQO_HIP_EINVAL;
     }
     src->layout = layout;
@@ -4035,19 +4067,11 @@ int host_rois_yuv(int method, unsigned degree, int layout, size_t dstW, size_t d
         return rc;
     iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
     iqo_amd::RoiLayout l;
-    const int st = iqo_amd::roi_yuv_layout(&cache, src, c.nRois, reinterpret_cast<const iqo_amd::RoiBox *>(c.rois), &l, &bad);
-    if (st != iqo_amd::kRoiOk) {
-        if (badRoi)
-            *badRoi = bad;
-        return roi_status(st);
-    }
+    const int st = iqo_amd::roi_yuv_layout(&cache, src, c.nRois, roi_boxes(c.rois), &l, &bad);
+    if (st != iqo_amd::kRoiOk)
+        return roi_fail(st, bad, badRoi);
     if (stats) {
-        stats->arenaBytes = l.words * 4;
-        stats->xTables = l.nXTables;
-        stats->yTables = l.nYTables;
-        stats->workgroups = l.groups;
-        stats->ldsBytes = l.ldsBytes;
-        stats->recordBytes = iqo_amd::kRoiYuvRecWords * 4;
+        roi_stats(l, iqo_amd::kRoiYuvRecWords, stats);
         return IQO_HIP_OK;
     }
     std::vector<uint32_t> arena(l.words);
@@ -4062,69 +4086,42 @@ int run_rois_yuv(iqo_hip_roi_yuv_plan *h, const RoiYuvCall &c, hipStream_t s, in
         *badRoi = -1;
     if (!h)
         return IQO_HIP_EINVAL;
+    RoiPlanCore &p = h->core;
     iqo_amd::RoiYuvSrc src;
     iqo_amd::RoiYuvOut out;
-    const int rc = roi_yuv_check(h->layout, static_cast<size_t>(h->cache.dstW()), static_cast<size_t>(h->cache.dstH()), c,
-                                 true, &src, &out);
+    const int rc = roi_yuv_check(h->layout, static_cast<size_t>(p.cache.dstW()), static_cast<size_t>(p.cache.dstH()), c, true,
+                                 &src, &out);
     if (rc)
         return rc;
     int bad = -1;
-    const int st = iqo_amd::roi_yuv_layout(&h->cache, src, c.nRois, reinterpret_cast<const iqo_amd::RoiBox *>(c.rois),
-                                           &h->boxes, &bad);
-    if (st != iqo_amd::kRoiOk) {
-        if (badRoi)
-            *badRoi = bad;
-        return roi_status(st);
-    }
-    const iqo_amd::RoiLayout &l = h->boxes;
+    const int st = iqo_amd::roi_yuv_layout(&p.cache, src, c.nRois, roi_boxes(c.rois), &p.layout, &bad);
+    if (st != iqo_amd::kRoiOk)
+        return roi_fail(st, bad, badRoi);
     if (c.nRois == 0)
         return IQO_HIP_OK;
-    DeviceGuard guard(h->device);
-    if (!guard.ok())
-        return IQO_HIP_ENODEV;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess)
-        return IQO_HIP_EHIP;
-    if (cap != hipStreamCaptureStatusNone)
-        return IQO_HIP_EUNSUP;  // the tables are per call: nothing to replay
-    iqo_hip_roi_plan::Arena &a = h->arena[h->next];
-    const int ra = roi_arena_reserve(&a, l.words);
-    if (ra)
-        return ra;
-    iqo_amd::roi_yuv_fill(h->cache, l, src, a.h);
-    if (hipMemcpyAsync(a.d, a.h, l.words * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return IQO_HIP_EHIP;
-    a.pending = true;  // from here on the arena is in flight, whatever follows
-    iqo_amd::RoiYuvDev d;
-    d.arena = a.d;
-    d.y = c.y;
-    d.u = c.u;
-    d.v = c.v;
-    d.dst = static_cast<uint8_t *>(c.dst);
-    d.dstSt = static_cast<int64_t>(c.dstSt);
-    d.dstRoiSt = static_cast<int64_t>(c.dstRoiSt);
-    d.lanczos = h->cache.method() == iqo_amd::kLanczos;
-    d.interleavedUV = h->layout == IQO_ROI_NV12;
-    d.k = iqo_amd::kYuvRgb[c.standard];
-    d.channels = out.channels;
-    d.groups = l.groups;
-    d.ldsBytes = l.ldsBytes;
-    iqo_amd::NormDev n;
-    n.dtype = out.n.dtype;
-    n.planes = out.n.planes;
-    n.planeSt = static_cast<int>(c.planeSt);
-    for (int i = 0; i < 4; ++i) {
-        d.order[i] = out.order[i];
-        n.order[i] = out.n.order[i];
-        n.scale[i] = out.n.scale[i];
-        n.bias[i] = out.n.bias[i];
-    }
-    const hipError_t e = iqo_amd::launch_roi_yuv(d, c.isNorm ? &n : nullptr, s);
-    const hipError_t e2 = hipEventRecord(a.ev, s);
-    h->next ^= 1;
-    if (e == hipErrorInvalidValue)
-        return IQO_HIP_EINVAL;
-    return e == hipSuccess && e2 == hipSuccess ? IQO_HIP_OK : IQO_HIP_EHIP;
+    return roi_submit(
+        &p, [&](uint32_t *words) { iqo_amd::roi_yuv_fill(p.cache, p.layout, src, words); },
+        [&](const uint32_t *words) {
+            iqo_amd::RoiYuvDev d;
+            d.arena = words;
+            d.y = c.y;
+            d.u = c.u;
+            d.v = c.v;
+            d.dst = static_cast<uint8_t *>(c.dst);
+            d.dstSt = static_cast<int64_t>(c.dstSt);
+            d.dstRoiSt = static_cast<int64_t>(c.dstRoiSt);
+            d.lanczos = p.cache.method() == iqo_amd::kLanczos;
+            d.interleavedUV = h->layout == IQO_ROI_NV12;
+            d.k = iqo_amd::kYuvRgb[c.standard];
+            d.channels = out.channels;
+            for (int i = 0; i < 4; ++i)
+                d.order[i] = out.order[i];
+            d.groups = p.layout.groups;
+            d.ldsBytes = p.layout.ldsBytes;
+            const iqo_amd::NormDev n = norm_dev(out.n, c.planeSt);
+            return iqo_amd::launch_roi_yuv(d, c.isNorm ? &n : nullptr, s);
+        },
+        s);
 }
 
 } // namespace
@@ -4134,47 +4131,11 @@ extern "C" {
 int iqo_hip_plan_rois_yuv(int method, unsigned degree, int layout, size_t dstW, size_t dstH, int device,
                           iqo_hip_roi_yuv_plan **out)
 {
-    if (!out)
-        return IQO_HIP_EINVAL;
-    *out = nullptr;
-    if (method < 0 || method > 2 || (method == IQO_METHOD_LANCZOS && degree < 1) || !dstW || !dstH ||
-        dstW > (1u << 20) || dstH > (1u << 20) || (layout != IQO_ROI_NV12 && layout != IQO_ROI_I420))
-        return IQO_HIP_EINVAL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || !is_gfx950(device))
-        return IQO_HIP_ENODEV;
-    DeviceGuard guard(device);
-    if (!guard.ok())
-        return IQO_HIP_ENODEV;
-    iqo_hip_roi_yuv_plan *h = new (std::nothrow) iqo_hip_roi_yuv_plan(
-        static_cast<iqo_amd::Method>(method), degree, layout, static_cast<int>(dstW), static_cast<int>(dstH), device);
-    if (!h)
-        return IQO_HIP_ENOMEM;
-    for (auto &a : h->arena)
-        if (hipEventCreateWithFlags(&a.ev, hipEventDisableTiming) != hipSuccess) {
-            iqo_hip_roi_yuv_plan_destroy(h);
-            return IQO_HIP_EHIP;
-        }
-    *out = h;
-    return IQO_HIP_OK;
+    const bool ok = layout == IQO_ROI_NV12 || layout == IQO_ROI_I420;
+    return roi_plan_create(method, degree, layout, ok ? IQO_HIP_OK : IQO_HIP_EINVAL, dstW, dstH, device, out);
 }
 
-void iqo_hip_roi_yuv_plan_destroy(iqo_hip_roi_yuv_plan *h)
-{
-    if (!h)
-        return;
-    {
-        DeviceGuard guard(h->device);
-        for (auto &a : h->arena) {
-            if (a.pending)
-                (void)hipEventSynchronize(a.ev);
-            if (a.ev)
-                (void)hipEventDestroy(a.ev);
-            roi_arena_free(&a);
-        }
-    }
-    delete h;
-}
+void iqo_hip_roi_yuv_plan_destroy(iqo_hip_roi_yuv_plan *h) { roi_plan_destroy(h); }
 
 int iqo_hip_resize_rois_yuv_rgb_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
                                        size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
@@ -4236,8 +4197,7 @@ int iqo_host_roi_yuv_arena_stats(int method, unsigned degree, int layout, size_t
 int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
                                 iqo_hip_roi_yuv_box_layout *out)
 {
-    if (!out || method < 0 || method > 2 || !dstW || !dstH || dstW > (1u << 20) || dstH > (1u << 20) || !w || !h ||
-        w > (1u << 24) || h > (1u << 24))
+    if (!out || method < 0 || method > 2 || !roi_dst_dims_ok(dstW, dstH) || !w || !h || w > (1u << 24) || h > (1u << 24))
         return IQO_HIP_EINVAL;
     // the box as the whole of one tightly packed frame: roi_yuv_layout on a one-box call, as the device call
     const iqo_amd::RoiBox box = {0, 0, 0, static_cast<int>(w), static_cast<int>(h), 0};

@@ -108,17 +108,94 @@ void RoiTableCache::clear()
     bytes_ = 0;
 }
 
+void RoiLayout::reset()
+{
+    // (cleared member by member: a plan's layout keeps its capacity from call to call)
+    nRois = channels = nXTables = nYTables = 0;
+    words = ldsBytes = 0;
+    groups = 0;
+    tables.clear();
+    rec.clear();
+    xIdx.clear();
+    yIdx.clear();
+}
+
+namespace {
+
+struct TableRef {
+    const uint32_t *t = nullptr;  // nullptr: the axis has no table, and *status says why
+    uint32_t off = 0;             // its word offset in the arena
+};
+
+// The table of (axis, len) in the layout, appended at *words (from the cache) where the call has none yet.
+TableRef table_for(RoiTableCache *cache, RoiLayout *l, bool isX, int len, size_t *words, int *status)
+{
+    std::vector<std::pair<int, int>> &idx = isX ? l->xIdx : l->yIdx;
+    auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(len, 0));
+    if (it == idx.end() || it->first != len) {
+        int why = 0;
+        RoiTableCache::Table t = cache->get(isX, len, &why);
+        if (!t) {
+            *status = why ? kRoiUnsupported : kRoiInvalid;
+            return TableRef();
+        }
+        it = idx.insert(it, std::make_pair(len, static_cast<int>(l->tables.size())));
+        l->tables.emplace_back(t, static_cast<uint32_t>(*words));
+        *words += t->size();
+        ++(isX ? l->nXTables : l->nYTables);
+    }
+    const auto &e = l->tables[static_cast<size_t>(it->second)];
+    TableRef r;
+    r.t = e.first->data();
+    r.off = e.second;
+    return r;
+}
+
+bool box_in_frame(const RoiBox &b, size_t nFrames, size_t frameW, size_t frameH)
+{
+    return b.w > 0 && b.h > 0 && b.x >= 0 && b.y >= 0 && static_cast<size_t>(b.x) + static_cast<size_t>(b.w) <= frameW &&
+           static_cast<size_t>(b.y) + static_cast<size_t>(b.h) <= frameH && b.frame >= 0 &&
+           static_cast<size_t>(b.frame) < nFrames && !(b.flags & ~1);
+}
+
+// Output rows per workgroup of a box whose band row takes rowBytes of LDS (tap records and work rows): as many
+// as fit in kRoiLdsTarget, at most kRoiMaxRows; 0 when one row is over kRoiLdsMax.  *ldsBytes: the call's largest.
+int band_rows(int dstH, size_t rowBytes, size_t *ldsBytes)
+{
+    if (rowBytes > static_cast<size_t>(kRoiLdsMax))
+        return 0;
+    const int rows = std::max(1, std::min(std::min(dstH, kRoiMaxRows), static_cast<int>(kRoiLdsTarget / rowBytes)));
+    *ldsBytes = std::max(*ldsBytes, rows * rowBytes);
+    return rows;
+}
+
+// more boxes than one grid (or one arena) can address
+bool over_caps(uint64_t groups, size_t words) { return groups >= (uint64_t(1) << 31) || words >= (size_t(1) << 30); }
+
+// The header words both formats share, the records and the tables.
+void fill_common(uint32_t magic, const RoiTableCache &cache, const RoiLayout &l, uint32_t *arena)
+{
+    std::memset(arena, 0, kRoiHdrWords * 4);
+    arena[kHMagic] = magic;
+    arena[kHRois] = static_cast<uint32_t>(l.nRois);
+    arena[kHGroups] = l.groups;
+    arena[kHDstW] = static_cast<uint32_t>(cache.dstW());
+    arena[kHDstH] = static_cast<uint32_t>(cache.dstH());
+    arena[kHLanczos] = cache.method() == kLanczos ? 1u : 0u;
+    arena[kHRecOff] = kRoiHdrWords;
+    arena[kHWords] = static_cast<uint32_t>(l.words);
+    if (!l.rec.empty())
+        std::memcpy(arena + kRoiHdrWords, l.rec.data(), l.rec.size() * 4);
+    for (const auto &t : l.tables)
+        std::memcpy(arena + t.second, t.first->data(), t.first->size() * 4);
+}
+
+} // namespace
+
 int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, size_t nFrames, size_t frameW,
                size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad)
 {
-    // (cleared member by member: a plan's layout keeps its capacity from call to call)
-    out->nRois = out->channels = out->nXTables = out->nYTables = 0;
-    out->words = out->ldsBytes = 0;
-    out->groups = 0;
-    out->tables.clear();
-    out->rec.clear();
-    out->xIdx.clear();
-    out->yIdx.clear();
+    out->reset();
     *bad = -1;
     if (channels != 1 && channels != 3 && channels != 4)
         return kRoiUnsupported;
@@ -140,38 +217,19 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
     for (size_t i = 0; i < nRois; ++i) {
         const RoiBox &b = rois[i];
         *bad = static_cast<int>(i);
-        if (b.w <= 0 || b.h <= 0 || b.x < 0 || b.y < 0 || static_cast<size_t>(b.x) + static_cast<size_t>(b.w) > frameW ||
-            static_cast<size_t>(b.y) + static_cast<size_t>(b.h) > frameH || b.frame < 0 ||
-            static_cast<size_t>(b.frame) >= nFrames || (b.flags & ~1))
+        if (!box_in_frame(b, nFrames, frameW, frameH))
             return kRoiInvalid;
-        uint32_t tabOff[2];
-        const uint32_t *tab[2];
-        for (int ax = 0; ax < 2; ++ax) {
-            const bool isX = ax == 0;
-            std::vector<std::pair<int, int>> &idx = isX ? out->xIdx : out->yIdx;
-            const int len = isX ? b.w : b.h;
-            auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(len, 0));
-            if (it == idx.end() || it->first != len) {
-                int why = 0;
-                RoiTableCache::Table t = cache->get(isX, len, &why);
-                if (!t)
-                    return why ? kRoiUnsupported : kRoiInvalid;
-                it = idx.insert(it, std::make_pair(len, static_cast<int>(out->tables.size())));
-                out->tables.emplace_back(t, static_cast<uint32_t>(words));
-                words += t->size();
-                ++(isX ? out->nXTables : out->nYTables);
-            }
-            tabOff[ax] = out->tables[static_cast<size_t>(it->second)].second;
-            tab[ax] = out->tables[static_cast<size_t>(it->second)].first->data();
-        }
-        // rows per workgroup: the band's tap records and its work rows over the box's width and channels
-        const size_t pitchDw = tab[0][2], nYp = tab[1][0];
-        const size_t rowBytes = C * pitchDw * 4 + nYp * 8;
-        if (rowBytes > static_cast<size_t>(kRoiLdsMax))
+        int st = kRoiOk;
+        const TableRef x = table_for(cache, out, true, b.w, &words, &st);
+        const TableRef y = x.t ? table_for(cache, out, false, b.h, &words, &st) : x;
+        if (!y.t)
+            return st;
+        // a band row: its tap records and its work rows over the box's width and channels
+        const size_t pitchDw = x.t[2], nYp = y.t[0];
+        const int rows = band_rows(dstH, C * pitchDw * 4 + nYp * 8, &out->ldsBytes);
+        if (!rows)
             return kRoiUnsupported;
-        const int rows = std::max(1, std::min(std::min(dstH, kRoiMaxRows), static_cast<int>(kRoiLdsTarget / rowBytes)));
         const uint32_t g = static_cast<uint32_t>((dstH + rows - 1) / rows);
-        out->ldsBytes = std::max(out->ldsBytes, rows * rowBytes);
         const uint64_t off = static_cast<uint64_t>(b.frame) * frameSt + static_cast<uint64_t>(b.y) * srcSt +
                              static_cast<uint64_t>(b.x) * C;
         uint32_t *r = out->rec.data() + i * kRoiRecWords;
@@ -183,15 +241,15 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
         r[kRW] = static_cast<uint32_t>(b.w);
         r[kRH] = static_cast<uint32_t>(b.h);
         r[kRFlags] = static_cast<uint32_t>(b.flags);
-        r[kRXTab] = tabOff[0];
-        r[kRYTab] = tabOff[1];
+        r[kRXTab] = x.off;
+        r[kRYTab] = y.off;
         r[kRRows] = static_cast<uint32_t>(rows);
         r[kRFirst] = static_cast<uint32_t>(groups);
         r[kRGroups] = g;
         r[kRPitch] = static_cast<uint32_t>(pitchDw);
         groups += g;
-        if (groups >= (uint64_t(1) << 31) || words >= (size_t(1) << 30))
-            return kRoiUnsupported;  // more boxes than one grid (or one arena) can address
+        if (over_caps(groups, words))
+            return kRoiUnsupported;
     }
     *bad = -1;
     out->words = words;
@@ -201,21 +259,9 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
 
 void roi_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena)
 {
-    std::memset(arena, 0, kRoiHdrWords * 4);
-    arena[kHMagic] = kRoiMagic;
-    arena[kHRois] = static_cast<uint32_t>(l.nRois);
-    arena[kHGroups] = l.groups;
-    arena[kHDstW] = static_cast<uint32_t>(cache.dstW());
-    arena[kHDstH] = static_cast<uint32_t>(cache.dstH());
+    fill_common(kRoiMagic, cache, l, arena);
     arena[kHChannels] = static_cast<uint32_t>(l.channels);
-    arena[kHLanczos] = cache.method() == kLanczos ? 1u : 0u;
     arena[kHRowBytes] = static_cast<uint32_t>(frameW * static_cast<size_t>(l.channels));
-    arena[kHRecOff] = kRoiHdrWords;
-    arena[kHWords] = static_cast<uint32_t>(l.words);
-    if (!l.rec.empty())
-        std::memcpy(arena + kRoiHdrWords, l.rec.data(), l.rec.size() * 4);
-    for (const auto &t : l.tables)
-        std::memcpy(arena + t.second, t.first->data(), t.first->size() * 4);
 }
 
 // ---------------------------------------------------------------- CPU twin
@@ -256,231 +302,9 @@ uint16_t bf16_bits_host(float f)
     return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
-} // namespace
-
-void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
-              void *dstV, const RoiNorm &n)
-{
-    const int nRois = static_cast<int>(arena[kHRois]);
-    const int dstW = static_cast<int>(arena[kHDstW]), dstH = static_cast<int>(arena[kHDstH]);
-    const int C = static_cast<int>(arena[kHChannels]);
-    const bool LZ = arena[kHLanczos] != 0;
-    uint8_t *dst = static_cast<uint8_t *>(dstV);
-    std::vector<uint16_t> work;
-    for (int i = 0; i < nRois; ++i) {
-        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * kRoiRecWords;
-        const uint8_t *box = src + ((static_cast<uint64_t>(r[kROffHi]) << 32) | r[kROffLo]);
-        const int w = static_cast<int>(r[kRW]);
-        const bool flip = r[kRFlags] & 1u;
-        const uint32_t *xt = arena + r[kRXTab], *yt = arena + r[kRYTab];
-        const int NP = static_cast<int>(xt[0]), padL = static_cast<int>(xt[1]), pitch = 2 * static_cast<int>(xt[2]);
-        const int32_t *col = reinterpret_cast<const int32_t *>(xt + 4);
-        const uint32_t *cx = xt + 4 + 2 * static_cast<size_t>(dstW);
-        const int nYp = static_cast<int>(yt[0]);
-        const int32_t *row = reinterpret_cast<const int32_t *>(yt + 4);
-        const uint32_t *cy = yt + 4 + 4 * static_cast<size_t>(dstH);
-        work.assign(static_cast<size_t>(C) * pitch, 0);
-        for (int y = 0; y < dstH; ++y) {
-            const int32_t start = row[4 * y], lo = row[4 * y + 1], hi = row[4 * y + 2], deno = row[4 * y + 3];
-            // vertical: 16-bit wrapping sums over the row window, rows clamped to the box
-            for (int q = 0; q < w * C; ++q) {
-                uint16_t acc = 0;
-                for (int k = 0; k < nYp; ++k) {
-                    const int rr = std::max(lo, std::min(start + k, hi));
-                    const uint16_t c = static_cast<uint16_t>(cy[static_cast<size_t>(y) * (nYp / 2) + k / 2] >> (16 * (k & 1)));
-                    acc = static_cast<uint16_t>(acc + box[static_cast<size_t>(rr) * srcSt + q] * c);
-                }
-                if (LZ && deno != 0)
-                    acc = static_cast<uint16_t>(static_cast<int16_t>(static_cast<int>(static_cast<int16_t>(acc)) * 64 / deno));
-                work[static_cast<size_t>(q % C) * pitch + padL + q / C] = acc;
-            }
-            for (int c = 0; c < C; ++c) {  // columns outside the box: the clamped edge column
-                uint16_t *wr = work.data() + static_cast<size_t>(c) * pitch;
-                for (int k = 0; k < padL; ++k)
-                    wr[k] = wr[padL];
-                for (int k = padL + w; k < pitch; ++k)
-                    wr[k] = wr[padL + w - 1];
-            }
-            // horizontal
-            for (int x = 0; x < dstW; ++x) {
-                const int32_t a = col[2 * x], D = col[2 * x + 1];
-                uint32_t bt[4] = {0, 0, 0, 0};
-                for (int c = 0; c < C; ++c) {
-                    const uint16_t *wr = work.data() + static_cast<size_t>(c) * pitch + padL + a;
-                    if (LZ) {
-                        int32_t s = 1 << 19;
-                        for (int p = 0; p < NP; ++p) {
-                            const uint32_t cf = cx[static_cast<size_t>(p) * dstW + x];
-                            s += static_cast<int16_t>(wr[2 * p]) * static_cast<int16_t>(cf & 0xffffu) +
-                                 static_cast<int16_t>(wr[2 * p + 1]) * static_cast<int16_t>(cf >> 16);
-                        }
-                        int v = s >> 20;
-                        if (D != 0)
-                            v = static_cast<int16_t>(s / D);
-                        bt[c] = static_cast<uint32_t>(std::min(std::max(v, 0), 255));
-                    } else {
-                        uint32_t s = 1u << 22;
-                        for (int p = 0; p < NP; ++p) {
-                            const uint32_t cf = cx[static_cast<size_t>(p) * dstW + x];
-                            s += static_cast<uint32_t>(wr[2 * p]) * (cf & 0xffffu) + static_cast<uint32_t>(wr[2 * p + 1]) * (cf >> 16);
-                        }
-                        bt[c] = std::min((s >> 23) & 0xffffu, 255u);
-                    }
-                }
-                const int xo = flip ? dstW - 1 - x : x;
-                if (n.dtype == 0) {
-                    uint8_t *o = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt + static_cast<size_t>(xo) * C;
-                    for (int c = 0; c < C; ++c)
-                        o[c] = static_cast<uint8_t>(bt[c]);
-                } else {
-                    const size_t elem = n.dtype == 1 ? 4 : 2;
-                    for (int p = 0; p < n.planes; ++p) {
-                        volatile float m = static_cast<float>(bt[n.order[p]]) * n.scale[p];  // two roundings
-                        const float f = m + n.bias[p];
-                        uint8_t *o = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(p) * planeSt +
-                                     static_cast<size_t>(y) * dstSt + static_cast<size_t>(xo) * elem;
-                        if (n.dtype == 1) {
-                            std::memcpy(o, &f, 4);
-                        } else {
-                            const uint16_t h = n.dtype == 2 ? f16_bits_host(f) : bf16_bits_host(f);
-                            std::memcpy(o, &h, 2);
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB
-
-int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, RoiLayout *out, int *bad)
-{
-    out->nRois = out->channels = out->nXTables = out->nYTables = 0;
-    out->words = out->ldsBytes = 0;
-    out->groups = 0;
-    out->tables.clear();
-    out->rec.clear();
-    out->xIdx.clear();
-    out->yIdx.clear();
-    *bad = -1;
-    const bool nv12 = s.layout == kRoiNv12;
-    if ((!nv12 && s.layout != kRoiI420) || !s.frameW || !s.frameH || (s.frameW & 1) || (s.frameH & 1) ||
-        s.frameW > (1u << 24) || s.frameH > (1u << 24) || s.stY < s.frameW || s.stUV < (nv12 ? s.frameW : s.frameW / 2) ||
-        (nRois && !rois) || cache->dstW() < 1 || cache->dstH() < 1)
-        return kRoiInvalid;
-    // the kernel keeps byte offsets within a frame's planes in 32 bits
-    if (s.stY >= (size_t(1) << 31) / s.frameH || s.stUV >= (size_t(1) << 31) / (s.frameH / 2))
-        return kRoiUnsupported;
-    if (nRois >= (size_t(1) << 24))
-        return kRoiUnsupported;
-    out->nRois = static_cast<int>(nRois);
-    out->channels = s.layout;
-    out->rec.assign(nRois * kRoiYuvRecWords, 0u);
-    size_t words = kRoiHdrWords + nRois * kRoiYuvRecWords;
-    uint64_t groups = 0;
-    const int dstW = cache->dstW(), dstH = cache->dstH();
-    const bool linear = cache->method() == kLinear;
-    for (size_t i = 0; i < nRois; ++i) {
-        const RoiBox &b = rois[i];
-        *bad = static_cast<int>(i);
-        if (b.w < 2 || b.h < 2 || b.x < 0 || b.y < 0 || ((b.x | b.y | b.w | b.h) & 1) ||
-            static_cast<size_t>(b.x) + static_cast<size_t>(b.w) > s.frameW ||
-            static_cast<size_t>(b.y) + static_cast<size_t>(b.h) > s.frameH || b.frame < 0 ||
-            static_cast<size_t>(b.frame) >= s.nFrames || (b.flags & ~1))
-            return kRoiInvalid;
-        // Linear chroma above 2x has no pinned answer (the rule of the YUV plans' full-grid chroma)
-        if (linear && (dstW > b.w || dstH > b.h))
-            return kRoiUnsupported;
-        // tables: X of w, Y of h, X of w / 2, Y of h / 2
-        uint32_t tabOff[4];
-        const uint32_t *tab[4];
-        for (int k = 0; k < 4; ++k) {
-            const bool isX = !(k & 1);
-            std::vector<std::pair<int, int>> &idx = isX ? out->xIdx : out->yIdx;
-            const int len = (isX ? b.w : b.h) >> (k >> 1);
-            auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(len, 0));
-            if (it == idx.end() || it->first != len) {
-                int why = 0;
-                RoiTableCache::Table t = cache->get(isX, len, &why);
-                if (!t)
-                    return why ? kRoiUnsupported : kRoiInvalid;
-                it = idx.insert(it, std::make_pair(len, static_cast<int>(out->tables.size())));
-                out->tables.emplace_back(t, static_cast<uint32_t>(words));
-                words += t->size();
-                ++(isX ? out->nXTables : out->nYTables);
-            }
-            tabOff[k] = out->tables[static_cast<size_t>(it->second)].second;
-            tab[k] = out->tables[static_cast<size_t>(it->second)].first->data();
-        }
-        // rows per workgroup: both sets of tap records, and the Y, U and V work rows
-        const size_t pitchY = tab[0][2], pitchC = tab[2][2], nYpY = tab[1][0], nYpC = tab[3][0];
-        const size_t rowBytes = (pitchY + 2 * pitchC) * 4 + (nYpY + nYpC) * 8;
-        if (rowBytes > static_cast<size_t>(kRoiLdsMax))
-            return kRoiUnsupported;
-        const int rows = std::max(1, std::min(std::min(dstH, kRoiMaxRows), static_cast<int>(kRoiLdsTarget / rowBytes)));
-        const uint32_t g = static_cast<uint32_t>((dstH + rows - 1) / rows);
-        out->ldsBytes = std::max(out->ldsBytes, rows * rowBytes);
-        const uint64_t frame = static_cast<uint64_t>(b.frame) * s.frameSt;
-        const uint64_t off = frame + static_cast<uint64_t>(b.y) * s.stY + static_cast<uint64_t>(b.x);
-        const uint64_t offC = frame + static_cast<uint64_t>(b.y / 2) * s.stUV + static_cast<uint64_t>(nv12 ? b.x : b.x / 2);
-        uint32_t *r = out->rec.data() + i * kRoiYuvRecWords;
-        r[kYFrame] = static_cast<uint32_t>(b.frame);
-        r[kYOffLo] = static_cast<uint32_t>(off);
-        r[kYOffHi] = static_cast<uint32_t>(off >> 32);
-        r[kYOffCLo] = static_cast<uint32_t>(offC);
-        r[kYOffCHi] = static_cast<uint32_t>(offC >> 32);
-        r[kYX] = static_cast<uint32_t>(b.x);
-        r[kYY] = static_cast<uint32_t>(b.y);
-        r[kYW] = static_cast<uint32_t>(b.w);
-        r[kYH] = static_cast<uint32_t>(b.h);
-        r[kYFlags] = static_cast<uint32_t>(b.flags);
-        r[kYXTab] = tabOff[0];
-        r[kYYTab] = tabOff[1];
-        r[kYXTabC] = tabOff[2];
-        r[kYYTabC] = tabOff[3];
-        r[kYRows] = static_cast<uint32_t>(rows);
-        r[kYFirst] = static_cast<uint32_t>(groups);
-        r[kYGroups] = g;
-        r[kYPitch] = static_cast<uint32_t>(pitchY);
-        r[kYPitchC] = static_cast<uint32_t>(pitchC);
-        groups += g;
-        if (groups >= (uint64_t(1) << 31) || words >= (size_t(1) << 30))
-            return kRoiUnsupported;  // more boxes than one grid (or one arena) can address
-    }
-    *bad = -1;
-    out->words = words;
-    out->groups = static_cast<uint32_t>(groups);
-    return kRoiOk;
-}
-
-void roi_yuv_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena)
-{
-    std::memset(arena, 0, kRoiHdrWords * 4);
-    arena[kHMagic] = kRoiYuvMagic;
-    arena[kHRois] = static_cast<uint32_t>(l.nRois);
-    arena[kHGroups] = l.groups;
-    arena[kHDstW] = static_cast<uint32_t>(cache.dstW());
-    arena[kHDstH] = static_cast<uint32_t>(cache.dstH());
-    arena[kHYLayout] = static_cast<uint32_t>(s.layout);
-    arena[kHLanczos] = cache.method() == kLanczos ? 1u : 0u;
-    arena[kHYRowBytes] = static_cast<uint32_t>(s.frameW);
-    arena[kHRecOff] = kRoiHdrWords;
-    arena[kHWords] = static_cast<uint32_t>(l.words);
-    arena[kHYRowBytesC] = static_cast<uint32_t>(s.layout == kRoiNv12 ? s.frameW : s.frameW / 2);
-    arena[kHYStY] = static_cast<uint32_t>(s.stY);
-    arena[kHYStC] = static_cast<uint32_t>(s.stUV);
-    if (!l.rec.empty())
-        std::memcpy(arena + kRoiHdrWords, l.rec.data(), l.rec.size() * 4);
-    for (const auto &t : l.tables)
-        std::memcpy(arena + t.second, t.first->data(), t.first->size() * 4);
-}
-
-namespace {
-
-// One component's bytes of output row y of a box, with roi_walk's formulas: sample q of source row rr is
-// box[rr * st + q * step] (step 2: one half of an interleaved UV row), n samples per row.
-void yuv_component_row(const uint32_t *xt, const uint32_t *yt, int dstW, int dstH, bool LZ, const uint8_t *box, size_t st,
+// One component's bytes of output row y of a box, with the kernels' integer formulas: sample q of source row rr
+// is box[rr * st + q * step] (step C: one channel of interleaved pixels, one half of a UV row), n samples per row.
+void component_row(const uint32_t *xt, const uint32_t *yt, int dstW, int dstH, bool LZ, const uint8_t *box, size_t st,
                        int step, int n, int y, std::vector<uint16_t> *workV, uint8_t *out)
 {
     const int NP = static_cast<int>(xt[0]), padL = static_cast<int>(xt[1]), pitch = 2 * static_cast<int>(xt[2]);
@@ -492,6 +316,7 @@ void yuv_component_row(const uint32_t *xt, const uint32_t *yt, int dstW, int dst
     workV->assign(static_cast<size_t>(pitch), 0);
     uint16_t *work = workV->data();
     const int32_t start = row[4 * y], lo = row[4 * y + 1], hi = row[4 * y + 2], deno = row[4 * y + 3];
+    // vertical: 16-bit wrapping sums over the row window, rows clamped to the box
     for (int q = 0; q < n; ++q) {
         uint16_t acc = 0;
         for (int k = 0; k < nYp; ++k) {
@@ -503,10 +328,11 @@ void yuv_component_row(const uint32_t *xt, const uint32_t *yt, int dstW, int dst
             acc = static_cast<uint16_t>(static_cast<int16_t>(static_cast<int>(static_cast<int16_t>(acc)) * 64 / deno));
         work[padL + q] = acc;
     }
-    for (int k = 0; k < padL; ++k)
+    for (int k = 0; k < padL; ++k)  // columns outside the box: the clamped edge column
         work[k] = work[padL];
     for (int k = padL + n; k < pitch; ++k)
         work[k] = work[padL + n - 1];
+    // horizontal
     for (int x = 0; x < dstW; ++x) {
         const int32_t a = col[2 * x], D = col[2 * x + 1];
         const uint16_t *wr = work + padL + a;
@@ -532,7 +358,150 @@ void yuv_component_row(const uint32_t *xt, const uint32_t *yt, int dstW, int dst
     }
 }
 
+// One output pixel at column xo of row `o` (of its box's first plane): bytes px[order[c]], c < channels
+// (n.dtype == 0), or plane p = px[n.order[p]] scaled and biased, planeSt bytes apart.
+void store_pixel(const int px[4], int channels, const int order[4], const RoiNorm &n, size_t planeSt, uint8_t *o, int xo)
+{
+    if (n.dtype == 0) {
+        uint8_t *e = o + static_cast<size_t>(xo) * channels;
+        for (int c = 0; c < channels; ++c)
+            e[c] = static_cast<uint8_t>(px[order[c]]);
+        return;
+    }
+    const size_t elem = n.dtype == 1 ? 4 : 2;
+    for (int p = 0; p < n.planes; ++p) {
+        volatile float m = static_cast<float>(px[n.order[p]]) * n.scale[p];  // two roundings
+        const float f = m + n.bias[p];
+        uint8_t *e = o + static_cast<size_t>(p) * planeSt + static_cast<size_t>(xo) * elem;
+        if (n.dtype == 1) {
+            std::memcpy(e, &f, 4);
+        } else {
+            const uint16_t h = n.dtype == 2 ? f16_bits_host(f) : bf16_bits_host(f);
+            std::memcpy(e, &h, 2);
+        }
+    }
+}
+
 } // namespace
+
+void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+              void *dstV, const RoiNorm &n)
+{
+    const int nRois = static_cast<int>(arena[kHRois]);
+    const int dstW = static_cast<int>(arena[kHDstW]), dstH = static_cast<int>(arena[kHDstH]);
+    const int C = static_cast<int>(arena[kHChannels]);
+    const bool LZ = arena[kHLanczos] != 0;
+    const int order[4] = {0, 1, 2, 3};
+    uint8_t *dst = static_cast<uint8_t *>(dstV);
+    std::vector<uint16_t> work;
+    std::vector<uint8_t> line(static_cast<size_t>(C) * dstW);
+    for (int i = 0; i < nRois; ++i) {
+        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * kRoiRecWords;
+        const uint8_t *box = src + ((static_cast<uint64_t>(r[kROffHi]) << 32) | r[kROffLo]);
+        const int w = static_cast<int>(r[kRW]);
+        const bool flip = r[kRFlags] & 1u;
+        const uint32_t *xt = arena + r[kRXTab], *yt = arena + r[kRYTab];
+        for (int y = 0; y < dstH; ++y) {
+            for (int c = 0; c < C; ++c)
+                component_row(xt, yt, dstW, dstH, LZ, box + c, srcSt, C, w, y, &work, line.data() + static_cast<size_t>(c) * dstW);
+            uint8_t *o = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt;
+            for (int x = 0; x < dstW; ++x) {
+                int px[4] = {0, 0, 0, 0};
+                for (int c = 0; c < C; ++c)
+                    px[c] = line[static_cast<size_t>(c) * dstW + x];
+                store_pixel(px, C, order, n, planeSt, o, flip ? dstW - 1 - x : x);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB
+
+int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, RoiLayout *out, int *bad)
+{
+    out->reset();
+    *bad = -1;
+    const bool nv12 = s.layout == kRoiNv12;
+    if ((!nv12 && s.layout != kRoiI420) || !s.frameW || !s.frameH || (s.frameW & 1) || (s.frameH & 1) ||
+        s.frameW > (1u << 24) || s.frameH > (1u << 24) || s.stY < s.frameW || s.stUV < (nv12 ? s.frameW : s.frameW / 2) ||
+        (nRois && !rois) || cache->dstW() < 1 || cache->dstH() < 1)
+        return kRoiInvalid;
+    // the kernel keeps byte offsets within a frame's planes in 32 bits
+    if (s.stY >= (size_t(1) << 31) / s.frameH || s.stUV >= (size_t(1) << 31) / (s.frameH / 2))
+        return kRoiUnsupported;
+    if (nRois >= (size_t(1) << 24))
+        return kRoiUnsupported;
+    out->nRois = static_cast<int>(nRois);
+    out->channels = s.layout;
+    out->rec.assign(nRois * kRoiYuvRecWords, 0u);
+    size_t words = kRoiHdrWords + nRois * kRoiYuvRecWords;
+    uint64_t groups = 0;
+    const int dstW = cache->dstW(), dstH = cache->dstH();
+    const bool linear = cache->method() == kLinear;
+    for (size_t i = 0; i < nRois; ++i) {
+        const RoiBox &b = rois[i];
+        *bad = static_cast<int>(i);
+        if (!box_in_frame(b, s.nFrames, s.frameW, s.frameH) || ((b.x | b.y | b.w | b.h) & 1))
+            return kRoiInvalid;
+        // Linear chroma above 2x has no pinned answer (the rule of the YUV plans' full-grid chroma)
+        if (linear && (dstW > b.w || dstH > b.h))
+            return kRoiUnsupported;
+        // tables: X of w, Y of h, X of w / 2, Y of h / 2
+        TableRef t[4];
+        int st = kRoiOk;
+        for (int k = 0; k < 4; ++k) {
+            t[k] = table_for(cache, out, !(k & 1), ((k & 1) ? b.h : b.w) >> (k >> 1), &words, &st);
+            if (!t[k].t)
+                return st;
+        }
+        // a band row: both sets of tap records, and the Y, U and V work rows
+        const size_t pitchY = t[0].t[2], pitchC = t[2].t[2], nYpY = t[1].t[0], nYpC = t[3].t[0];
+        const int rows = band_rows(dstH, (pitchY + 2 * pitchC) * 4 + (nYpY + nYpC) * 8, &out->ldsBytes);
+        if (!rows)
+            return kRoiUnsupported;
+        const uint32_t g = static_cast<uint32_t>((dstH + rows - 1) / rows);
+        const uint64_t frame = static_cast<uint64_t>(b.frame) * s.frameSt;
+        const uint64_t off = frame + static_cast<uint64_t>(b.y) * s.stY + static_cast<uint64_t>(b.x);
+        const uint64_t offC = frame + static_cast<uint64_t>(b.y / 2) * s.stUV + static_cast<uint64_t>(nv12 ? b.x : b.x / 2);
+        uint32_t *r = out->rec.data() + i * kRoiYuvRecWords;
+        r[kYFrame] = static_cast<uint32_t>(b.frame);
+        r[kYOffLo] = static_cast<uint32_t>(off);
+        r[kYOffHi] = static_cast<uint32_t>(off >> 32);
+        r[kYOffCLo] = static_cast<uint32_t>(offC);
+        r[kYOffCHi] = static_cast<uint32_t>(offC >> 32);
+        r[kYX] = static_cast<uint32_t>(b.x);
+        r[kYY] = static_cast<uint32_t>(b.y);
+        r[kYW] = static_cast<uint32_t>(b.w);
+        r[kYH] = static_cast<uint32_t>(b.h);
+        r[kYFlags] = static_cast<uint32_t>(b.flags);
+        r[kYXTab] = t[0].off;
+        r[kYYTab] = t[1].off;
+        r[kYXTabC] = t[2].off;
+        r[kYYTabC] = t[3].off;
+        r[kYRows] = static_cast<uint32_t>(rows);
+        r[kYFirst] = static_cast<uint32_t>(groups);
+        r[kYGroups] = g;
+        r[kYPitch] = static_cast<uint32_t>(pitchY);
+        r[kYPitchC] = static_cast<uint32_t>(pitchC);
+        groups += g;
+        if (over_caps(groups, words))
+            return kRoiUnsupported;
+    }
+    *bad = -1;
+    out->words = words;
+    out->groups = static_cast<uint32_t>(groups);
+    return kRoiOk;
+}
+
+void roi_yuv_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena)
+{
+    fill_common(kRoiYuvMagic, cache, l, arena);
+    arena[kHYLayout] = static_cast<uint32_t>(s.layout);
+    arena[kHYRowBytes] = static_cast<uint32_t>(s.frameW);
+    arena[kHYRowBytesC] = static_cast<uint32_t>(s.layout == kRoiNv12 ? s.frameW : s.frameW / 2);
+    arena[kHYStY] = static_cast<uint32_t>(s.stY);
+    arena[kHYStC] = static_cast<uint32_t>(s.stUV);
+}
 
 void roi_yuv_walk(const uint32_t *arena, const uint8_t *yP, const uint8_t *uP, const uint8_t *vP, const RoiYuvOut &o,
                   size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dstV)
@@ -542,7 +511,6 @@ void roi_yuv_walk(const uint32_t *arena, const uint8_t *yP, const uint8_t *uP, c
     const bool LZ = arena[kHLanczos] != 0, nv12 = arena[kHYLayout] == static_cast<uint32_t>(kRoiNv12);
     const size_t stY = arena[kHYStY], stC = arena[kHYStC];
     const YuvRgbCoef &k = kYuvRgb[o.standard];
-    const RoiNorm &n = o.n;
     uint8_t *dst = static_cast<uint8_t *>(dstV);
     std::vector<uint16_t> work;
     std::vector<uint8_t> line(3 * static_cast<size_t>(dstW));
@@ -556,33 +524,14 @@ void roi_yuv_walk(const uint32_t *arena, const uint8_t *yP, const uint8_t *uP, c
         const uint32_t *xt = arena + r[kYXTab], *yt = arena + r[kYYTab];
         const uint32_t *xtC = arena + r[kYXTabC], *ytC = arena + r[kYYTabC];
         for (int y = 0; y < dstH; ++y) {
-            yuv_component_row(xt, yt, dstW, dstH, LZ, yP + off, stY, 1, w, y, &work, Y);
-            yuv_component_row(xtC, ytC, dstW, dstH, LZ, uP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, U);
-            yuv_component_row(xtC, ytC, dstW, dstH, LZ, nv12 ? uP + offC + 1 : vP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, V);
+            component_row(xt, yt, dstW, dstH, LZ, yP + off, stY, 1, w, y, &work, Y);
+            component_row(xtC, ytC, dstW, dstH, LZ, uP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, U);
+            component_row(xtC, ytC, dstW, dstH, LZ, nv12 ? uP + offC + 1 : vP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, V);
+            uint8_t *e = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt;
             for (int x = 0; x < dstW; ++x) {
                 int px[4] = {0, 0, 0, 255};
                 yuv_to_rgb(k, Y[x], yuv_chroma_terms(k, U[x], V[x]), px[0], px[1], px[2]);
-                const int xo = flip ? dstW - 1 - x : x;
-                if (n.dtype == 0) {
-                    uint8_t *e = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt +
-                                 static_cast<size_t>(xo) * o.channels;
-                    for (int c = 0; c < o.channels; ++c)
-                        e[c] = static_cast<uint8_t>(px[o.order[c]]);
-                } else {
-                    const size_t elem = n.dtype == 1 ? 4 : 2;
-                    for (int p = 0; p < n.planes; ++p) {
-                        volatile float m = static_cast<float>(px[n.order[p]]) * n.scale[p];  // two roundings
-                        const float f = m + n.bias[p];
-                        uint8_t *e = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(p) * planeSt +
-                                     static_cast<size_t>(y) * dstSt + static_cast<size_t>(xo) * elem;
-                        if (n.dtype == 1) {
-                            std::memcpy(e, &f, 4);
-                        } else {
-                            const uint16_t h = n.dtype == 2 ? f16_bits_host(f) : bf16_bits_host(f);
-                            std::memcpy(e, &h, 2);
-                        }
-                    }
-                }
+                store_pixel(px, o.channels, o.order, o.n, planeSt, e, flip ? dstW - 1 - x : x);
             }
         }
     }

@@ -1,18 +1,29 @@
-// roi.hpp -- crop-and-resize of a batch of boxes to one output size (iqo_hip_resize_rois_device):
-// the per-call ARENA the kernel (kernels_roi.hip roi_kernel) and its CPU twin (roi_walk) both read,
-// the per-plan cache of axis tables that fills it, and the twin itself.  Pure C++ (no HIP).
+// roi.hpp -- crop-and-resize of a batch of boxes to one output size, of packed frames
+// (iqo_hip_resize_rois_device) and of NV12 / I420 frames to RGB (iqo_hip_resize_rois_yuv_*_device): the per-call
+// ARENA a kernel (kernels_roi.hip roi_kernel, kernels_roi_yuv.hip roi_yuv_kernel) and its CPU twin (roi_walk,
+// roi_yuv_walk) both read, the per-plan cache of axis tables that fills it, and the twins.  Pure C++ (no HIP).
 // (roi.cpp includes the HIP runtime header only where the HIP compiler builds it, so that colorspace.hpp's
 // __host__ __device__ markers parse in its device pass; a plain C++ compiler builds both files as they are.)
 //
-// Box i of a call is a rectangle (x, y, w, h) of frame `frame`; its output is what the planar resize
-// (w, h) -> (dstW, dstH) gives on the cropped image, channel by channel.  Each axis is independent
-// (plan.hpp build_axis), so a box needs the X table of (w -> dstW) and the Y table of (h -> dstH),
-// both in the one-window-per-coordinate form of plan.hpp axis_windows.
+// Box i of a call is a rectangle (x, y, w, h) of frame `frame`; a component of its output is what the planar
+// resize (w, h) -> (dstW, dstH) gives on that component of the cropped image.  Each axis is independent
+// (plan.hpp build_axis), so a component needs the X table of (w -> dstW) and the Y table of (h -> dstH), both in
+// the one-window-per-coordinate form of plan.hpp axis_windows, so identity, replicated and masked borders are
+// all one formula per axis.  A packed box has one such pair for all its channels; a YUV box one for its luma and
+// one for its half-size chroma (below).
+//
+// Rules of both formats, each in one function of roi.cpp:
+//   - a box lies inside its frame, and flags has no bit but bit 0 (box_in_frame);
+//   - a table is in the arena once, however many boxes and components use it (table_for);
+//   - a workgroup takes as many output rows of a box as fit in kRoiLdsTarget bytes of tap records and work
+//     rows, at most kRoiMaxRows, and one row fits in kRoiLdsMax (band_rows);
+//   - a call has fewer than 2^31 workgroups and 2^30 arena words (over_caps), fewer than 2^24 boxes, and byte
+//     offsets within a frame's plane fit in 32 bits.
 //
 // Arena: one flat buffer of 32-bit words.
-//   header   kRoiHdrWords words    see RoiHdr
-//   records  nRois x kRoiRecWords  see RoiRec
-//   tables   every distinct X table (one per distinct w) and Y table (one per distinct h), once
+//   header   kRoiHdrWords words    see RoiHdr (YUV: RoiYuvHdr)
+//   records  nRois x kRoiRecWords  see RoiRec (YUV: kRoiYuvRecWords, RoiYuvRec)
+//   tables   every distinct X table (one per distinct length) and Y table, once
 // X table (word offsets from the table's start):
 //   [0] NP  coefficient pairs per column      [1] padL  work columns left of column 0 (even)
 //   [2] pitchDw  work-row pitch of one channel (dwords; >= (padL + w + padR + 1) / 2, odd)
@@ -110,6 +121,7 @@ struct RoiLayout {
     std::vector<std::pair<RoiTableCache::Table, uint32_t>> tables;
     std::vector<uint32_t> rec;  // nRois x kRoiRecWords
     std::vector<std::pair<int, int>> xIdx, yIdx;  // sorted (distinct length, index in tables)
+    void reset();               // empty, keeping the vectors' capacity from call to call
 };
 
 // Status of roi_layout: kRoiOk, or the first offending box in *bad (-1: an argument of the call)
@@ -136,16 +148,12 @@ void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t ds
 
 // ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB
 //
-// iqo_hip_resize_rois_yuv_*_device (kernels_roi_yuv.hip roi_yuv_kernel, CPU twin roi_yuv_walk).  Box i is a
-// rectangle with even x, y, w, h of a 4:2:0 frame.  Its Y is the planar resize (w, h) -> (dstW, dstH) of the
-// cropped luma, its U and V the planar resize (w/2, h/2) -> (dstW, dstH) of the cropped chroma (the
+// Box i is a rectangle with even x, y, w, h of a 4:2:0 frame.  Its Y is the planar resize (w, h) -> (dstW, dstH)
+// of the cropped luma, its U and V the planar resize (w/2, h/2) -> (dstW, dstH) of the cropped chroma (the
 // full-grid chroma of IQO_CHROMA_FULL), and a pixel is colorspace.hpp yuv_to_rgb of the three.  A box so
 // needs four of the tables above: X of w and of w/2, Y of h and of h/2, from the one RoiTableCache -- keyed
-// by (axis, length), so a chroma axis shares the table of a luma axis of its length.
-//
-// The call has an arena format of its own: the same tables, with
-//   header   kRoiHdrWords words      see RoiYuvHdr
-//   records  nRois x kRoiYuvRecWords see RoiYuvRec
+// by (axis, length), so a chroma axis shares the table of a luma axis of its length.  The arena has the same
+// tables behind a header and records of its own:
 constexpr int kRoiYuvRecWords = 24;
 constexpr uint32_t kRoiYuvMagic = 0x494f5931u;  // "IOY1"
 enum { kRoiNv12 = 0, kRoiI420 = 1 };            // iqo_hip.h IQO_ROI_NV12 / IQO_ROI_I420
