@@ -879,6 +879,103 @@ typedef struct {
 int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
                                 iqo_hip_roi_yuv_box_layout *out);
 
+/* ---- Boxes into destination rectangles (letterbox, pad to square, aspect-true crops), of both box families.
+ *
+ * Output i of a fit call is a dstW x dstH canvas.  Rectangle rects[i] = (x, y, w, h) = (ox, oy, iw, ih) of it
+ * holds, bit for bit, what the stretch call of the same plan gives for box i with (iw, ih) in place of (dstW,
+ * dstH): the resizer (w, h -> iw, ih) on the cropped image per channel; for NV12 / I420 Y (w, h -> iw, ih), U and V
+ * (w/2, h/2 -> iw, ih) and the integer matrix.  IQO_ROI_FLIP mirrors the columns inside the rectangle.  Every
+ * pixel outside the rectangle is the pad colour: pad[c] is the byte of channel c (packed), or pad[0 .. 2] are R, G,
+ * B in output space, stored through `order` as a pixel is, the fourth byte of a 4-byte pixel being 255 (YUV;
+ * pad[3] is not read).  The norm forms are byte * scale + bias of that canvas, pad included.  rects == NULL: every
+ * rectangle is the whole output (the stretch call's result); pad == NULL: zeros.  rects and pad are host memory,
+ * read during the call.
+ *
+ * The calls take the plans of their stretch twins (one plan serves both kinds of call; its table cache is keyed by
+ * (axis, source length, output length)) and their arguments, and reject what they reject with (iw, ih) for
+ * (dstW, dstH) -- Lanczos rows without a defined result, Linear above 2x (YUV: iw > w or ih > h), more than
+ * IQO_HIP_ROI_MAX_TAPS taps, a band row over IQO_HIP_ROI_LDS_BYTES, a capturing stream -- and, with
+ * IQO_HIP_EINVAL and the box in *badRoi, a rectangle that does not lie inside the output or has w or h below 1.
+ * The destination checks are the stretch calls'.  Every byte of every canvas is written exactly once: a band
+ * workgroup writes its rows of the rectangle and the pad columns left and right of them, and pad workgroups of
+ * the same launch write the rows above and below the rectangle, at most padRows rows each (see the layout query). */
+typedef struct { int x, y, w, h; } iqo_hip_roi_rect;
+int iqo_hip_resize_rois_fit_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                   size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt,
+                                   const uint8_t *dSrc, size_t dstSt, size_t dstRoiSt, uint8_t *dDst, void *stream,
+                                   int *badRoi, const iqo_hip_roi_rect *rects /* host */, const uint8_t pad[4]);
+int iqo_hip_resize_rois_fit_norm_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                        size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt,
+                                        const uint8_t *dSrc, const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt,
+                                        size_t dstRoiSt, void *dDst, void *stream, int *badRoi,
+                                        const iqo_hip_roi_rect *rects /* host */, const uint8_t pad[4]);
+int iqo_hip_resize_rois_yuv_fit_rgb_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                           size_t nFrames, size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV,
+                                           size_t srcFrameSt, const uint8_t *dY, const uint8_t *dUorUV,
+                                           const uint8_t *dV /* NULL for NV12 */, int standard, int channels,
+                                           const int *order, size_t dstSt, size_t dstRoiSt, uint8_t *dDst, void *stream,
+                                           int *badRoi, const iqo_hip_roi_rect *rects /* host */, const uint8_t pad[4]);
+int iqo_hip_resize_rois_yuv_fit_norm_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois /* host */,
+                                            size_t nFrames, size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV,
+                                            size_t srcFrameSt, const uint8_t *dY, const uint8_t *dUorUV,
+                                            const uint8_t *dV /* NULL for NV12 */, int standard,
+                                            const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt,
+                                            void *dDst, void *stream, int *badRoi,
+                                            const iqo_hip_roi_rect *rects /* host */, const uint8_t pad[4]);
+/* Host-only CPU twins: the fit arena walked in plain C++.  Same status codes and *badRoi. */
+int iqo_host_resize_rois_fit(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                             const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                             size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstRoiSt, uint8_t *dst,
+                             int *badRoi, const iqo_hip_roi_rect *rects, const uint8_t pad[4]);
+int iqo_host_resize_rois_fit_norm(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                                  const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                                  size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, size_t dstSt,
+                                  size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi,
+                                  const iqo_hip_roi_rect *rects, const uint8_t pad[4]);
+int iqo_host_resize_rois_yuv_fit_rgb(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                     const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                     size_t srcStY, size_t srcStUV, size_t srcFrameSt, const uint8_t *y,
+                                     const uint8_t *uOrUV, const uint8_t *v, int standard, int channels,
+                                     const int *order, size_t dstSt, size_t dstRoiSt, uint8_t *dst, int *badRoi,
+                                     const iqo_hip_roi_rect *rects, const uint8_t pad[4]);
+int iqo_host_resize_rois_yuv_fit_norm(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                      const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                      size_t srcStY, size_t srcStUV, size_t srcFrameSt, const uint8_t *y,
+                                      const uint8_t *uOrUV, const uint8_t *v, int standard, const iqo_hip_norm *norm,
+                                      size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi,
+                                      const iqo_hip_roi_rect *rects, const uint8_t pad[4]);
+/* The rectangle of a w x h box in a dstW x dstH output, by one pinned integer rule (64-bit; a caller maps
+ * detections back to the frame with these numbers).  IQO_FIT_STRETCH: the whole output.  Letterbox: if
+ * w*dstH >= h*dstW then iw = dstW and ih = max(1, (h*dstW + w/2) / w), otherwise ih = dstH and
+ * iw = max(1, (w*dstH + h/2) / h); centred (ox = (dstW - iw) / 2, oy = (dstH - ih) / 2, floored) or at the top
+ * left (ox = oy = 0).  IQO_HIP_EINVAL: an unknown mode, a null `out`, a zero size, w or h above 2^24, dstW or dstH
+ * above 2^20. */
+enum { IQO_FIT_STRETCH = 0, IQO_FIT_LETTERBOX = 1, IQO_FIT_LETTERBOX_TOPLEFT = 2 };
+int iqo_host_fit_rect(int mode, size_t w, size_t h, size_t dstW, size_t dstH, iqo_hip_roi_rect *out);
+/* Host-only: the arenas of fit calls on tightly packed frames (recordBytes: the fit formats'; workgroups: bands and
+ * pad workgroups), and what the layout decides for ONE box of w x h pixels going to rectangle *rect (NULL: the
+ * whole output) of a dstW x dstH canvas: `box` is what the stretch query reports for (w, h) -> (iw, ih). */
+int iqo_host_roi_fit_arena_stats(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                                 const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                 iqo_hip_roi_arena_stats *stats, int *badRoi, const iqo_hip_roi_rect *rects);
+int iqo_host_roi_yuv_fit_arena_stats(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                     const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                     iqo_hip_roi_arena_stats *stats, int *badRoi, const iqo_hip_roi_rect *rects);
+typedef struct {
+    iqo_hip_roi_box_layout box;
+    unsigned padAbove, padBelow;  /* pad workgroups above and below the rectangle: ceil(rows there / padRows) */
+    int padRows;                  /* canvas rows one pad workgroup writes, at most */
+} iqo_hip_roi_fit_box_layout;
+typedef struct {
+    iqo_hip_roi_yuv_box_layout box;
+    unsigned padAbove, padBelow;
+    int padRows;
+} iqo_hip_roi_yuv_fit_box_layout;
+int iqo_host_roi_fit_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
+                                const iqo_hip_roi_rect *rect, iqo_hip_roi_fit_box_layout *out);
+int iqo_host_roi_yuv_fit_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w,
+                                    size_t h, const iqo_hip_roi_rect *rect, iqo_hip_roi_yuv_fit_box_layout *out);
+
 /* Drop-in classes (iqo::LanczosResizer, AreaResizer, LinearResizer): how many objects this process constructed on the
  * HIP backend, and on the CPU backend (no gfx950 device) plus the resize() calls of HIP objects that fell back to the
  * CPU (a device failure, or a call the HIP path rejected).  IQO_REQUIRE_HIP=1 makes any CPU use abort;

@@ -21,6 +21,7 @@ __all__ = ["IqoError", "LanczosResizer", "AreaResizer", "LinearResizer", "Yuv420
            "SOURCE_ORDERS", "RoiResizer", "Roi", "RoiArenaStats", "host_resize_rois", "host_roi_arena_stats",
            "RoiBoxLayout", "host_roi_box_layout", "ROI_MAX_TAPS", "ROI_LDS_BYTES", "YuvRoiResizer", "ROI_LAYOUTS",
            "RoiYuvBoxLayout", "host_resize_rois_yuv", "host_roi_yuv_arena_stats", "host_roi_yuv_box_layout", "LaunchGrid",
+           "RoiRect", "FIT_MODES", "fit_rects", "host_roi_fit_box_layout", "host_roi_yuv_fit_box_layout",
            "host_launch_grid", "GRID_MAPS", "GRID_STRIDE_BLOCKS"]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -138,6 +139,25 @@ class RoiYuvBoxLayout(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_int), ("workgroups", ctypes.c_uint), ("ldsBytes", _c_sz), ("nYp", ctypes.c_int),
                 ("np", ctypes.c_int), ("pitchDw", ctypes.c_int), ("nYpC", ctypes.c_int), ("npC", ctypes.c_int),
                 ("pitchDwC", ctypes.c_int)]
+
+
+class RoiRect(ctypes.Structure):
+    """iqo_hip_roi_rect: the rectangle of an output a box goes to."""
+    _fields_ = [("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_int), ("h", ctypes.c_int)]
+
+
+class RoiFitBoxLayout(ctypes.Structure):
+    """iqo_hip_roi_fit_box_layout"""
+    _fields_ = [("box", RoiBoxLayout), ("padAbove", ctypes.c_uint), ("padBelow", ctypes.c_uint), ("padRows", ctypes.c_int)]
+
+
+class RoiYuvFitBoxLayout(ctypes.Structure):
+    """iqo_hip_roi_yuv_fit_box_layout"""
+    _fields_ = [("box", RoiYuvBoxLayout), ("padAbove", ctypes.c_uint), ("padBelow", ctypes.c_uint),
+                ("padRows", ctypes.c_int)]
+
+
+FIT_MODES = {"stretch": 0, "letterbox": 1, "letterbox-topleft": 2}  # IQO_FIT_*
 
 
 class IpcHandle(ctypes.Structure):
@@ -272,6 +292,20 @@ def lib():
     L.iqo_host_roi_yuv_arena_stats.argtypes = roi_host + [_c_sz, ctypes.POINTER(Roi), _c_sz, _c_sz, _c_sz,
                                                           ctypes.POINTER(RoiArenaStats), pi]
     L.iqo_host_roi_yuv_box_layout.argtypes = roi_host + [_c_sz, _c_sz, ctypes.POINTER(RoiYuvBoxLayout)]
+    # the fit entries: their stretch twins' arguments, then the rectangles and the pad colour
+    fit = [ctypes.POINTER(RoiRect), ctypes.POINTER(ctypes.c_ubyte)]
+    for name in ("hip_resize_rois_device", "hip_resize_rois_norm_device", "host_resize_rois", "host_resize_rois_norm",
+                 "hip_resize_rois_yuv_rgb_device", "hip_resize_rois_yuv_norm_device", "host_resize_rois_yuv_rgb",
+                 "host_resize_rois_yuv_norm"):
+        twin = name.replace("rois_yuv", "rois_yuv_fit") if "yuv" in name else name.replace("rois", "rois_fit")
+        getattr(L, "iqo_" + twin).argtypes = getattr(L, "iqo_" + name).argtypes + fit
+    L.iqo_host_roi_fit_arena_stats.argtypes = L.iqo_host_roi_arena_stats.argtypes + fit[:1]
+    L.iqo_host_roi_yuv_fit_arena_stats.argtypes = L.iqo_host_roi_yuv_arena_stats.argtypes + fit[:1]
+    L.iqo_host_fit_rect.argtypes = [ctypes.c_int, _c_sz, _c_sz, _c_sz, _c_sz, ctypes.POINTER(RoiRect)]
+    L.iqo_host_roi_fit_box_layout.argtypes = roi_host + [_c_sz, _c_sz, ctypes.POINTER(RoiRect),
+                                                         ctypes.POINTER(RoiFitBoxLayout)]
+    L.iqo_host_roi_yuv_fit_box_layout.argtypes = roi_host + [_c_sz, _c_sz, ctypes.POINTER(RoiRect),
+                                                             ctypes.POINTER(RoiYuvFitBoxLayout)]
     L.iqo_hip_copy_frames.argtypes = [_vp, ctypes.c_int, _c_sz, _vp, ctypes.c_int, _c_sz, _c_sz, _c_sz, _vp,
                                       ctypes.POINTER(ctypes.c_int)]
     L.iqo_hip_ipc_export.argtypes = [_vp, ctypes.POINTER(IpcHandle)]
@@ -540,6 +574,49 @@ def _check_rois(rc, bad, boxes, what, where=None):
         raise err
 
 
+def fit_rects(boxes, dstW, dstH, mode="letterbox"):
+    """iqo_host_fit_rect per box: the rectangles [(x, y, w, h)] of a dstW x dstH output that boxes (frame, x, y, w,
+    h[, flip]) go to with their aspect ratio kept ("letterbox": centred; "letterbox-topleft"; "stretch": the whole
+    output).  A point (px, py) of output i lies at x + (px - rx + 0.5) * w / rw - 0.5 of the frame (y alike)."""
+    if mode not in FIT_MODES:
+        raise IqoError("fit must be one of %s" % ", ".join(sorted(FIT_MODES)))
+    out, r = [], RoiRect()
+    for i, b in enumerate(boxes):
+        rc = lib().iqo_host_fit_rect(FIT_MODES[mode], max(int(b[3]), 0), max(int(b[4]), 0), dstW, dstH, ctypes.byref(r))
+        if rc != 0:
+            raise IqoError("fit_rects: box %d %s into %d x %d: %s (%d)" % (i, tuple(b), dstW, dstH,
+                                                                         lib().iqo_hip_strerror(rc).decode(), rc))
+        out.append((r.x, r.y, r.w, r.h))
+    return out
+
+
+def _fit_args(boxes, dstW, dstH, rects, fit, pad):
+    """() for a stretch call (no rects, no fit, pad 0), or the two trailing arguments of a fit entry.  A nonzero pad
+    alone selects the fit entry with no rectangles: the same output as the stretch call, by the fit arena and kernel."""
+    import operator
+    if rects is not None and fit is not None:
+        raise IqoError("give rects or fit, not both")
+    try:
+        pad = tuple(operator.index(v) for v in pad) if hasattr(pad, "__len__") else (operator.index(pad),) * 4
+    except TypeError:
+        raise IqoError("pad: an int or up to 4 ints, 0 .. 255")
+    if len(pad) > 4 or any(not 0 <= v <= 255 for v in pad):
+        raise IqoError("pad: an int or up to 4 ints, 0 .. 255")
+    if rects is None and fit is None and not any(pad):
+        return ()
+    if fit is not None:
+        if fit not in ("letterbox", "letterbox-topleft"):
+            raise IqoError("fit must be letterbox or letterbox-topleft")
+        rects = fit_rects(boxes, dstW, dstH, fit)
+    arr = None
+    if rects is not None:
+        rects = [tuple(int(v) for v in r) for r in rects]
+        if len(rects) != len(boxes) or any(len(r) != 4 for r in rects):
+            raise IqoError("rects: one (x, y, w, h) per box")
+        arr = (RoiRect * max(1, len(rects)))(*[RoiRect(*r) for r in rects])
+    return (arr, (ctypes.c_ubyte * 4)(*(pad + (0,) * (4 - len(pad)))))
+
+
 def _norm_of(C, scale, bias, order, code):
     order = tuple(range(C)) if order is None else tuple(int(c) for c in order)
     scale, bias = tuple(float(v) for v in scale), tuple(float(v) for v in bias)
@@ -577,23 +654,27 @@ def _host_roi_out_norm(C, scale, bias, order, dtype, N, dstH, dstW, out):
     return n, out
 
 
-def _host_arena_stats(entry, method, degree, variant, dstW, dstH, boxes, nFrames, frameW, frameH):
+def _host_arena_stats(entry, method, degree, variant, dstW, dstH, boxes, nFrames, frameW, frameH, rects=None, fit=None):
     m = _METHODS[method] if isinstance(method, str) else int(method)
     boxes = [tuple(b) for b in boxes]
     st, bad = RoiArenaStats(), ctypes.c_int(-1)
+    tail = _fit_args(boxes, dstW, dstH, rects, fit, 0)[:1]
+    if tail:
+        entry = entry.replace("_arena", "_fit_arena")
     rc = getattr(lib(), "iqo_" + entry)(m, degree, variant, dstW, dstH, len(boxes), _roi_array(boxes), nFrames, frameW,
-                                        frameH, ctypes.byref(st), ctypes.byref(bad))
+                                        frameH, ctypes.byref(st), ctypes.byref(bad), *tail)
     _check_rois(rc, bad, boxes, entry)
     return {"arena_bytes": st.arenaBytes, "x_tables": st.xTables, "y_tables": st.yTables, "workgroups": st.workgroups,
             "lds_bytes": st.ldsBytes, "record_bytes": st.recordBytes}
 
 
-def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=None, dtype=None, order=None, out=None):
+def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=None, dtype=None, order=None, out=None,
+                     rects=None, fit=None, pad=0):
     """iqo_host_resize_rois / iqo_host_resize_rois_norm on numpy arrays (no GPU): the CPU twin of
     RoiResizer.resize_rois and, with scale / bias, of resize_rois_normalized.  src: uint8 [F, H, W] or
     [F, H, W, C] (row and frame strides free, pixel bytes contiguous).  Returns uint8 [N, dstH, dstW(, C)], or
     [N, planes, dstH, dstW] of dtype "float32", "float16" (numpy arrays of that type) or "bfloat16" (uint16 bit
-    patterns)."""
+    patterns).  rects / fit / pad: the fit twins (iqo_host_resize_rois_fit / _fit_norm), as RoiResizer.resize_rois."""
     import numpy as np
     m = _METHODS[method] if isinstance(method, str) else int(method)
     if src.dtype != np.uint8 or src.ndim not in (3, 4):
@@ -604,27 +685,49 @@ def host_resize_rois(method, degree, dstW, dstH, src, boxes, scale=None, bias=No
     F, H, W = src.shape[:3]
     boxes = [tuple(b) for b in boxes]
     arr, bad, N = _roi_array(boxes), ctypes.c_int(-1), len(boxes)
+    tail = _fit_args(boxes, dstW, dstH, rects, fit, pad)
+    sfx = "_fit" if tail else ""
     head = (m, degree, C, dstW, dstH, N, arr, F, W, H, src.strides[1], src.strides[0], src.ctypes.data)
     if scale is None:
         out = _host_roi_out_u8((N, dstH, dstW) if src.ndim == 3 else (N, dstH, dstW, C), C, out)
         if N == 0:  # (numpy gives an empty array no usable strides)
             return out
-        rc = lib().iqo_host_resize_rois(*head, out.strides[1], out.strides[0], out.ctypes.data, ctypes.byref(bad))
+        rc = getattr(lib(), "iqo_host_resize_rois" + sfx)(*head, out.strides[1], out.strides[0], out.ctypes.data,
+                                                          ctypes.byref(bad), *tail)
         _check_rois(rc, bad, boxes, "host_resize_rois")
         return out
     n, out = _host_roi_out_norm(C, scale, bias, order, dtype, N, dstH, dstW, out)
     if N == 0:
         return out
-    rc = lib().iqo_host_resize_rois_norm(*head, ctypes.byref(n), out.strides[2], out.strides[1], out.strides[0],
-                                         out.ctypes.data, ctypes.byref(bad))
+    rc = getattr(lib(), "iqo_host_resize_rois%s_norm" % sfx)(*head, ctypes.byref(n), out.strides[2], out.strides[1],
+                                                             out.strides[0], out.ctypes.data, ctypes.byref(bad), *tail)
     _check_rois(rc, bad, boxes, "host_resize_rois")
     return out
 
 
-def host_roi_arena_stats(method, degree, dstW, dstH, channels, boxes, nFrames, frameW, frameH):
+def host_roi_arena_stats(method, degree, dstW, dstH, channels, boxes, nFrames, frameW, frameH, rects=None, fit=None):
     """iqo_host_roi_arena_stats: {"arena_bytes", "x_tables", "y_tables", "workgroups", "lds_bytes", "record_bytes"}
-    of the call's arena, without a GPU."""
-    return _host_arena_stats("host_roi_arena_stats", method, degree, channels, dstW, dstH, boxes, nFrames, frameW, frameH)
+    of the call's arena, without a GPU.  With rects or fit: of the fit call's (iqo_host_roi_fit_arena_stats)."""
+    return _host_arena_stats("host_roi_arena_stats", method, degree, channels, dstW, dstH, boxes, nFrames, frameW, frameH,
+                             rects, fit)
+
+
+def _fit_layout_dict(d, bl):
+    d.update({"pad_above": bl.padAbove, "pad_below": bl.padBelow, "pad_rows": bl.padRows})
+    return d
+
+
+def host_roi_fit_box_layout(method, degree, channels, dstW, dstH, w, h, rect=None):
+    """iqo_host_roi_fit_box_layout: host_roi_box_layout of (w, h) -> the rectangle's (iw, ih), and "pad_above",
+    "pad_below" (pad workgroups above and below rectangle (x, y, iw, ih); None: the whole output) and "pad_rows" (the
+    canvas rows one of them writes, at most)."""
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    bl, r = RoiFitBoxLayout(), None if rect is None else RoiRect(*[int(v) for v in rect])
+    rc = lib().iqo_host_roi_fit_box_layout(m, degree, channels, dstW, dstH, w, h, r, ctypes.byref(bl))
+    _check_rois(rc, ctypes.c_int(-1), (), "host_roi_fit_box_layout", " (box %d x %d into %s)" % (w, h, rect))
+    b = bl.box
+    return _fit_layout_dict({"rows": b.rows, "workgroups": b.workgroups, "lds_bytes": b.ldsBytes, "nYp": b.nYp, "NP": b.np,
+                             "pitchDw": b.pitchDw}, bl)
 
 
 def host_roi_box_layout(method, degree, channels, dstW, dstH, w, h):
@@ -662,11 +765,13 @@ def _rgb_order(order):
 
 
 def host_resize_rois_yuv(method, degree, dstW, dstH, src, boxes, frameW, frameH, layout="nv12", standard="bt709",
-                         order="rgb", scale=None, bias=None, dtype=None, planes=(0, 1, 2), out=None):
+                         order="rgb", scale=None, bias=None, dtype=None, planes=(0, 1, 2), out=None, rects=None, fit=None,
+                         pad=0):
     """iqo_host_resize_rois_yuv_rgb / _norm on numpy arrays (no GPU): the CPU twin of YuvRoiResizer.resize_rois_rgb
     and, with scale / bias, of resize_rois_normalized (`planes`: its order).  src: uint8 [F, frameW*frameH*3/2], the
     tight NV12 / I420 frames (unit byte stride; the frame stride is free).  Returns uint8 [N, dstH, dstW, 3|4], or
-    [N, planes, dstH, dstW] of "float32", "float16" or "bfloat16" (uint16 bit patterns)."""
+    [N, planes, dstH, dstW] of "float32", "float16" or "bfloat16" (uint16 bit patterns).  rects / fit / pad: the fit
+    twins (iqo_host_resize_rois_yuv_fit_rgb / _fit_norm), as YuvRoiResizer.resize_rois_rgb; pad is (R, G, B)."""
     import numpy as np
     m = _METHODS[method] if isinstance(method, str) else int(method)
     lay, cs = _roi_layout(layout), _standard(standard)
@@ -676,6 +781,8 @@ def host_resize_rois_yuv(method, degree, dstW, dstH, src, boxes, frameW, frameH,
         src = np.ascontiguousarray(src)
     boxes = [tuple(b) for b in boxes]
     arr, bad, N = _roi_array(boxes), ctypes.c_int(-1), len(boxes)
+    tail = _fit_args(boxes, dstW, dstH, rects, fit, pad)
+    sfx = "_fit" if tail else ""
     stY, stUV, y, u, v = _yuv_planes(layout, src.ctypes.data, frameW, frameH)
     head = (m, degree, lay, dstW, dstH, N, arr, src.shape[0], frameW, frameH, stY, stUV, src.strides[0], y, u, v, cs)
     if scale is None:
@@ -683,24 +790,36 @@ def host_resize_rois_yuv(method, degree, dstW, dstH, src, boxes, frameW, frameH,
         out = _host_roi_out_u8((N, dstH, dstW, C), C, out)
         if N == 0:
             return out
-        rc = lib().iqo_host_resize_rois_yuv_rgb(*head, C, o4, out.strides[1], out.strides[0], out.ctypes.data,
-                                                ctypes.byref(bad))
+        rc = getattr(lib(), "iqo_host_resize_rois_yuv%s_rgb" % sfx)(*head, C, o4, out.strides[1], out.strides[0],
+                                                                    out.ctypes.data, ctypes.byref(bad), *tail)
         _check_rois(rc, bad, boxes, "host_resize_rois_yuv")
         return out
     n, out = _host_roi_out_norm(3, scale, bias, planes, dtype, N, dstH, dstW, out)
     if N == 0:
         return out
-    rc = lib().iqo_host_resize_rois_yuv_norm(*head, ctypes.byref(n), out.strides[2], out.strides[1], out.strides[0],
-                                             out.ctypes.data, ctypes.byref(bad))
+    rc = getattr(lib(), "iqo_host_resize_rois_yuv%s_norm" % sfx)(*head, ctypes.byref(n), out.strides[2], out.strides[1],
+                                                                 out.strides[0], out.ctypes.data, ctypes.byref(bad), *tail)
     _check_rois(rc, bad, boxes, "host_resize_rois_yuv")
     return out
 
 
-def host_roi_yuv_arena_stats(method, degree, dstW, dstH, layout, boxes, nFrames, frameW, frameH):
+def host_roi_yuv_arena_stats(method, degree, dstW, dstH, layout, boxes, nFrames, frameW, frameH, rects=None, fit=None):
     """iqo_host_roi_yuv_arena_stats: host_roi_arena_stats of a YUV box call; "x_tables" / "y_tables" count every
     distinct table once, whether luma, chroma or both use it."""
     return _host_arena_stats("host_roi_yuv_arena_stats", method, degree, _roi_layout(layout), dstW, dstH, boxes, nFrames,
-                             frameW, frameH)
+                             frameW, frameH, rects, fit)
+
+
+def host_roi_yuv_fit_box_layout(method, degree, layout, dstW, dstH, w, h, rect=None):
+    """iqo_host_roi_yuv_fit_box_layout: host_roi_yuv_box_layout of (w, h) -> the rectangle's (iw, ih), and the pad
+    workgroups of host_roi_fit_box_layout."""
+    m = _METHODS[method] if isinstance(method, str) else int(method)
+    bl, r = RoiYuvFitBoxLayout(), None if rect is None else RoiRect(*[int(v) for v in rect])
+    rc = lib().iqo_host_roi_yuv_fit_box_layout(m, degree, _roi_layout(layout), dstW, dstH, w, h, r, ctypes.byref(bl))
+    _check_rois(rc, ctypes.c_int(-1), (), "host_roi_yuv_fit_box_layout", " (box %d x %d into %s)" % (w, h, rect))
+    b = bl.box
+    return _fit_layout_dict({"rows": b.rows, "workgroups": b.workgroups, "lds_bytes": b.ldsBytes, "nYp": b.nYp, "NP": b.np,
+                             "pitchDw": b.pitchDw, "nYpC": b.nYpC, "NPC": b.npC, "pitchDwC": b.pitchDwC}, bl)
 
 
 def host_roi_yuv_box_layout(method, degree, layout, dstW, dstH, w, h):
@@ -1163,10 +1282,13 @@ class RoiResizer(_RoiPlan):
             src = src.contiguous()
         return src
 
-    def resize_rois(self, src, boxes, out=None, stream=None):
+    def resize_rois(self, src, boxes, out=None, stream=None, rects=None, fit=None, pad=0):
         """boxes: a sequence of (frame, x, y, w, h) or (frame, x, y, w, h, flip).  Returns / fills out
         [N, dstH, dstW] (3-dimensional src) or [N, dstH, dstW, C]: a uint8 tensor on src's device with contiguous
-        pixels and non-overlapping rows and outputs."""
+        pixels and non-overlapping rows and outputs.
+        rects (one (x, y, w, h) of the output per box) or fit ("letterbox", "letterbox-topleft": fit_rects) sends
+        each box to a rectangle of its output, resized to the rectangle's size, and fills the rest with `pad` (an
+        int, or up to 4 channel bytes), in the same launch (iqo_hip_resize_rois_fit_device)."""
         import torch
         s = self._source(src)
         C, boxes = self.channels, [tuple(b) for b in boxes]
@@ -1174,19 +1296,21 @@ class RoiResizer(_RoiPlan):
         out = _roi_out_u8((N, self.dstH, self.dstW) if s.dim() == 3 else (N, self.dstH, self.dstW, C), C, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
-        bad = ctypes.c_int(-1)
-        rc = lib().iqo_hip_resize_rois_device(self._plan, N, _roi_array(boxes), s.shape[0], s.shape[2], s.shape[1],
-                                              s.stride(1), s.stride(0), _ptr(s), out.stride(1), out.stride(0),
-                                              _ptr(out), _stream_ptr(stream), ctypes.byref(bad))
+        bad, tail = ctypes.c_int(-1), _fit_args(boxes, self.dstW, self.dstH, rects, fit, pad)
+        entry = lib().iqo_hip_resize_rois_fit_device if tail else lib().iqo_hip_resize_rois_device
+        rc = entry(self._plan, N, _roi_array(boxes), s.shape[0], s.shape[2], s.shape[1], s.stride(1), s.stride(0), _ptr(s),
+                   out.stride(1), out.stride(0), _ptr(out), _stream_ptr(stream), ctypes.byref(bad), *tail)
         _check_rois(rc, bad, boxes, "resize_rois")
         return out
 
-    def resize_rois_normalized(self, src, boxes, scale, bias, dtype=None, order=None, out=None, stream=None):
+    def resize_rois_normalized(self, src, boxes, scale, bias, dtype=None, order=None, out=None, stream=None, rects=None,
+                               fit=None, pad=0):
         """As resize_rois, stored as the normalised planar tensor a model takes: [N, planes, dstH, dstW] of `dtype`
         (float32, float16 or bfloat16), plane p = float32(byte of channel order[p]) * scale[p] + bias[p], each
         operation rounded to float32, then rounded to `dtype`.  planes = len(order), or C with the identity order
         (channels 1: order (0, 0, 0) gives grey -> 3 planes).  `out` may be a strided view with unit column stride
-        and non-overlapping rows, planes and outputs."""
+        and non-overlapping rows, planes and outputs.  rects / fit / pad as resize_rois: the pad bytes are normalised
+        as pixels are."""
         import torch
         dtype, code = _out_code(dtype)
         s = self._source(src)
@@ -1196,11 +1320,11 @@ class RoiResizer(_RoiPlan):
         out = _roi_out_norm((N, planes, self.dstH, self.dstW), dtype, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
-        e, bad = out.element_size(), ctypes.c_int(-1)
-        rc = lib().iqo_hip_resize_rois_norm_device(self._plan, N, _roi_array(boxes), s.shape[0], s.shape[2], s.shape[1],
-                                                   s.stride(1), s.stride(0), _ptr(s), ctypes.byref(n),
-                                                   out.stride(2) * e, out.stride(1) * e, out.stride(0) * e, _ptr(out),
-                                                   _stream_ptr(stream), ctypes.byref(bad))
+        e, bad, tail = out.element_size(), ctypes.c_int(-1), _fit_args(boxes, self.dstW, self.dstH, rects, fit, pad)
+        entry = lib().iqo_hip_resize_rois_fit_norm_device if tail else lib().iqo_hip_resize_rois_norm_device
+        rc = entry(self._plan, N, _roi_array(boxes), s.shape[0], s.shape[2], s.shape[1], s.stride(1), s.stride(0), _ptr(s),
+                   ctypes.byref(n), out.stride(2) * e, out.stride(1) * e, out.stride(0) * e, _ptr(out),
+                   _stream_ptr(stream), ctypes.byref(bad), *tail)
         _check_rois(rc, bad, boxes, "resize_rois_normalized")
         return out
 
@@ -1232,24 +1356,30 @@ class YuvRoiResizer(_RoiPlan):
         return src, (src.shape[0], frameW, frameH, stY, stUV, src.stride(0), y, u, v)
 
     def resize_rois_rgb_device(self, boxes, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV,
-                               dstSt, dstRoiSt, dDst, standard="bt709", order="rgb", stream=None):
+                               dstSt, dstRoiSt, dDst, standard="bt709", order="rgb", stream=None, rects=None, fit=None,
+                               pad=0):
         """The raw form (iqo_hip_resize_rois_yuv_rgb_device) for planes that lie anywhere: device addresses (or
         tensors) of frame 0's planes, their row strides and the one frame stride, and the destination's strides, all
-        in bytes.  dV is None for NV12."""
+        in bytes.  dV is None for NV12.  rects / fit / pad as resize_rois_rgb."""
         boxes = [tuple(b) for b in boxes]
         C, o4 = _rgb_order(order)
-        bad = ctypes.c_int(-1)
-        rc = lib().iqo_hip_resize_rois_yuv_rgb_device(
+        bad, tail = ctypes.c_int(-1), _fit_args(boxes, self.dstW, self.dstH, rects, fit, pad)
+        entry = lib().iqo_hip_resize_rois_yuv_fit_rgb_device if tail else lib().iqo_hip_resize_rois_yuv_rgb_device
+        rc = entry(
             self._plan, len(boxes), _roi_array(boxes), nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, _ptr(dY),
             _ptr(dUorUV), None if dV is None else _ptr(dV), _standard(standard), C, o4, dstSt, dstRoiSt, _ptr(dDst),
-            _stream_ptr(stream), ctypes.byref(bad))
+            _stream_ptr(stream), ctypes.byref(bad), *tail)
         _check_rois(rc, bad, boxes, "resize_rois_rgb_device")
 
-    def resize_rois_rgb(self, src, boxes, frameW, frameH, standard="bt709", order="rgb", out=None, stream=None):
+    def resize_rois_rgb(self, src, boxes, frameW, frameH, standard="bt709", order="rgb", out=None, stream=None,
+                        rects=None, fit=None, pad=0):
         """src: uint8 [F, frameW*frameH*3/2] on the device, the tight frames resize_frames of the YUV resizers takes.
         boxes: (frame, x, y, w, h) or (frame, x, y, w, h, flip), all even.  Returns / fills out [N, dstH, dstW, C]
         uint8, C = 3 ("rgb", "bgr") or 4 ("rgba", "bgra"; alpha 255), with contiguous pixels and non-overlapping rows
-        and outputs."""
+        and outputs.
+        rects (one (x, y, w, h) of the output per box) or fit ("letterbox", "letterbox-topleft": fit_rects) sends
+        each box to a rectangle of its output, resized to the rectangle's size, and fills the rest with `pad` (an
+        int, or (R, G, B), stored through `order` as a pixel is), in the same launch."""
         import torch
         s, args = self._source(src, frameW, frameH)
         C, _ = _rgb_order(order)
@@ -1258,15 +1388,17 @@ class YuvRoiResizer(_RoiPlan):
         out = _roi_out_u8((N, self.dstH, self.dstW, C), C, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
-        self.resize_rois_rgb_device(boxes, *args, out.stride(1), out.stride(0), out, standard, order, stream)
+        self.resize_rois_rgb_device(boxes, *args, out.stride(1), out.stride(0), out, standard, order, stream, rects, fit,
+                                    pad)
         return out
 
     def resize_rois_normalized(self, src, boxes, frameW, frameH, scale, bias, standard="bt709", dtype=None,
-                               order=(0, 1, 2), out=None, stream=None):
+                               order=(0, 1, 2), out=None, stream=None, rects=None, fit=None, pad=0):
         """As resize_rois_rgb, stored as the normalised planar tensor a model takes: [N, planes, dstH, dstW] of `dtype`
         (float32, float16 or bfloat16), plane p = float32(byte order[p] of (R, G, B)) * scale[p] + bias[p], each
         operation rounded to float32, then rounded to `dtype`.  `out` may be a strided view with unit column stride
-        and non-overlapping rows, planes and outputs."""
+        and non-overlapping rows, planes and outputs.  rects / fit / pad as resize_rois_rgb (the letterboxed model
+        input in one launch): the pad bytes are normalised as pixels are."""
         import torch
         dtype, code = _out_code(dtype)
         s, args = self._source(src, frameW, frameH)
@@ -1276,11 +1408,10 @@ class YuvRoiResizer(_RoiPlan):
         out = _roi_out_norm((N, planes, self.dstH, self.dstW), dtype, s, out)
         if stream is None:
             stream = torch.cuda.current_stream(s.device)
-        e, bad = out.element_size(), ctypes.c_int(-1)
-        rc = lib().iqo_hip_resize_rois_yuv_norm_device(self._plan, N, _roi_array(boxes), *args, _standard(standard),
-                                                       ctypes.byref(n), out.stride(2) * e, out.stride(1) * e,
-                                                       out.stride(0) * e, _ptr(out), _stream_ptr(stream),
-                                                       ctypes.byref(bad))
+        e, bad, tail = out.element_size(), ctypes.c_int(-1), _fit_args(boxes, self.dstW, self.dstH, rects, fit, pad)
+        entry = lib().iqo_hip_resize_rois_yuv_fit_norm_device if tail else lib().iqo_hip_resize_rois_yuv_norm_device
+        rc = entry(self._plan, N, _roi_array(boxes), *args, _standard(standard), ctypes.byref(n), out.stride(2) * e,
+                   out.stride(1) * e, out.stride(0) * e, _ptr(out), _stream_ptr(stream), ctypes.byref(bad), *tail)
         _check_rois(rc, bad, boxes, "resize_rois_normalized")
         return out
 

@@ -3662,6 +3662,22 @@ bool roi_dst_dims_ok(size_t dstW, size_t dstH) { return dstW && dstH && dstW <= 
 
 const iqo_amd::RoiBox *roi_boxes(const iqo_hip_roi *rois) { return reinterpret_cast<const iqo_amd::RoiBox *>(rois); }
 
+// What a fit call brings beyond its stretch twin (nullptr in the calls below: a stretch call)
+struct RoiFit {
+    const iqo_hip_roi_rect *rects;  // nRois of them, or nullptr: the whole output
+    const uint8_t *pad;             // 4 bytes, or nullptr: zeros
+    const iqo_amd::RoiRect *rois() const { return reinterpret_cast<const iqo_amd::RoiRect *>(rects); }
+    void colour(uint8_t out[4]) const
+    {
+        for (int c = 0; c < 4; ++c)
+            out[c] = pad ? pad[c] : 0;
+    }
+};
+static_assert(sizeof(iqo_hip_roi_rect) == sizeof(iqo_amd::RoiRect), "iqo_hip_roi_rect is roi.hpp RoiRect");
+static_assert(IQO_FIT_STRETCH == iqo_amd::kFitStretch && IQO_FIT_LETTERBOX == iqo_amd::kFitLetterbox &&
+                  IQO_FIT_LETTERBOX_TOPLEFT == iqo_amd::kFitLetterboxTopLeft,
+              "iqo_hip.h fit modes are roi.hpp's");
+
 // The destination checks of both forms (norm == nullptr: interleaved bytes); fills *rn for the twin.
 int roi_check_dst(int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_norm *norm, bool isNorm,
                   size_t dstSt, size_t planeSt, size_t dstRoiSt, const void *dst, iqo_amd::RoiNorm *rn)
@@ -3833,7 +3849,7 @@ int roi_submit(RoiPlanCore *p, Fill fill, Launch launch, hipStream_t s)
 int host_rois(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois, const iqo_hip_roi *rois,
               size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *src,
               const iqo_hip_norm *norm, bool isNorm, size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst,
-              iqo_hip_roi_arena_stats *stats, int *badRoi)
+              iqo_hip_roi_arena_stats *stats, int *badRoi, const RoiFit *fit = nullptr)
 {
     int bad = -1;
     if (badRoi)
@@ -3854,15 +3870,24 @@ int host_rois(int method, unsigned degree, int channels, size_t dstW, size_t dst
     }
     iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
     iqo_amd::RoiLayout l;
-    const int st = iqo_amd::roi_layout(&cache, channels, nRois, roi_boxes(rois), nFrames, frameW, frameH, srcSt, srcFrameSt,
-                                       &l, &bad);
+    const int st = fit ? iqo_amd::roi_fit_layout(&cache, channels, nRois, roi_boxes(rois), fit->rois(), nFrames, frameW, frameH,
+                                                 srcSt, srcFrameSt, &l, &bad)
+                       : iqo_amd::roi_layout(&cache, channels, nRois, roi_boxes(rois), nFrames, frameW, frameH, srcSt, srcFrameSt,
+                                             &l, &bad);
     if (st != iqo_amd::kRoiOk)
         return roi_fail(st, bad, badRoi);
     if (stats) {
-        roi_stats(l, iqo_amd::kRoiRecWords, stats);
+        roi_stats(l, fit ? iqo_amd::kRoiFitRecWords : iqo_amd::kRoiRecWords, stats);
         return IQO_HIP_OK;
     }
     std::vector<uint32_t> arena(l.words);
+    if (fit) {
+        uint8_t pad[4];
+        fit->colour(pad);
+        iqo_amd::roi_fit_fill(cache, l, frameW, arena.data());
+        iqo_amd::roi_fit_walk(arena.data(), src, srcSt, dstSt, planeSt, dstRoiSt, dst, rn, pad);
+        return IQO_HIP_OK;
+    }
     iqo_amd::roi_fill(cache, l, frameW, arena.data());
     iqo_amd::roi_walk(arena.data(), src, srcSt, dstSt, planeSt, dstRoiSt, dst, rn);
     return IQO_HIP_OK;
@@ -3870,7 +3895,7 @@ int host_rois(int method, unsigned degree, int channels, size_t dstW, size_t dst
 
 int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
              size_t srcSt, size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, bool isNorm, size_t dstSt,
-             size_t planeSt, size_t dstRoiSt, void *dst, hipStream_t s, int *badRoi)
+             size_t planeSt, size_t dstRoiSt, void *dst, hipStream_t s, int *badRoi, const RoiFit *fit = nullptr)
 {
     if (badRoi)
         *badRoi = -1;
@@ -3883,14 +3908,22 @@ int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t 
     if (rc)
         return rc;
     int bad = -1;
-    const int st = iqo_amd::roi_layout(&p.cache, h->channels, nRois, roi_boxes(rois), nFrames, frameW, frameH, srcSt,
-                                       srcFrameSt, &p.layout, &bad);
+    const int st = fit ? iqo_amd::roi_fit_layout(&p.cache, h->channels, nRois, roi_boxes(rois), fit->rois(), nFrames, frameW,
+                                                 frameH, srcSt, srcFrameSt, &p.layout, &bad)
+                       : iqo_amd::roi_layout(&p.cache, h->channels, nRois, roi_boxes(rois), nFrames, frameW, frameH, srcSt,
+                                             srcFrameSt, &p.layout, &bad);
     if (st != iqo_amd::kRoiOk)
         return roi_fail(st, bad, badRoi);
     if (nRois == 0)
         return IQO_HIP_OK;
     return roi_submit(
-        &p, [&](uint32_t *words) { iqo_amd::roi_fill(p.cache, p.layout, frameW, words); },
+        &p,
+        [&](uint32_t *words) {
+            if (fit)
+                iqo_amd::roi_fit_fill(p.cache, p.layout, frameW, words);
+            else
+                iqo_amd::roi_fill(p.cache, p.layout, frameW, words);
+        },
         [&](const uint32_t *words) {
             iqo_amd::RoiDev d;
             d.arena = words;
@@ -3903,6 +3936,9 @@ int run_rois(iqo_hip_roi_plan *h, size_t nRois, const iqo_hip_roi *rois, size_t 
             d.channels = h->channels;
             d.groups = p.layout.groups;
             d.ldsBytes = p.layout.ldsBytes;
+            d.fit = fit != nullptr;
+            if (fit)
+                fit->colour(d.pad);
             const iqo_amd::NormDev n = norm_dev(rn, planeSt);
             return iqo_amd::launch_roi(d, isNorm ? &n : nullptr, s);
         },
@@ -3967,8 +4003,85 @@ int iqo_host_roi_arena_stats(int method, unsigned degree, int channels, size_t d
                      frameW * C * frameH, nullptr, nullptr, false, 0, 0, 0, nullptr, stats, badRoi);
 }
 
-int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
-                            iqo_hip_roi_box_layout *out)
+int iqo_hip_resize_rois_fit_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                   size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrc,
+                                   size_t dstSt, size_t dstRoiSt, uint8_t *dDst, void *stream, int *badRoi,
+                                   const iqo_hip_roi_rect *rects, const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    return run_rois(plan, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, dSrc, nullptr, false, dstSt, 0,
+                    dstRoiSt, dDst, static_cast<hipStream_t>(stream), badRoi, &fit);
+}
+
+int iqo_hip_resize_rois_fit_norm_device(iqo_hip_roi_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                        size_t frameW, size_t frameH, size_t srcSt, size_t srcFrameSt, const uint8_t *dSrc,
+                                        const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt,
+                                        void *dDst, void *stream, int *badRoi, const iqo_hip_roi_rect *rects,
+                                        const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    return run_rois(plan, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, dSrc, norm, true, dstSt, dstPlaneSt,
+                    dstRoiSt, dDst, static_cast<hipStream_t>(stream), badRoi, &fit);
+}
+
+int iqo_host_resize_rois_fit(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                             const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                             size_t srcFrameSt, const uint8_t *src, size_t dstSt, size_t dstRoiSt, uint8_t *dst, int *badRoi,
+                             const iqo_hip_roi_rect *rects, const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    return host_rois(method, degree, channels, dstW, dstH, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, src,
+                     nullptr, false, dstSt, 0, dstRoiSt, dst, nullptr, badRoi, &fit);
+}
+
+int iqo_host_resize_rois_fit_norm(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                                  const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcSt,
+                                  size_t srcFrameSt, const uint8_t *src, const iqo_hip_norm *norm, size_t dstSt,
+                                  size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi, const iqo_hip_roi_rect *rects,
+                                  const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    return host_rois(method, degree, channels, dstW, dstH, nRois, rois, nFrames, frameW, frameH, srcSt, srcFrameSt, src,
+                     norm, true, dstSt, dstPlaneSt, dstRoiSt, dst, nullptr, badRoi, &fit);
+}
+
+int iqo_host_roi_fit_arena_stats(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t nRois,
+                                 const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                 iqo_hip_roi_arena_stats *stats, int *badRoi, const iqo_hip_roi_rect *rects)
+{
+    if (!stats)
+        return IQO_HIP_EINVAL;
+    const size_t C = channels > 0 ? static_cast<size_t>(channels) : 1;
+    const RoiFit fit = {rects, nullptr};
+    return host_rois(method, degree, channels, dstW, dstH, nRois, rois, nFrames, frameW, frameH, frameW * C,
+                     frameW * C * frameH, nullptr, nullptr, false, 0, 0, 0, nullptr, stats, badRoi, &fit);
+}
+
+int iqo_host_fit_rect(int mode, size_t w, size_t h, size_t dstW, size_t dstH, iqo_hip_roi_rect *out)
+{
+    iqo_amd::RoiRect r;
+    if (!out || !iqo_amd::fit_rect(mode, w, h, dstW, dstH, &r))
+        return IQO_HIP_EINVAL;
+    *out = iqo_hip_roi_rect{r.x, r.y, r.w, r.h};
+    return IQO_HIP_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+// The pad words of a one-box fit layout's record
+template <typename Out>
+void fit_box_pads(const uint32_t *ext, Out *out)
+{
+    out->padAbove = ext[iqo_amd::kFPadAbove];
+    out->padBelow = ext[iqo_amd::kFPadBelow];
+    out->padRows = iqo_amd::kRoiPadRows;
+}
+
+// iqo_host_roi_box_layout (fit == nullptr) and iqo_host_roi_fit_box_layout (*pads: its pad words)
+int roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h, const RoiFit *fit,
+                   iqo_hip_roi_box_layout *out, iqo_hip_roi_fit_box_layout *pads)
 {
     if (!out || method < 0 || method > 2 || !roi_dst_dims_ok(dstW, dstH) || !w || !h || w > (1u << 24) || h > (1u << 24))
         return IQO_HIP_EINVAL;
@@ -3978,9 +4091,12 @@ int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t ds
     iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
     iqo_amd::RoiLayout l;
     int bad = -1;
-    const int st = iqo_amd::roi_layout(&cache, channels, 1, &box, 1, w, h, w * C, w * C * h, &l, &bad);
+    const int st = fit ? iqo_amd::roi_fit_layout(&cache, channels, 1, &box, fit->rois(), 1, w, h, w * C, w * C * h, &l, &bad)
+                       : iqo_amd::roi_layout(&cache, channels, 1, &box, 1, w, h, w * C, w * C * h, &l, &bad);
     if (st != iqo_amd::kRoiOk)
         return roi_status(st);
+    if (fit)
+        fit_box_pads(l.rec.data() + iqo_amd::kRoiFitExt, pads);
     const uint32_t *xt = l.tables[static_cast<size_t>(l.xIdx[0].second)].first->data();
     const uint32_t *yt = l.tables[static_cast<size_t>(l.yIdx[0].second)].first->data();
     out->rows = static_cast<int>(l.rec[iqo_amd::kRRows]);
@@ -3990,6 +4106,23 @@ int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t ds
     out->np = static_cast<int>(xt[0]);
     out->pitchDw = static_cast<int>(l.rec[iqo_amd::kRPitch]);
     return IQO_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int iqo_host_roi_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
+                            iqo_hip_roi_box_layout *out)
+{
+    return roi_box_layout(method, degree, channels, dstW, dstH, w, h, nullptr, out, nullptr);
+}
+
+int iqo_host_roi_fit_box_layout(int method, unsigned degree, int channels, size_t dstW, size_t dstH, size_t w, size_t h,
+                                const iqo_hip_roi_rect *rect, iqo_hip_roi_fit_box_layout *out)
+{
+    const RoiFit fit = {rect, nullptr};
+    return roi_box_layout(method, degree, channels, dstW, dstH, w, h, &fit, out ? &out->box : nullptr, out);
 }
 
 } // extern "C"
@@ -4010,6 +4143,7 @@ struct RoiYuvCall {
     bool isNorm;
     size_t dstSt, planeSt, dstRoiSt;
     void *dst;
+    const RoiFit *fit;         // nullptr: a stretch call
 };
 
 // The checks of a call's own arguments that roi_yuv_layout does not make; fills *src and *out.
@@ -4067,14 +4201,22 @@ int host_rois_yuv(int method, unsigned degree, int layout, size_t dstW, size_t d
         return rc;
     iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
     iqo_amd::RoiLayout l;
-    const int st = iqo_amd::roi_yuv_layout(&cache, src, c.nRois, roi_boxes(c.rois), &l, &bad);
+    const int st = c.fit ? iqo_amd::roi_yuv_fit_layout(&cache, src, c.nRois, roi_boxes(c.rois), c.fit->rois(), &l, &bad)
+                         : iqo_amd::roi_yuv_layout(&cache, src, c.nRois, roi_boxes(c.rois), &l, &bad);
     if (st != iqo_amd::kRoiOk)
         return roi_fail(st, bad, badRoi);
     if (stats) {
-        roi_stats(l, iqo_amd::kRoiYuvRecWords, stats);
+        roi_stats(l, c.fit ? iqo_amd::kRoiYuvFitRecWords : iqo_amd::kRoiYuvRecWords, stats);
         return IQO_HIP_OK;
     }
     std::vector<uint32_t> arena(l.words);
+    if (c.fit) {
+        uint8_t pad[4];
+        c.fit->colour(pad);
+        iqo_amd::roi_yuv_fit_fill(cache, l, src, arena.data());
+        iqo_amd::roi_yuv_fit_walk(arena.data(), c.y, c.u, c.v, out, c.dstSt, c.planeSt, c.dstRoiSt, c.dst, pad);
+        return IQO_HIP_OK;
+    }
     iqo_amd::roi_yuv_fill(cache, l, src, arena.data());
     iqo_amd::roi_yuv_walk(arena.data(), c.y, c.u, c.v, out, c.dstSt, c.planeSt, c.dstRoiSt, c.dst);
     return IQO_HIP_OK;
@@ -4094,13 +4236,20 @@ int run_rois_yuv(iqo_hip_roi_yuv_plan *h, const RoiYuvCall &c, hipStream_t s, in
     if (rc)
         return rc;
     int bad = -1;
-    const int st = iqo_amd::roi_yuv_layout(&p.cache, src, c.nRois, roi_boxes(c.rois), &p.layout, &bad);
+    const int st = c.fit ? iqo_amd::roi_yuv_fit_layout(&p.cache, src, c.nRois, roi_boxes(c.rois), c.fit->rois(), &p.layout, &bad)
+                         : iqo_amd::roi_yuv_layout(&p.cache, src, c.nRois, roi_boxes(c.rois), &p.layout, &bad);
     if (st != iqo_amd::kRoiOk)
         return roi_fail(st, bad, badRoi);
     if (c.nRois == 0)
         return IQO_HIP_OK;
     return roi_submit(
-        &p, [&](uint32_t *words) { iqo_amd::roi_yuv_fill(p.cache, p.layout, src, words); },
+        &p,
+        [&](uint32_t *words) {
+            if (c.fit)
+                iqo_amd::roi_yuv_fit_fill(p.cache, p.layout, src, words);
+            else
+                iqo_amd::roi_yuv_fill(p.cache, p.layout, src, words);
+        },
         [&](const uint32_t *words) {
             iqo_amd::RoiYuvDev d;
             d.arena = words;
@@ -4118,6 +4267,9 @@ int run_rois_yuv(iqo_hip_roi_yuv_plan *h, const RoiYuvCall &c, hipStream_t s, in
                 d.order[i] = out.order[i];
             d.groups = p.layout.groups;
             d.ldsBytes = p.layout.ldsBytes;
+            d.fit = c.fit != nullptr;
+            if (c.fit)
+                c.fit->colour(d.pad);
             const iqo_amd::NormDev n = norm_dev(out.n, c.planeSt);
             return iqo_amd::launch_roi_yuv(d, c.isNorm ? &n : nullptr, s);
         },
@@ -4144,7 +4296,7 @@ int iqo_hip_resize_rois_yuv_rgb_device(iqo_hip_roi_yuv_plan *plan, size_t nRois,
                                        void *stream, int *badRoi)
 {
     const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV, standard,
-                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dDst};
+                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dDst, nullptr};
     return run_rois_yuv(plan, c, static_cast<hipStream_t>(stream), badRoi);
 }
 
@@ -4155,7 +4307,7 @@ int iqo_hip_resize_rois_yuv_norm_device(iqo_hip_roi_yuv_plan *plan, size_t nRois
                                         void *dDst, void *stream, int *badRoi)
 {
     const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV, standard,
-                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dDst};
+                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dDst, nullptr};
     return run_rois_yuv(plan, c, static_cast<hipStream_t>(stream), badRoi);
 }
 
@@ -4166,7 +4318,7 @@ int iqo_host_resize_rois_yuv_rgb(int method, unsigned degree, int layout, size_t
                                  size_t dstRoiSt, uint8_t *dst, int *badRoi)
 {
     const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, y, uOrUV, v, standard,
-                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dst};
+                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dst, nullptr};
     return host_rois_yuv(method, degree, layout, dstW, dstH, c, nullptr, badRoi);
 }
 
@@ -4177,7 +4329,7 @@ int iqo_host_resize_rois_yuv_norm(int method, unsigned degree, int layout, size_
                                   size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi)
 {
     const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, y, uOrUV, v, standard,
-                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dst};
+                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dst, nullptr};
     return host_rois_yuv(method, degree, layout, dstW, dstH, c, nullptr, badRoi);
 }
 
@@ -4190,12 +4342,81 @@ int iqo_host_roi_yuv_arena_stats(int method, unsigned degree, int layout, size_t
     const size_t stUV = layout == IQO_ROI_NV12 ? frameW : frameW / 2;
     // (no planes and no destination: tightly packed frames, and the output form plays no part in the arena)
     const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, frameW, stUV, frameW * frameH * 3 / 2, nullptr, nullptr,
-                          nullptr, 0, 3, nullptr, nullptr, true, 0, 0, 0, nullptr};
+                          nullptr, 0, 3, nullptr, nullptr, true, 0, 0, 0, nullptr, nullptr};
     return host_rois_yuv(method, degree, layout, dstW, dstH, c, stats, badRoi);
 }
 
-int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
-                                iqo_hip_roi_yuv_box_layout *out)
+int iqo_hip_resize_rois_yuv_fit_rgb_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                           size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                                           const uint8_t *dY, const uint8_t *dUorUV, const uint8_t *dV, int standard,
+                                           int channels, const int *order, size_t dstSt, size_t dstRoiSt, uint8_t *dDst,
+                                           void *stream, int *badRoi, const iqo_hip_roi_rect *rects, const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV, standard,
+                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dDst, &fit};
+    return run_rois_yuv(plan, c, static_cast<hipStream_t>(stream), badRoi);
+}
+
+int iqo_hip_resize_rois_yuv_fit_norm_device(iqo_hip_roi_yuv_plan *plan, size_t nRois, const iqo_hip_roi *rois, size_t nFrames,
+                                            size_t frameW, size_t frameH, size_t srcStY, size_t srcStUV, size_t srcFrameSt,
+                                            const uint8_t *dY, const uint8_t *dUorUV, const uint8_t *dV, int standard,
+                                            const iqo_hip_norm *norm, size_t dstSt, size_t dstPlaneSt, size_t dstRoiSt,
+                                            void *dDst, void *stream, int *badRoi, const iqo_hip_roi_rect *rects,
+                                            const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, dY, dUorUV, dV, standard,
+                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dDst, &fit};
+    return run_rois_yuv(plan, c, static_cast<hipStream_t>(stream), badRoi);
+}
+
+int iqo_host_resize_rois_yuv_fit_rgb(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                     const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcStY,
+                                     size_t srcStUV, size_t srcFrameSt, const uint8_t *y, const uint8_t *uOrUV,
+                                     const uint8_t *v, int standard, int channels, const int *order, size_t dstSt,
+                                     size_t dstRoiSt, uint8_t *dst, int *badRoi, const iqo_hip_roi_rect *rects,
+                                     const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, y, uOrUV, v, standard,
+                          channels, order, nullptr, false, dstSt, 0, dstRoiSt, dst, &fit};
+    return host_rois_yuv(method, degree, layout, dstW, dstH, c, nullptr, badRoi);
+}
+
+int iqo_host_resize_rois_yuv_fit_norm(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                      const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH, size_t srcStY,
+                                      size_t srcStUV, size_t srcFrameSt, const uint8_t *y, const uint8_t *uOrUV,
+                                      const uint8_t *v, int standard, const iqo_hip_norm *norm, size_t dstSt,
+                                      size_t dstPlaneSt, size_t dstRoiSt, void *dst, int *badRoi,
+                                      const iqo_hip_roi_rect *rects, const uint8_t pad[4])
+{
+    const RoiFit fit = {rects, pad};
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, srcStY, srcStUV, srcFrameSt, y, uOrUV, v, standard,
+                          3, nullptr, norm, true, dstSt, dstPlaneSt, dstRoiSt, dst, &fit};
+    return host_rois_yuv(method, degree, layout, dstW, dstH, c, nullptr, badRoi);
+}
+
+int iqo_host_roi_yuv_fit_arena_stats(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t nRois,
+                                     const iqo_hip_roi *rois, size_t nFrames, size_t frameW, size_t frameH,
+                                     iqo_hip_roi_arena_stats *stats, int *badRoi, const iqo_hip_roi_rect *rects)
+{
+    if (!stats)
+        return IQO_HIP_EINVAL;
+    const size_t stUV = layout == IQO_ROI_NV12 ? frameW : frameW / 2;
+    const RoiFit fit = {rects, nullptr};
+    const RoiYuvCall c = {nRois, rois, nFrames, frameW, frameH, frameW, stUV, frameW * frameH * 3 / 2, nullptr, nullptr,
+                          nullptr, 0, 3, nullptr, nullptr, true, 0, 0, 0, nullptr, &fit};
+    return host_rois_yuv(method, degree, layout, dstW, dstH, c, stats, badRoi);
+}
+
+} // extern "C"
+
+namespace {
+
+// iqo_host_roi_yuv_box_layout (fit == nullptr) and iqo_host_roi_yuv_fit_box_layout (*pads: its pad words)
+int roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h, const RoiFit *fit,
+                       iqo_hip_roi_yuv_box_layout *out, iqo_hip_roi_yuv_fit_box_layout *pads)
 {
     if (!out || method < 0 || method > 2 || !roi_dst_dims_ok(dstW, dstH) || !w || !h || w > (1u << 24) || h > (1u << 24))
         return IQO_HIP_EINVAL;
@@ -4211,10 +4432,13 @@ int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t 
     iqo_amd::RoiTableCache cache(static_cast<iqo_amd::Method>(method), degree, static_cast<int>(dstW), static_cast<int>(dstH));
     iqo_amd::RoiLayout l;
     int bad = -1;
-    const int st = iqo_amd::roi_yuv_layout(&cache, src, 1, &box, &l, &bad);
+    const int st = fit ? iqo_amd::roi_yuv_fit_layout(&cache, src, 1, &box, fit->rois(), &l, &bad)
+                       : iqo_amd::roi_yuv_layout(&cache, src, 1, &box, &l, &bad);
     if (st != iqo_amd::kRoiOk)
         return roi_status(st);
     const uint32_t *r = l.rec.data();
+    if (fit)
+        fit_box_pads(r + iqo_amd::kRoiYuvFitExt, pads);
     auto tab = [&](int word) {  // the table at arena word offset r[word]
         for (const auto &t : l.tables)
             if (t.second == r[word])
@@ -4231,6 +4455,23 @@ int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t 
     out->npC = static_cast<int>(tab(iqo_amd::kYXTabC)[0]);
     out->pitchDwC = static_cast<int>(r[iqo_amd::kYPitchC]);
     return IQO_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int iqo_host_roi_yuv_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
+                                iqo_hip_roi_yuv_box_layout *out)
+{
+    return roi_yuv_box_layout(method, degree, layout, dstW, dstH, w, h, nullptr, out, nullptr);
+}
+
+int iqo_host_roi_yuv_fit_box_layout(int method, unsigned degree, int layout, size_t dstW, size_t dstH, size_t w, size_t h,
+                                    const iqo_hip_roi_rect *rect, iqo_hip_roi_yuv_fit_box_layout *out)
+{
+    const RoiFit fit = {rect, nullptr};
+    return roi_yuv_box_layout(method, degree, layout, dstW, dstH, w, h, &fit, out ? &out->box : nullptr, out);
 }
 
 } // extern "C"

@@ -188,6 +188,8 @@ struct RoiDev {
     int channels;                // 1, 3 or 4
     unsigned groups;             // the arena's workgroup count
     size_t ldsBytes;             // the largest workgroup's LDS (roi.hpp RoiLayout)
+    bool fit = false;            // the arena is the fit format (roi_fit_kernel), and
+    uint8_t pad[4] = {0, 0, 0, 0};  // the pad colour: byte c of a pixel
 };
 hipError_t launch_roi(const RoiDev &d, const NormDev *norm, hipStream_t s);
 
@@ -205,6 +207,8 @@ struct RoiYuvDev {
     int channels, order[4];
     unsigned groups;
     size_t ldsBytes;
+    bool fit = false;            // the arena is the fit format (roi_yuv_fit_kernel), and
+    uint8_t pad[4] = {0, 0, 0, 0};  // the pad colour: R, G, B
 };
 hipError_t launch_roi_yuv(const RoiYuvDev &d, const NormDev *norm, hipStream_t s);
 

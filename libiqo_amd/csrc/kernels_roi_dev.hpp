@@ -249,6 +249,99 @@ __device__ __forceinline__ void roi_store_norm(const NormDev &n, int p, uint32_t
         reinterpret_cast<uint16_t *>(e)[xo] = static_cast<uint16_t>(n.dtype == 2 ? f16_bits(f) : bf16_bits(f));
 }
 
+// ---------------------------------------------------------------- the fit kernels' pad stores
+//
+// A pad run is a row of equal pixels (U8, 1, 3 or 4 bytes) or equal elements (fp32 / fp16 / bf16) that begins on
+// a pixel: its byte k is byte k % period of the pixel.  The pattern is the run's first 8 bytes as one 64-bit value,
+// uniform over the workgroup, so the 4 bytes at any k are a shift of it by k % period bytes (at most 3): plain
+// register arithmetic, no table.
+struct RoiPadPat {
+    uint64_t d;  // bytes 0 .. 7 of a run
+    int period;  // 1 .. 4
+};
+
+// The pattern of a pixel or element of `period` bytes (1 .. 4), the low bytes of px
+__device__ __forceinline__ RoiPadPat roi_pad_pattern(uint32_t px, int period)
+{
+    uint64_t d;
+    if (period == 3) {
+        const uint64_t p = px & 0xffffffu;
+        d = p | (p << 24) | (p << 48);
+    } else {
+        const uint32_t w = period == 1 ? (px & 0xffu) * 0x01010101u : period == 2 ? (px & 0xffffu) * 0x00010001u : px;
+        d = w | (static_cast<uint64_t>(w) << 32);
+    }
+    return RoiPadPat{d, period};
+}
+
+// ... of plane p of the float epilogue: the element roi_store_norm stores for byte v
+__device__ __forceinline__ RoiPadPat roi_pad_pattern_norm(const NormDev &n, int p, uint32_t v)
+{
+    const float f = norm_affine(v, n.scale[p], n.bias[p]);
+    if (n.dtype == 1)
+        return roi_pad_pattern(__float_as_uint(f), 4);
+    return roi_pad_pattern(static_cast<uint32_t>(n.dtype == 2 ? f16_bits(f) : bf16_bits(f)) & 0xffffu, 2);
+}
+
+// nRows pad runs of nBytes each, rowSt apart from `base`, by the whole workgroup.  A task is one 16-byte aligned
+// slot of one row: a slot wholly inside the run is one 16-byte store (a 3-byte pixel so sees a 48-byte pattern
+// rotate through three slots), the two slots at a run's misaligned ends are stores of `unit` bytes (1: bytes; 2, 4: the
+// element size, which base, rowSt and nBytes are multiples of).  Every byte of the runs is stored once, and no other.
+__device__ __forceinline__ void roi_pad_rows(uint8_t *base, int64_t rowSt, int nRows, int nBytes, RoiPadPat pat, int unit,
+                                             int tid)
+{
+    if (nRows <= 0 || nBytes <= 0)
+        return;
+    const uint64_t d = pat.d;
+    const int period = pat.period;
+    // bytes [k, k + 4) of the run, k >= 0
+    auto word = [=](int k) {
+        const int r = period == 3 ? k % 3 : k & (period - 1);
+        return static_cast<uint32_t>(d >> (8 * r));
+    };
+    const int nSlots = ((nBytes + 15) >> 4) + 1;
+    for (int t = tid; t < nRows * nSlots; t += 256) {
+        const int j = t / nSlots, s = t - j * nSlots;
+        uint8_t *const p = base + j * rowSt;
+        const int b0 = 16 * s - static_cast<int>(reinterpret_cast<uintptr_t>(p) & 15);  // the slot's first run byte
+        const int lo = max(b0, 0), hi = min(b0 + 16, nBytes);
+        if (hi - lo == 16) {
+            *reinterpret_cast<uint4 *>(p + b0) = make_uint4(word(b0), word(b0 + 4), word(b0 + 8), word(b0 + 12));
+        } else {
+            for (int k = lo; k < hi; k += unit) {
+                const uint32_t v = word(k);
+                if (unit == 4)
+                    *reinterpret_cast<uint32_t *>(p + k) = v;
+                else if (unit == 2)
+                    *reinterpret_cast<uint16_t *>(p + k) = static_cast<uint16_t>(v);
+                else
+                    p[k] = static_cast<uint8_t>(v);
+            }
+        }
+    }
+}
+
+// What a fit workgroup is to its box, from the fit words `ext` of the box's record (roi.hpp RoiFitRec): a band
+// (true: *y0 is its first row of the rectangle), or a pad workgroup above or below the rectangle (false: it writes
+// canvas rows [*y0, *y1)).  k: the workgroup's number within its box; g: the box's bands of `rows` rows.
+__device__ __forceinline__ bool roi_fit_role(const uint32_t *ext, int k, int g, int rows, int dstH, int *y0, int *y1)
+{
+    const int above = sld(ext, kFPadAbove), oy = sld(ext, kFOY), ih = sld(ext, kFIH);
+    if (k < above) {
+        *y0 = k * kRoiPadRows;
+        *y1 = min(*y0 + kRoiPadRows, oy);
+        return false;
+    }
+    if (k >= above + g) {
+        *y0 = oy + ih + (k - above - g) * kRoiPadRows;
+        *y1 = min(*y0 + kRoiPadRows, dstH);
+        return false;
+    }
+    *y0 = (k - above) * rows;
+    *y1 = min(*y0 + rows, ih);
+    return true;
+}
+
 // Launches `kern` over the arena's workgroups on its Args slice of `a`, or with `norm` on the whole of it.
 template <typename Args, typename NormArgs>
 hipError_t roi_launch(const void *kern, NormArgs &a, const NormDev *norm, unsigned groups, size_t ldsBytes, hipStream_t s)

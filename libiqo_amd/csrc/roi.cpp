@@ -76,15 +76,17 @@ std::vector<uint32_t> build_roi_table(Method m, unsigned degree, int srcLen, int
 
 } // namespace
 
-RoiTableCache::Table RoiTableCache::get(bool isX, int srcLen, int *why)
+RoiTableCache::Table RoiTableCache::get(bool isX, int srcLen, int dstLen, int *why)
 {
-    const uint64_t key = (static_cast<uint64_t>(isX) << 32) | static_cast<uint32_t>(srcLen);
+    // (srcLen <= 2^24, dstLen <= 2^20)
+    const uint64_t key = (static_cast<uint64_t>(isX) << 63) | (static_cast<uint64_t>(static_cast<uint32_t>(srcLen)) << 32) |
+                         static_cast<uint32_t>(dstLen);
     auto it = map_.find(key);
     if (it != map_.end()) {
         lru_.splice(lru_.begin(), lru_, it->second);
         return it->second->t;
     }
-    std::vector<uint32_t> t = build_roi_table(m_, degree_, srcLen, isX ? dstW_ : dstH_, isX, why);
+    std::vector<uint32_t> t = build_roi_table(m_, degree_, srcLen, dstLen, isX, why);
     if (t.empty())
         return nullptr;
     ++misses_;
@@ -127,19 +129,20 @@ struct TableRef {
     uint32_t off = 0;             // its word offset in the arena
 };
 
-// The table of (axis, len) in the layout, appended at *words (from the cache) where the call has none yet.
-TableRef table_for(RoiTableCache *cache, RoiLayout *l, bool isX, int len, size_t *words, int *status)
+// The table of (axis, len -> dstLen) in the layout, appended at *words (from the cache) where the call has none yet.
+TableRef table_for(RoiTableCache *cache, RoiLayout *l, bool isX, int len, int dstLen, size_t *words, int *status)
 {
-    std::vector<std::pair<int, int>> &idx = isX ? l->xIdx : l->yIdx;
-    auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(len, 0));
-    if (it == idx.end() || it->first != len) {
+    std::vector<std::pair<uint64_t, int>> &idx = isX ? l->xIdx : l->yIdx;
+    const uint64_t key = (static_cast<uint64_t>(static_cast<uint32_t>(len)) << 32) | static_cast<uint32_t>(dstLen);
+    auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(key, 0));
+    if (it == idx.end() || it->first != key) {
         int why = 0;
-        RoiTableCache::Table t = cache->get(isX, len, &why);
+        RoiTableCache::Table t = cache->get(isX, len, dstLen, &why);
         if (!t) {
             *status = why ? kRoiUnsupported : kRoiInvalid;
             return TableRef();
         }
-        it = idx.insert(it, std::make_pair(len, static_cast<int>(l->tables.size())));
+        it = idx.insert(it, std::make_pair(key, static_cast<int>(l->tables.size())));
         l->tables.emplace_back(t, static_cast<uint32_t>(*words));
         *words += t->size();
         ++(isX ? l->nXTables : l->nYTables);
@@ -172,7 +175,30 @@ int band_rows(int dstH, size_t rowBytes, size_t *ldsBytes)
 // more boxes than one grid (or one arena) can address
 bool over_caps(uint64_t groups, size_t words) { return groups >= (uint64_t(1) << 31) || words >= (size_t(1) << 30); }
 
-// The header words both formats share, the records and the tables.
+// The destination rectangle of box i: the whole output in a stretch call and where a fit call brings no
+// rectangles.  false: it does not lie inside the output, or is less than a pixel wide or high.
+bool rect_of(const RoiRect *rects, size_t i, int dstW, int dstH, RoiRect *r)
+{
+    *r = rects ? rects[i] : RoiRect{0, 0, dstW, dstH};
+    return r->w >= 1 && r->h >= 1 && r->x >= 0 && r->y >= 0 && r->x <= dstW - r->w && r->y <= dstH - r->h;
+}
+
+// The fit words of a record (roi.hpp RoiFitRec) whose box has g bands; returns all its workgroups: the pad
+// workgroups above the rectangle, the bands, the pad workgroups below it.
+uint64_t fit_words(uint32_t *ext, const RoiRect &r, int dstH, uint32_t g)
+{
+    const uint32_t above = static_cast<uint32_t>((r.y + kRoiPadRows - 1) / kRoiPadRows);
+    const uint32_t below = static_cast<uint32_t>((dstH - r.y - r.h + kRoiPadRows - 1) / kRoiPadRows);
+    ext[kFIW] = static_cast<uint32_t>(r.w);
+    ext[kFIH] = static_cast<uint32_t>(r.h);
+    ext[kFOX] = static_cast<uint32_t>(r.x);
+    ext[kFOY] = static_cast<uint32_t>(r.y);
+    ext[kFPadAbove] = above;
+    ext[kFPadBelow] = below;
+    return static_cast<uint64_t>(above) + g + below;
+}
+
+// The header words all four formats share, the records and the tables.
 void fill_common(uint32_t magic, const RoiTableCache &cache, const RoiLayout &l, uint32_t *arena)
 {
     std::memset(arena, 0, kRoiHdrWords * 4);
@@ -190,11 +216,11 @@ void fill_common(uint32_t magic, const RoiTableCache &cache, const RoiLayout &l,
         std::memcpy(arena + t.second, t.first->data(), t.first->size() * 4);
 }
 
-} // namespace
-
-int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, size_t nFrames, size_t frameW,
-               size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad)
+// roi_layout (fit == false: every box to the whole output, stretch records) and roi_fit_layout
+int layout_packed(bool fit, RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, const RoiRect *rects,
+                  size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad)
 {
+    const size_t recWords = fit ? kRoiFitRecWords : kRoiRecWords;
     out->reset();
     *bad = -1;
     if (channels != 1 && channels != 3 && channels != 4)
@@ -210,18 +236,19 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
         return kRoiUnsupported;
     out->nRois = static_cast<int>(nRois);
     out->channels = channels;
-    out->rec.assign(nRois * kRoiRecWords, 0u);
-    size_t words = kRoiHdrWords + nRois * kRoiRecWords;
+    out->rec.assign(nRois * recWords, 0u);
+    size_t words = kRoiHdrWords + nRois * recWords;
     uint64_t groups = 0;
-    const int dstH = cache->dstH();
     for (size_t i = 0; i < nRois; ++i) {
         const RoiBox &b = rois[i];
         *bad = static_cast<int>(i);
-        if (!box_in_frame(b, nFrames, frameW, frameH))
+        RoiRect rc;
+        if (!box_in_frame(b, nFrames, frameW, frameH) || !rect_of(fit ? rects : nullptr, i, cache->dstW(), cache->dstH(), &rc))
             return kRoiInvalid;
+        const int dstH = rc.h;
         int st = kRoiOk;
-        const TableRef x = table_for(cache, out, true, b.w, &words, &st);
-        const TableRef y = x.t ? table_for(cache, out, false, b.h, &words, &st) : x;
+        const TableRef x = table_for(cache, out, true, b.w, rc.w, &words, &st);
+        const TableRef y = x.t ? table_for(cache, out, false, b.h, rc.h, &words, &st) : x;
         if (!y.t)
             return st;
         // a band row: its tap records and its work rows over the box's width and channels
@@ -232,7 +259,7 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
         const uint32_t g = static_cast<uint32_t>((dstH + rows - 1) / rows);
         const uint64_t off = static_cast<uint64_t>(b.frame) * frameSt + static_cast<uint64_t>(b.y) * srcSt +
                              static_cast<uint64_t>(b.x) * C;
-        uint32_t *r = out->rec.data() + i * kRoiRecWords;
+        uint32_t *r = out->rec.data() + i * recWords;
         r[kRFrame] = static_cast<uint32_t>(b.frame);
         r[kROffLo] = static_cast<uint32_t>(off);
         r[kROffHi] = static_cast<uint32_t>(off >> 32);
@@ -247,7 +274,7 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
         r[kRFirst] = static_cast<uint32_t>(groups);
         r[kRGroups] = g;
         r[kRPitch] = static_cast<uint32_t>(pitchDw);
-        groups += g;
+        groups += fit ? fit_words(r + kRoiFitExt, rc, cache->dstH(), g) : g;
         if (over_caps(groups, words))
             return kRoiUnsupported;
     }
@@ -257,11 +284,35 @@ int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *r
     return kRoiOk;
 }
 
-void roi_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena)
+void fill_packed(uint32_t magic, const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena)
 {
-    fill_common(kRoiMagic, cache, l, arena);
+    fill_common(magic, cache, l, arena);
     arena[kHChannels] = static_cast<uint32_t>(l.channels);
     arena[kHRowBytes] = static_cast<uint32_t>(frameW * static_cast<size_t>(l.channels));
+}
+
+} // namespace
+
+int roi_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, size_t nFrames, size_t frameW,
+               size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad)
+{
+    return layout_packed(false, cache, channels, nRois, rois, nullptr, nFrames, frameW, frameH, srcSt, frameSt, out, bad);
+}
+
+int roi_fit_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, const RoiRect *rects,
+                   size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad)
+{
+    return layout_packed(true, cache, channels, nRois, rois, rects, nFrames, frameW, frameH, srcSt, frameSt, out, bad);
+}
+
+void roi_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena)
+{
+    fill_packed(kRoiMagic, cache, l, frameW, arena);
+}
+
+void roi_fit_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena)
+{
+    fill_packed(kRoiFitMagic, cache, l, frameW, arena);
 }
 
 // ---------------------------------------------------------------- CPU twin
@@ -382,11 +433,29 @@ void store_pixel(const int px[4], int channels, const int order[4], const RoiNor
     }
 }
 
-} // namespace
-
-void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
-              void *dstV, const RoiNorm &n)
+// The rectangle of a record: the whole output (ext == nullptr: a stretch record), or its fit words
+RoiRect rect_in(const uint32_t *ext, int dstW, int dstH)
 {
+    if (!ext)
+        return RoiRect{0, 0, dstW, dstH};
+    return RoiRect{static_cast<int>(ext[kFOX]), static_cast<int>(ext[kFOY]), static_cast<int>(ext[kFIW]), static_cast<int>(ext[kFIH])};
+}
+
+// Every pixel of a dstW x dstH canvas outside rc: px
+void pad_canvas(const RoiRect &rc, int dstW, int dstH, const int px[4], int channels, const int order[4], const RoiNorm &n,
+                size_t planeSt, size_t dstSt, uint8_t *canvas)
+{
+    for (int y = 0; y < dstH; ++y)
+        for (int x = 0; x < dstW; ++x)
+            if (y < rc.y || y >= rc.y + rc.h || x < rc.x || x >= rc.x + rc.w)
+                store_pixel(px, channels, order, n, planeSt, canvas + static_cast<size_t>(y) * dstSt, x);
+}
+
+// roi_walk (pad == nullptr: stretch records) and roi_fit_walk
+void walk_packed(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+                 void *dstV, const RoiNorm &n, const uint8_t *pad)
+{
+    const size_t recWords = pad ? kRoiFitRecWords : kRoiRecWords;
     const int nRois = static_cast<int>(arena[kHRois]);
     const int dstW = static_cast<int>(arena[kHDstW]), dstH = static_cast<int>(arena[kHDstH]);
     const int C = static_cast<int>(arena[kHChannels]);
@@ -396,29 +465,54 @@ void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t ds
     std::vector<uint16_t> work;
     std::vector<uint8_t> line(static_cast<size_t>(C) * dstW);
     for (int i = 0; i < nRois; ++i) {
-        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * kRoiRecWords;
+        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * recWords;
         const uint8_t *box = src + ((static_cast<uint64_t>(r[kROffHi]) << 32) | r[kROffLo]);
         const int w = static_cast<int>(r[kRW]);
         const bool flip = r[kRFlags] & 1u;
         const uint32_t *xt = arena + r[kRXTab], *yt = arena + r[kRYTab];
-        for (int y = 0; y < dstH; ++y) {
+        const RoiRect rc = rect_in(pad ? r + kRoiFitExt : nullptr, dstW, dstH);
+        uint8_t *canvas = dst + static_cast<size_t>(i) * dstRoiSt;
+        if (pad) {
+            const int px[4] = {pad[0], pad[1], pad[2], pad[3]};
+            pad_canvas(rc, dstW, dstH, px, C, order, n, planeSt, dstSt, canvas);
+        }
+        for (int y = 0; y < rc.h; ++y) {
             for (int c = 0; c < C; ++c)
-                component_row(xt, yt, dstW, dstH, LZ, box + c, srcSt, C, w, y, &work, line.data() + static_cast<size_t>(c) * dstW);
-            uint8_t *o = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt;
-            for (int x = 0; x < dstW; ++x) {
+                component_row(xt, yt, rc.w, rc.h, LZ, box + c, srcSt, C, w, y, &work, line.data() + static_cast<size_t>(c) * rc.w);
+            uint8_t *o = canvas + static_cast<size_t>(rc.y + y) * dstSt;
+            for (int x = 0; x < rc.w; ++x) {
                 int px[4] = {0, 0, 0, 0};
                 for (int c = 0; c < C; ++c)
-                    px[c] = line[static_cast<size_t>(c) * dstW + x];
-                store_pixel(px, C, order, n, planeSt, o, flip ? dstW - 1 - x : x);
+                    px[c] = line[static_cast<size_t>(c) * rc.w + x];
+                store_pixel(px, C, order, n, planeSt, o, rc.x + (flip ? rc.w - 1 - x : x));
             }
         }
     }
 }
 
+} // namespace
+
+void roi_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+              void *dst, const RoiNorm &n)
+{
+    walk_packed(arena, src, srcSt, dstSt, planeSt, dstRoiSt, dst, n, nullptr);
+}
+
+void roi_fit_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+                  void *dst, const RoiNorm &n, const uint8_t pad[4])
+{
+    walk_packed(arena, src, srcSt, dstSt, planeSt, dstRoiSt, dst, n, pad);
+}
+
 // ---------------------------------------------------------------- boxes of NV12 / I420 frames to RGB
 
-int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, RoiLayout *out, int *bad)
+namespace {
+
+// roi_yuv_layout (fit == false: every box to the whole output, stretch records) and roi_yuv_fit_layout
+int layout_yuv(bool fit, RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, const RoiRect *rects,
+               RoiLayout *out, int *bad)
 {
+    const size_t recWords = fit ? kRoiYuvFitRecWords : kRoiYuvRecWords;
     out->reset();
     *bad = -1;
     const bool nv12 = s.layout == kRoiNv12;
@@ -433,16 +527,18 @@ int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const
         return kRoiUnsupported;
     out->nRois = static_cast<int>(nRois);
     out->channels = s.layout;
-    out->rec.assign(nRois * kRoiYuvRecWords, 0u);
-    size_t words = kRoiHdrWords + nRois * kRoiYuvRecWords;
+    out->rec.assign(nRois * recWords, 0u);
+    size_t words = kRoiHdrWords + nRois * recWords;
     uint64_t groups = 0;
-    const int dstW = cache->dstW(), dstH = cache->dstH();
     const bool linear = cache->method() == kLinear;
     for (size_t i = 0; i < nRois; ++i) {
         const RoiBox &b = rois[i];
         *bad = static_cast<int>(i);
-        if (!box_in_frame(b, s.nFrames, s.frameW, s.frameH) || ((b.x | b.y | b.w | b.h) & 1))
+        RoiRect rc;
+        if (!box_in_frame(b, s.nFrames, s.frameW, s.frameH) || ((b.x | b.y | b.w | b.h) & 1) ||
+            !rect_of(fit ? rects : nullptr, i, cache->dstW(), cache->dstH(), &rc))
             return kRoiInvalid;
+        const int dstW = rc.w, dstH = rc.h;
         // Linear chroma above 2x has no pinned answer (the rule of the YUV plans' full-grid chroma)
         if (linear && (dstW > b.w || dstH > b.h))
             return kRoiUnsupported;
@@ -450,7 +546,7 @@ int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const
         TableRef t[4];
         int st = kRoiOk;
         for (int k = 0; k < 4; ++k) {
-            t[k] = table_for(cache, out, !(k & 1), ((k & 1) ? b.h : b.w) >> (k >> 1), &words, &st);
+            t[k] = table_for(cache, out, !(k & 1), ((k & 1) ? b.h : b.w) >> (k >> 1), (k & 1) ? dstH : dstW, &words, &st);
             if (!t[k].t)
                 return st;
         }
@@ -463,7 +559,7 @@ int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const
         const uint64_t frame = static_cast<uint64_t>(b.frame) * s.frameSt;
         const uint64_t off = frame + static_cast<uint64_t>(b.y) * s.stY + static_cast<uint64_t>(b.x);
         const uint64_t offC = frame + static_cast<uint64_t>(b.y / 2) * s.stUV + static_cast<uint64_t>(nv12 ? b.x : b.x / 2);
-        uint32_t *r = out->rec.data() + i * kRoiYuvRecWords;
+        uint32_t *r = out->rec.data() + i * recWords;
         r[kYFrame] = static_cast<uint32_t>(b.frame);
         r[kYOffLo] = static_cast<uint32_t>(off);
         r[kYOffHi] = static_cast<uint32_t>(off >> 32);
@@ -483,7 +579,7 @@ int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const
         r[kYGroups] = g;
         r[kYPitch] = static_cast<uint32_t>(pitchY);
         r[kYPitchC] = static_cast<uint32_t>(pitchC);
-        groups += g;
+        groups += fit ? fit_words(r + kRoiYuvFitExt, rc, cache->dstH(), g) : g;
         if (over_caps(groups, words))
             return kRoiUnsupported;
     }
@@ -493,9 +589,9 @@ int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const
     return kRoiOk;
 }
 
-void roi_yuv_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena)
+void fill_yuv(uint32_t magic, const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena)
 {
-    fill_common(kRoiYuvMagic, cache, l, arena);
+    fill_common(magic, cache, l, arena);
     arena[kHYLayout] = static_cast<uint32_t>(s.layout);
     arena[kHYRowBytes] = static_cast<uint32_t>(s.frameW);
     arena[kHYRowBytesC] = static_cast<uint32_t>(s.layout == kRoiNv12 ? s.frameW : s.frameW / 2);
@@ -503,9 +599,11 @@ void roi_yuv_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSr
     arena[kHYStC] = static_cast<uint32_t>(s.stUV);
 }
 
-void roi_yuv_walk(const uint32_t *arena, const uint8_t *yP, const uint8_t *uP, const uint8_t *vP, const RoiYuvOut &o,
-                  size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dstV)
+// roi_yuv_walk (pad == nullptr: stretch records) and roi_yuv_fit_walk
+void walk_yuv(const uint32_t *arena, const uint8_t *yP, const uint8_t *uP, const uint8_t *vP, const RoiYuvOut &o,
+              size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dstV, const uint8_t *pad)
 {
+    const size_t recWords = pad ? kRoiYuvFitRecWords : kRoiYuvRecWords;
     const int nRois = static_cast<int>(arena[kHRois]);
     const int dstW = static_cast<int>(arena[kHDstW]), dstH = static_cast<int>(arena[kHDstH]);
     const bool LZ = arena[kHLanczos] != 0, nv12 = arena[kHYLayout] == static_cast<uint32_t>(kRoiNv12);
@@ -516,25 +614,84 @@ void roi_yuv_walk(const uint32_t *arena, const uint8_t *yP, const uint8_t *uP, c
     std::vector<uint8_t> line(3 * static_cast<size_t>(dstW));
     uint8_t *Y = line.data(), *U = Y + dstW, *V = U + dstW;
     for (int i = 0; i < nRois; ++i) {
-        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * kRoiYuvRecWords;
+        const uint32_t *r = arena + arena[kHRecOff] + static_cast<size_t>(i) * recWords;
         const uint64_t off = (static_cast<uint64_t>(r[kYOffHi]) << 32) | r[kYOffLo];
         const uint64_t offC = (static_cast<uint64_t>(r[kYOffCHi]) << 32) | r[kYOffCLo];
         const int w = static_cast<int>(r[kYW]);
         const bool flip = r[kYFlags] & 1u;
         const uint32_t *xt = arena + r[kYXTab], *yt = arena + r[kYYTab];
         const uint32_t *xtC = arena + r[kYXTabC], *ytC = arena + r[kYYTabC];
-        for (int y = 0; y < dstH; ++y) {
-            component_row(xt, yt, dstW, dstH, LZ, yP + off, stY, 1, w, y, &work, Y);
-            component_row(xtC, ytC, dstW, dstH, LZ, uP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, U);
-            component_row(xtC, ytC, dstW, dstH, LZ, nv12 ? uP + offC + 1 : vP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, V);
-            uint8_t *e = dst + static_cast<size_t>(i) * dstRoiSt + static_cast<size_t>(y) * dstSt;
-            for (int x = 0; x < dstW; ++x) {
+        const RoiRect rc = rect_in(pad ? r + kRoiYuvFitExt : nullptr, dstW, dstH);
+        uint8_t *canvas = dst + static_cast<size_t>(i) * dstRoiSt;
+        if (pad) {
+            const int px[4] = {pad[0], pad[1], pad[2], 255};
+            pad_canvas(rc, dstW, dstH, px, o.channels, o.order, o.n, planeSt, dstSt, canvas);
+        }
+        for (int y = 0; y < rc.h; ++y) {
+            component_row(xt, yt, rc.w, rc.h, LZ, yP + off, stY, 1, w, y, &work, Y);
+            component_row(xtC, ytC, rc.w, rc.h, LZ, uP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, U);
+            component_row(xtC, ytC, rc.w, rc.h, LZ, nv12 ? uP + offC + 1 : vP + offC, stC, nv12 ? 2 : 1, w / 2, y, &work, V);
+            uint8_t *e = canvas + static_cast<size_t>(rc.y + y) * dstSt;
+            for (int x = 0; x < rc.w; ++x) {
                 int px[4] = {0, 0, 0, 255};
                 yuv_to_rgb(k, Y[x], yuv_chroma_terms(k, U[x], V[x]), px[0], px[1], px[2]);
-                store_pixel(px, o.channels, o.order, o.n, planeSt, e, flip ? dstW - 1 - x : x);
+                store_pixel(px, o.channels, o.order, o.n, planeSt, e, rc.x + (flip ? rc.w - 1 - x : x));
             }
         }
     }
+}
+
+} // namespace
+
+int roi_yuv_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, RoiLayout *out, int *bad)
+{
+    return layout_yuv(false, cache, s, nRois, rois, nullptr, out, bad);
+}
+
+int roi_yuv_fit_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, const RoiRect *rects,
+                       RoiLayout *out, int *bad)
+{
+    return layout_yuv(true, cache, s, nRois, rois, rects, out, bad);
+}
+
+void roi_yuv_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena)
+{
+    fill_yuv(kRoiYuvMagic, cache, l, s, arena);
+}
+
+void roi_yuv_fit_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena)
+{
+    fill_yuv(kRoiYuvFitMagic, cache, l, s, arena);
+}
+
+void roi_yuv_walk(const uint32_t *arena, const uint8_t *y, const uint8_t *u, const uint8_t *v, const RoiYuvOut &o,
+                  size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst)
+{
+    walk_yuv(arena, y, u, v, o, dstSt, planeSt, dstRoiSt, dst, nullptr);
+}
+
+void roi_yuv_fit_walk(const uint32_t *arena, const uint8_t *y, const uint8_t *u, const uint8_t *v, const RoiYuvOut &o,
+                      size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst, const uint8_t pad[4])
+{
+    walk_yuv(arena, y, u, v, o, dstSt, planeSt, dstRoiSt, dst, pad);
+}
+
+bool fit_rect(int mode, uint64_t w, uint64_t h, uint64_t dstW, uint64_t dstH, RoiRect *out)
+{
+    if (mode < kFitStretch || mode > kFitLetterboxTopLeft || !w || !h || !dstW || !dstH || w > (1u << 24) || h > (1u << 24) ||
+        dstW > (1u << 20) || dstH > (1u << 20))
+        return false;
+    uint64_t iw = dstW, ih = dstH;
+    if (mode != kFitStretch) {
+        if (w * dstH >= h * dstW)
+            ih = std::max<uint64_t>(1, (h * dstW + w / 2) / w);
+        else
+            iw = std::max<uint64_t>(1, (w * dstH + h / 2) / h);
+    }
+    const bool centred = mode == kFitLetterbox;
+    *out = RoiRect{centred ? static_cast<int>((dstW - iw) / 2) : 0, centred ? static_cast<int>((dstH - ih) / 2) : 0,
+                   static_cast<int>(iw), static_cast<int>(ih)};
+    return true;
 }
 
 } // namespace iqo_amd

@@ -79,9 +79,10 @@ struct RoiBox {
     int frame, x, y, w, h, flags;
 };
 
-// Host cache of axis tables in arena form, keyed by (axis, srcLen); dstLen, method and degree are the
-// owner's.  Least recently used tables are dropped beyond `cap` bytes (a table in use by the batch
-// being assembled stays alive through its shared_ptr).
+// Host cache of axis tables in arena form, keyed by (axis, srcLen, dstLen); method and degree are the
+// owner's (the stretch calls ask for the owner's dstW / dstH, the fit calls for a box's iw / ih).  Least
+// recently used tables are dropped beyond `cap` bytes (a table in use by the batch being assembled stays alive
+// through its shared_ptr).
 class RoiTableCache {
 public:
     typedef std::shared_ptr<const std::vector<uint32_t>> Table;
@@ -90,7 +91,7 @@ public:
     {
     }
     // nullptr (with *why: 0 invalid shape, 1 over kRoiMaxTaps) when the axis has no table
-    Table get(bool isX, int srcLen, int *why);
+    Table get(bool isX, int srcLen, int dstLen, int *why);
     size_t bytes() const { return bytes_; }
     size_t misses() const { return misses_; }
     void clear();
@@ -117,10 +118,10 @@ struct RoiLayout {
     int nXTables = 0, nYTables = 0;
     uint32_t groups = 0;       // total workgroups
     size_t ldsBytes = 0;       // dynamic LDS of the launch: the largest workgroup's
-    // per distinct length: table and its word offset in the arena
+    // per distinct (srcLen, dstLen): table and its word offset in the arena
     std::vector<std::pair<RoiTableCache::Table, uint32_t>> tables;
-    std::vector<uint32_t> rec;  // nRois x kRoiRecWords
-    std::vector<std::pair<int, int>> xIdx, yIdx;  // sorted (distinct length, index in tables)
+    std::vector<uint32_t> rec;  // nRois x the format's record words
+    std::vector<std::pair<uint64_t, int>> xIdx, yIdx;  // sorted (srcLen << 32 | dstLen, index in tables)
     void reset();               // empty, keeping the vectors' capacity from call to call
 };
 
@@ -210,5 +211,52 @@ struct RoiYuvOut {
 // CPU twin of roi_yuv_kernel.  NV12: u is the UV plane and v is not read.  Destination as roi_walk.
 void roi_yuv_walk(const uint32_t *arena, const uint8_t *y, const uint8_t *u, const uint8_t *v, const RoiYuvOut &o,
                   size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst);
+
+// ---------------------------------------------------------------- boxes into destination rectangles (fit)
+//
+// Output i of a fit call is a dstW x dstH canvas: rectangle (ox, oy, iw, ih) of it holds what the stretch call
+// gives for box i with (iw, ih) in place of (dstW, dstH) -- so its tables are those of (w -> iw) and (h -> ih),
+// from the same cache -- and every pixel outside it is the call's pad colour.  Both families have a fit format of
+// their own, so the stretch arenas stay word for word what they were: the same header, and records that begin
+// with the stretch record's words and carry RoiFitRec from word kRoiFitExt (YUV: kRoiYuvFitExt) on.
+//
+// Who writes which pad byte: a band workgroup (one of ceil(ih / rows), rows from band_rows(ih, ...)) writes the
+// pad columns left and right of its own rows; the rows above and below the rectangle are written by pad
+// workgroups of the same launch, kRoiPadRows whole rows each, ceil(oy / kRoiPadRows) above and
+// ceil((dstH - oy - ih) / kRoiPadRows) below.  A box's workgroups are numbered from its kRFirst: pad above, bands,
+// pad below.  The pad colour is an argument of the call, not of the arena.
+constexpr int kRoiFitRecWords = 24, kRoiFitExt = 16;
+constexpr int kRoiYuvFitRecWords = 32, kRoiYuvFitExt = 24;
+constexpr uint32_t kRoiFitMagic = 0x494f5232u;     // "IOR2"
+constexpr uint32_t kRoiYuvFitMagic = 0x494f5932u;  // "IOY2"
+// Rows of the canvas one pad workgroup writes.  NOT MEASURED: 32 keeps a workgroup's share of a 640-wide fp16
+// RGB canvas near 120 KB and gives a 140-row border five workgroups; nobody has timed other values.
+constexpr int kRoiPadRows = 32;
+enum RoiFitRec { kFIW = 0, kFIH, kFOX, kFOY, kFPadAbove, kFPadBelow };  // words from the format's Ext on
+
+struct RoiRect {
+    int x, y, w, h;
+};
+
+// roi_layout / roi_fill / roi_walk of the fit formats.  rects: nRois rectangles, or nullptr (every rectangle is
+// the whole output).  A rectangle outside the output or with w or h below 1 is kRoiInvalid at its box; the
+// stretch rules hold with (iw, ih) for (dstW, dstH).  pad: the bytes of the channels (packed) or R, G, B (YUV,
+// stored through the output's order as a pixel is; the fourth byte of a 4-byte pixel stays 255).
+int roi_fit_layout(RoiTableCache *cache, int channels, size_t nRois, const RoiBox *rois, const RoiRect *rects,
+                   size_t nFrames, size_t frameW, size_t frameH, size_t srcSt, size_t frameSt, RoiLayout *out, int *bad);
+void roi_fit_fill(const RoiTableCache &cache, const RoiLayout &l, size_t frameW, uint32_t *arena);
+void roi_fit_walk(const uint32_t *arena, const uint8_t *src, size_t srcSt, size_t dstSt, size_t planeSt, size_t dstRoiSt,
+                  void *dst, const RoiNorm &n, const uint8_t pad[4]);
+int roi_yuv_fit_layout(RoiTableCache *cache, const RoiYuvSrc &s, size_t nRois, const RoiBox *rois, const RoiRect *rects,
+                       RoiLayout *out, int *bad);
+void roi_yuv_fit_fill(const RoiTableCache &cache, const RoiLayout &l, const RoiYuvSrc &s, uint32_t *arena);
+void roi_yuv_fit_walk(const uint32_t *arena, const uint8_t *y, const uint8_t *u, const uint8_t *v, const RoiYuvOut &o,
+                      size_t dstSt, size_t planeSt, size_t dstRoiSt, void *dst, const uint8_t pad[4]);
+
+// The rectangle of a w x h box in a dstW x dstH output, in 64-bit integers: if w * dstH >= h * dstW then
+// iw = dstW, ih = max(1, (h * dstW + w / 2) / w), else ih = dstH, iw = max(1, (w * dstH + h / 2) / h); centred
+// (ox = (dstW - iw) / 2, oy = (dstH - ih) / 2) or at the top left.  mode 0: the whole output.
+enum { kFitStretch = 0, kFitLetterbox = 1, kFitLetterboxTopLeft = 2 };
+bool fit_rect(int mode, uint64_t w, uint64_t h, uint64_t dstW, uint64_t dstH, RoiRect *out);
 
 } // namespace iqo_amd
